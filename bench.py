@@ -14,13 +14,20 @@ Contract: `python bench.py --gpus N --steps K --warmup W`.  N > 1: one rank per 
 (`python -m torch.distributed.run ...`, launch_workers below) BEFORE it touches the GPU and relays rank 0's line;
 W untimed warm-up steps, then exactly K timed steps between barrier + synchronize, MAX over ranks,
 rank 0 prints ONE JSON line.  `value` = whole-job dequant GB/s (algorithmic bytes, inputs resident
-in HBM); the GEMV figures, the HIP-event roofline of the dequant kernel and a pure-torch CPU
-dequant baseline timed on the host cores ride along in the same line.  No data-path collective:
-rows of W are independent, so ranks process independent shards (weak scaling).
+in HBM); `ms_per_step` = wall milliseconds of one timed step; the GEMV figures and the HIP-event
+roofline of both kernels ride along in the same line.  No data-path collective: rows of W are
+independent, so ranks process independent shards (weak scaling).
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  `--full` adds everything
+else, outside the timed region and in the same line: a pure-torch CPU dequant baseline timed on the host
+cores, hot / other-dtype / small-batch / stacked / quantiser figures, the box's bare stream rates, the
+fused epilogues, the C3 / C4 legs and, for N > 1, the group evidence and the K-split / strong-split / C5 legs.
+`--dump-outputs DIR` writes what the timed path computed in its last step (float32 .npy, see dump_outputs);
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 stdout carries the ONE JSON line and nothing else (claim_stdout: RCCL's version banner, gloo's notes and every other print go to stderr).
 
-Environment switches (all optional; none changes the timed region):
+Environment switches (all optional; none changes the timed region; the leg switches act under --full):
   FP4_BENCH_BACKEND=gloo      N > 1 with the ranks SHARING devices and gloo standing in for RCCL (one-GPU rehearsal of the N > 1 path)
   FP4_BENCH_FORCE_GROUP=1     take the N > 1 code path with one rank (the only way through real RCCL on a one-GPU box)
   FP4_BENCH_C3=0              skip the sanity-MLP leg (BASELINE config 3: the reference's published table, re-measured; N = 1)
@@ -772,6 +779,51 @@ def time_replays(replay, reps, launches):
     return statistics.median(out), out
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files of all ranks together (.npy headers included)
+DUMP_SAMPLE_SEED = 20260101
+
+
+def dump_plan(rows, row_len, budget):
+    """How many elements of each of `rows` equally long outputs fit in `budget` bytes as float32: all of them, or a fixed sample."""
+    return max(1, min(row_len, budget // (4 * rows)))
+
+
+def sample_positions(n, count, seed=DUMP_SAMPLE_SEED):
+    """`count` distinct positions in [0, n), sorted, the same in every run (numpy's seeded generator, independent of torch and the GPU)."""
+    import numpy as np
+
+    if count >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=count, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, named, rank=0, world=1, limit=DUMP_LIMIT_BYTES):
+    """Writes what a caller of the timed path receives: `named` maps a name to a list of equally shaped output tensors (one per
+    weight), saved as `out_dir/<name>.npy` (float32, one row per tensor; ranks > 0 add `_rank<r>`).  The outputs of one rank share
+    limit / world bytes, split evenly between the names; a name whose outputs do not fit is saved as the same seeded sample of
+    positions in every tensor (`<name>_sample`).  Returns {file name: bytes}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    per_name = (limit // world - 1024 * len(named)) // len(named)  # (1 KiB per file for the .npy header, generously)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    written = {}
+    for name, tensors in named.items():
+        n = tensors[0].numel()
+        assert all(t.numel() == n for t in tensors), name
+        count = dump_plan(len(tensors), n, per_name)
+        if count < n:
+            pos = torch.from_numpy(sample_positions(n, count)).to(tensors[0].device)
+            rows, name = [t.reshape(-1).index_select(0, pos) for t in tensors], name + "_sample"
+        else:
+            rows = [t.reshape(-1) for t in tensors]
+        arr = np.ascontiguousarray(torch.stack(rows).float().cpu().numpy())
+        path = os.path.join(out_dir, f"{name}{suffix}.npy")
+        np.save(path, arr)
+        written[os.path.basename(path)] = os.path.getsize(path)
+    return written
+
+
 def committed_traffic(prefix: str, profiles_dir: str | None = None, repo: str = REPO):
     """Per-launch HBM bytes of a kernel from the committed PMC profile (profiles/rNN_traffic*.json, produced by
     tools/pmc_traffic.py from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this very script): the
@@ -883,7 +935,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--matrices", type=int, default=64, help="distinct 4096x4096 FP4 weights per step (R)")
     ap.add_argument("--gemv-reps", type=int, default=4, help="GEMV passes over the R weights per step")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary leg (CPU baseline, other dtypes / sizes / configurations, box "
+                         "streams, C3 / C4, N > 1 group evidence and C5) into the same line; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (of --full)")
     ap.add_argument("--deadline", type=float, default=480.0,
                     help="N > 1 started without torchrun: seconds after which the worker group is killed and the run fails with a reason")
     args = ap.parse_args()
@@ -936,7 +993,7 @@ def main():
             print(f"bench.py: rank {rank}: process-group initialisation ({backend}) failed: {type(exc).__name__}: {exc}", file=sys.stderr, flush=True)
             raise
     proof = None
-    if grouped:
+    if grouped and args.full:
         try:
             proof = group_proof(dist, backend, rank, world, local, dev)
         except Exception as exc:  # (an error every rank meets alike must not cost the headline; a one-rank failure ends in the time-outs)
@@ -1065,8 +1122,9 @@ def main():
                 return {"median_us": round(q[1], 3), "iqr_us": round(q[2] - q[0], 3), "min_us": round(us[0], 3), "max_us": round(us[-1], 3)}
 
             if grouped:
-                # row e evidence: who took part (real collectives on the data-path backend) and how evenly the ranks ran
-                line["group"] = proof
+                # row e evidence: who took part (real collectives on the data-path backend; --full) and how evenly the ranks ran
+                if proof is not None:
+                    line["group"] = proof
                 dq_rates = [dq_b * dq_launches / t[0] / 1e9 for t in per_rank]
                 gv_us_r = [t[1] * 1e6 / gv_launches for t in per_rank]
                 line["per_rank"] = {
@@ -1078,11 +1136,16 @@ def main():
             line["dequant_step_spread"] = spread(dq_ms, R)
             line["gemv_step_spread"] = spread(gv_ms, R * GR)
             _WATCHDOG.provisional = line
+        if args.dump_outputs:
+            # the last timed step's outputs, before any secondary leg writes into the same buffers
+            written = dump_outputs(args.dump_outputs, {"dequant_out": outs, "gemv_out": ys}, rank, world)
+            print(f"bench.py: rank {rank}: wrote {', '.join(written)} ({sum(written.values()) / 1e6:.1f} MB) to {args.dump_outputs}",
+                  file=sys.stderr, flush=True)
         stage("timed-region-done")
 
-        # ---- secondary figures (outside the timed region) ------------------------------------
+        # ---- secondary figures (--full; outside the timed region) ----------------------------
         extra = {}
-        if grouped:
+        if grouped and args.full:
             try:
                 extra["tp_ksplit"] = tp_ksplit_leg(lib, dist, backend, rank, world, dev, x, packed[0], absmax[0], barrier)
             except Exception as exc:  # never let the optional leg take the headline line down
@@ -1096,7 +1159,7 @@ def main():
                     extra["c5_llama3_8b_tp"] = c5_leg(dist, backend, rank, world, dev, barrier)
                 except Exception as exc:
                     extra["c5_llama3_8b_tp"] = {"error": repr(exc)[:300]}
-        if rank == 0:
+        if rank == 0 and args.full:
             hot_dq = capture(lambda: [lib.dequant(packed[0], absmax[0], outs[0], n) for _ in range(32)])
             hot_gv = capture(lambda: [lib.gemv(x, packed[0], absmax[0], ys[0], M, K) for _ in range(128)])
             extra["dequant_hot_us"] = round(time_replays(hot_dq, 10, 32)[0], 3)
@@ -1265,7 +1328,7 @@ def main():
                                      "direction) is the one meant as a ceiling; `frac` stays against the 8 TB/s spec (DESIGN.md section 3)")
         if "dequant_plus_hipblaslt_gemv_us" in extra:
             line["fused_gemv_speedup_vs_dequant_hipblaslt"] = round(extra["dequant_plus_hipblaslt_gemv_us"] / gv_us, 2)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline()
         _WATCHDOG.provisional = None
         print_result(line)

@@ -26,7 +26,7 @@ def _run(args, env_extra):
 
 
 def test_single_gpu_line_schema():
-    rec = _run(["--steps", "2", "--warmup", "1", "--matrices", "8", "--no-cpu"], {"FP4_BENCH_C4_LAYERS": "2"})
+    rec = _run(["--full", "--steps", "2", "--warmup", "1", "--matrices", "8", "--no-cpu"], {"FP4_BENCH_C4_LAYERS": "2"})
     assert SCHEMA <= set(rec) and rec["n_gpus"] == 1 and rec["steps"] == 2 and rec["unit"] == "GB/s" and rec["dtype"] == "bf16"
     r = rec["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
@@ -74,6 +74,41 @@ def test_single_gpu_line_schema():
     assert 1.0 < gv["box_bare_read_same_bytes_us"] < gv["avg_launch_us"] * 1.5 and 0.3 < gv["frac_of_box_bare_read_per_launch"] < 1.5, gv
 
 
+FULL_ONLY = {"cpu_baseline", "dequant_hot_us", "gemv_hot_us", "dequant_plus_hipblaslt_gemv_us", "dequant_f16_us", "dequant_f32_us",
+             "small_batch_us_by_rows", "quantize_bf16_us", "dequant_stack_of_R_one_launch_gbps", "gemv_python_op_us", "device_copy_gbps",
+             "box_stream_gbps", "fused_epilogue_us", "c3_sanity_mlp", "c4_mistral7b_decode", "roofline_quantize", "group", "tp_ksplit",
+             "strong_scaling_row_split", "c5_llama3_8b_tp"}
+
+
+def test_a_plain_run_times_its_steps_only_and_dumps_what_they_computed(tmp_path):
+    """Without --full the line carries the headline and nothing that needs runs of its own; --dump-outputs writes the last timed
+    step's outputs (the R bf16 dequants, as a seeded sample, and the R GEMV results) as float32 within 64 MB, and the same
+    arguments give the same arrays."""
+    import time
+
+    import numpy as np
+
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        t0 = time.monotonic()
+        rec = _run(["--steps", "3", "--warmup", "1", "--matrices", "8", "--dump-outputs", str(d)], {})
+        outside = time.monotonic() - t0 - (3 + 1) * rec["ms_per_step"] / 1e3
+        assert SCHEMA <= set(rec) and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0, rec
+        assert not FULL_ONLY & set(rec) and "box_stream_gbps" not in rec["roofline"], sorted(FULL_ONLY & set(rec))
+        assert outside < 30, outside  # the plain run's set-up, warm-up bookkeeping, dump and exit
+        names = sorted(os.listdir(d))
+        assert names == ["dequant_out_sample.npy", "gemv_out.npy"], names
+        assert sum(os.path.getsize(d / n) for n in names) <= 64 * 10**6
+        arrs = {n: np.load(d / n) for n in names}
+        dq, gv = arrs["dequant_out_sample.npy"], arrs["gemv_out.npy"]
+        assert dq.dtype == gv.dtype == np.float32 and gv.shape == (8, 4096) and dq.shape[0] == 8 and 0 < dq.shape[1] < 4096 * 4096
+        assert np.isfinite(dq).all() and np.isfinite(gv).all() and np.abs(dq).max() > 0 and np.abs(gv).max() > 0
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def test_the_stream_probe_moves_the_bytes_it_claims():
     """tools/libfp4_stream_probe.so is a measuring stick: its figure only means something if every launch really touches every byte it
     is credited with - copy mode reproduces its input, the write modes leave no byte of a sentinel-filled buffer unwritten."""
@@ -109,7 +144,7 @@ def test_the_stream_probe_moves_the_bytes_it_claims():
 
 
 def test_two_ranks_self_launched_over_gloo():
-    rec = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--matrices", "8"],
+    rec = _run(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--matrices", "8"],
                {"FP4_BENCH_BACKEND": "gloo", "FP4_BENCH_C5_LAYERS": "2"})
     assert SCHEMA <= set(rec) and rec["n_gpus"] == 2 and rec["scaling"] == "weak"
     assert "error" not in rec["tp_ksplit"], rec["tp_ksplit"]
@@ -147,7 +182,7 @@ def test_two_ranks_started_the_way_the_driver_starts_them():
     env = {k: v for k, v in os.environ.items() if k not in ("HSA_ENABLE_IPC_MODE_LEGACY", "WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(FP4_BENCH_BACKEND="gloo", FP4_BENCH_C5_LAYERS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--matrices", "8"]
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--matrices", "8"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:]
     # stdout carries ONE result line and nothing else: gloo's "[Gloo] Rank N is connected ..." chatter (and, with the nccl backend, RCCL's
@@ -173,7 +208,7 @@ def test_the_group_path_through_real_rccl_with_one_rank():
     fp4_hip_allreduce_oneshot) really are issued, `allreduces_per_token` times per token, over the one-rank group - the collective calls
     and dtypes of the 8-GPU run, issued through RCCL itself (what gloo rehearsals cannot show; what one rank cannot show is any data
     crossing a link: `collective_ranks` is 1)."""
-    rec = _run(["--steps", "2", "--warmup", "1", "--matrices", "8", "--no-cpu"],
+    rec = _run(["--full", "--steps", "2", "--warmup", "1", "--matrices", "8", "--no-cpu"],
                {"FP4_BENCH_FORCE_GROUP": "1", "FP4_BENCH_C5_LAYERS": "2", "FP4_BENCH_C4": "0"})
     g = rec["group"]
     assert g["backend"] == "nccl" and g["collective_library"].startswith("RCCL 2."), g

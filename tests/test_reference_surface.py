@@ -1,21 +1,18 @@
-"""Row b (the drop-in boundary) pinned by test instead of by reading: the reference's own Python and C++ are PARSED (never imported,
-nothing of them is copied) and every name it imports from `torch_bnb_fp4_ext`, every call site's positional arity and every
-parameter type of the seven bound functions is checked against the signatures pybind11 prints for this build's extension.
+"""Row b (the drop-in boundary) pinned by test instead of by reading: every name the reference imports from `torch_bnb_fp4_ext`,
+every call site's positional arity and every parameter type of the seven bound functions is checked against the signatures
+pybind11 prints for this build's extension, and the reference's Python surface against this package's.
 
-/root/reference exists in the build container only - it never travels to the GPU box - so these tests skip where it is absent."""
-import ast
+The reference checkout is not part of this repository: its Python and C++ were PARSED once (never imported, nothing of them is
+copied) into the data fixture tests/golden/reference_surface.json (tests/golden/make_reference_surface.py), which these tests read."""
+import json
 import os
 import re
 
-import pytest
 import torch  # noqa: F401
 
 import torch_bnb_fp4 as pkg
 
-REF = "/root/reference"
-REF_INIT = os.path.join(REF, "torch_bnb_fp4", "__init__.py")
-REF_CPP = os.path.join(REF, "csrc", "torch_fp4.cpp")
-needs_reference = pytest.mark.skipif(not (os.path.exists(REF_INIT) and os.path.exists(REF_CPP)), reason="the reference checkout is not on this machine")
+SURFACE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_surface.json")
 
 # C++ parameter type of the reference's bound functions -> the type pybind11 prints for the same position
 CPP_TO_PYBIND = {"torch::Tensor": "torch.Tensor", "int": "typing.SupportsInt", "ScalarTypeEnum": "torch_bnb_fp4_ext.ScalarType",
@@ -49,68 +46,52 @@ def pybind_signature(fn):
     return m.group(1), types, m.group(3).strip()
 
 
+def reference_surface():
+    with open(SURFACE) as f:
+        return json.load(f)
+
+
 def reference_ext_imports():
     """{local alias: extension attribute} for every `from torch_bnb_fp4_ext import X as Y` of the reference package (:11-18)."""
-    tree = ast.parse(open(REF_INIT).read())
-    out = {}
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ImportFrom) and node.module == "torch_bnb_fp4_ext":
-            for a in node.names:
-                out[a.asname or a.name] = a.name
-        elif isinstance(node, ast.Import):
-            assert all(a.name != "torch_bnb_fp4_ext" for a in node.names), "module-style import: extend this test"
-    return tree, out
+    return reference_surface()["ext_imports"]
 
 
-@needs_reference
 def test_every_extension_name_the_reference_imports_exists_here():
-    _, imports = reference_ext_imports()
+    imports = reference_ext_imports()
     assert set(imports.values()) == {"ScalarType", "dequantize_fp4", "gemv_fp4", "qlinear", "qlinear_bias", "dequantize_fp4_codebook",
                                      "qlinear_codebook", "qlinear_codebook_bias"}, imports  # reference __init__.py:11-18
     for attr in imports.values():
         assert hasattr(pkg.ext, attr), attr
     # the enum members the reference's Python enum re-exports (:27-29) and their C++ numbering (torch_fp4.cpp:22-26)
-    tree, _ = reference_ext_imports()
-    members = {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "ScalarType_"}
+    members = set(reference_surface()["scalar_type_members"])
     assert members == {"bfloat16", "float16", "float32"}
     assert {k: int(v) for k, v in pkg.ext.ScalarType.__members__.items()} == {"float16": 0, "float32": 1, "bfloat16": 2}
 
 
-@needs_reference
 def test_every_reference_call_site_fits_the_bound_signature():
-    tree, imports = reference_ext_imports()
-    calls = [n for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id in imports
-             and imports[n.func.id] != "ScalarType"]
+    imports = reference_ext_imports()
+    calls = reference_surface()["ext_call_sites"]
     seen = {}
     for c in calls:
-        attr = imports[c.func.id]
+        attr, line = c["function"], c["line"]
+        assert attr in imports.values() and attr != "ScalarType", c
         _, types, ret = pybind_signature(getattr(pkg.ext, attr))
-        assert not c.keywords, f"reference line {c.lineno}: keyword arguments cannot reach a positional pybind binding"
-        assert not any(isinstance(a, ast.Starred) for a in c.args), c.lineno
-        assert len(c.args) == len(types), f"reference line {c.lineno}: {attr} called with {len(c.args)} arguments, bound with {len(types)}"
+        assert not c["keyword_args"], f"reference line {line}: keyword arguments cannot reach a positional pybind binding"
+        assert not c["starred"], line
+        assert c["positional_args"] == len(types), f"reference line {line}: {attr} called with {c['positional_args']} arguments, bound with {len(types)}"
         assert ret == "torch.Tensor"
-        seen.setdefault(attr, []).append(c.lineno)
+        seen.setdefault(attr, []).append(line)
     # SURVEY 8b: the wrappers (:119,159,208,255,295,330) and the qlinear family (:507,516,539,549); every function is called somewhere
     assert set(seen) == set(imports.values()) - {"ScalarType"}, seen
     assert sum(len(v) for v in seen.values()) == 10, seen
 
 
 def reference_cpp_bindings():
-    """{python name: [C++ parameter types]} from PYBIND11_MODULE's m.def lines and the definitions they point at."""
-    text = open(REF_CPP).read()
-    text = re.sub(r"//[^\n]*", "", text)
-    defs = dict(re.findall(r'm\.def\(\s*"(\w+)"\s*,\s*&(\w+)', text))
-    enum_values = re.findall(r'\.value\(\s*"(\w+)"', text)
-    out = {}
-    for py_name, cpp_name in defs.items():
-        m = re.search(r"torch::Tensor\s+" + cpp_name + r"\s*\(([^)]*)\)\s*\{", text)
-        assert m, cpp_name
-        params = [p.strip() for p in m.group(1).split(",") if p.strip()]
-        out[py_name] = [p.rsplit(None, 1)[0].replace("const ", "").replace("&", "").strip() for p in params]
-    return out, enum_values
+    """{python name: [C++ parameter types]} from PYBIND11_MODULE's m.def lines and the definitions they point at, and the enum's values."""
+    rec = reference_surface()
+    return rec["cpp_bindings"], rec["cpp_enum_values"]
 
 
-@needs_reference
 def test_the_seven_bound_functions_have_the_reference_parameter_types_in_order():
     bindings, enum_values = reference_cpp_bindings()
     assert sorted(bindings) == sorted(["dequantize_fp4", "dequantize_fp4_codebook", "gemv_fp4", "qlinear", "qlinear_bias", "qlinear_codebook",
@@ -189,17 +170,10 @@ def test_a_profile_without_digests_is_reported_stale(tmp_path):
 
 # ---- the Python surface (functions, classes, methods, parameter names, defaults) ----------------------------------------------------
 
-def _ref_params(fn: ast.FunctionDef):
-    a = fn.args
-    names = [x.arg for x in a.posonlyargs + a.args if x.arg not in ("self", "cls")]
-    defaults = {}
-    pos = [x.arg for x in a.posonlyargs + a.args]
-    for name, d in zip(pos[len(pos) - len(a.defaults):], a.defaults):
-        try:
-            defaults[name] = ast.literal_eval(d)
-        except (ValueError, SyntaxError):
-            defaults[name] = ast.unparse(d)  # an expression (torch.float16, torch.device(...)): compared as text below
-    return names, defaults
+def _ref_params(entry):
+    """(parameter names, {name: default}) of one recorded reference function; a default that is an expression is kept as its text."""
+    defaults = {name: d["literal"] if "literal" in d else d["expression"] for name, d in entry["defaults"].items()}
+    return entry["params"], defaults
 
 
 def _our_params(obj):
@@ -226,25 +200,22 @@ def _same_default(ref, ours) -> bool:
     return ref == ours
 
 
-@needs_reference
 def test_python_surface_is_a_superset_of_the_reference_package():
     """Every module-level function and every method of ScalarType / QuantData / TorchFP4Linear in the reference's
     torch_bnb_fp4/__init__.py exists here under the same name, takes the same leading positional parameters BY NAME (keyword calls keep
     working) and has the same default values; extra trailing parameters with defaults are allowed (this package's opt-in extensions)."""
     import inspect
 
-    tree = ast.parse(open(REF_INIT).read())
     checked = 0
-    for node in tree.body:
+    for entry in reference_surface()["python_surface"]:
         targets = []
-        if isinstance(node, ast.FunctionDef):
-            targets.append((node.name, node, getattr(pkg, node.name, None)))
-        elif isinstance(node, ast.ClassDef):
-            cls = getattr(pkg, node.name, None)
-            assert cls is not None, f"class {node.name} is missing"
-            for m in node.body:
-                if isinstance(m, ast.FunctionDef):
-                    targets.append((f"{node.name}.{m.name}", m, inspect.getattr_static(cls, m.name, None)))
+        if entry["class"] is None:
+            targets.append((entry["name"], entry, getattr(pkg, entry["name"], None)))
+        elif entry["name"] is None:
+            assert getattr(pkg, entry["class"], None) is not None, f"class {entry['class']} is missing"
+        else:
+            cls = getattr(pkg, entry["class"])
+            targets.append((f"{entry['class']}.{entry['name']}", entry, inspect.getattr_static(cls, entry["name"], None)))
         for name, ref_fn, ours in targets:
             assert ours is not None, f"{name} is missing"
             if isinstance(ours, property):

@@ -37,7 +37,7 @@ def per_kernel(path, counter):
 
 fetch = per_kernel(sys.argv[1], "FETCH_SIZE")
 write = per_kernel(sys.argv[2], "WRITE_SIZE")
-out = {"_method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `python bench.py --no-cpu "
+out = {"_method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `python bench.py --full --no-cpu "
                   "--steps 3 --warmup 1`; per-launch means; FETCH_SIZE doubled (gfx950 tallies 128-B requests at 64 B), WRITE_SIZE as is; KB = 1024 B"}
 # the sources these counters were taken from (the profile runs from the tree it sits in): bench.py marks the figure stale when they change
 out["_source_sha256"] = file_digests()
