@@ -36,10 +36,11 @@ extern "C" {
 enum fp4_dtype { FP4_DTYPE_F16 = 0, FP4_DTYPE_F32 = 1, FP4_DTYPE_BF16 = 2 };
 
 /* Which 16-entry code table a dequant uses.
+ * NF4      = bitsandbytes' NF4 code (see "NF4" below), nibble used as the index, no sign bit;
  * CODEBOOK = the CODE_PARAM literals (csrc/dequant_fp4_optimized.cu:28-46),
  * TREE     = the constants of dequantize_fp4_tree (csrc/dequant_fp4_optimized.cu:55-76);
  * they differ by 1-12 ulp in f32 for nibbles 1,4,6 (and 9,12,14). */
-enum fp4_table { FP4_TABLE_CODEBOOK = 0, FP4_TABLE_TREE = 1 };
+enum fp4_table { FP4_TABLE_CODEBOOK = 0, FP4_TABLE_TREE = 1, FP4_TABLE_NF4 = 2 };
 
 /* Cache policy of the dequant's output stream.  AUTO = non-temporal loads and stores for large outputs (fastest
  * when the result is not read back at once: +30 % at 4096x4096); KEEP_CACHED = plain stores, for a consumer that
@@ -57,7 +58,7 @@ enum fp4_status {
 FP4_HIP_API int fp4_hip_abi_version(void);
 FP4_HIP_API const char *fp4_hip_last_error(void);
 
-/* Host-side copy of a code table (16 floats; nibble bit 3 = sign). */
+/* Host-side copy of a code table (16 floats; CODEBOOK / TREE: nibble bit 3 = sign; NF4: plain index). */
 FP4_HIP_API int fp4_hip_code_table(int table, float out16[16]);
 
 /*
@@ -216,8 +217,30 @@ FP4_HIP_API int fp4_hip_quantize_blockwise(const void *w, int w_dtype, uint8_t *
                                void *stream);
 
 /*
+ * NF4 -- bitsandbytes' second 4-bit code (quant_type "nf4"; QLoRA and most published bnb-4bit checkpoints).  Not in the
+ * reference.  These entry points and FP4_TABLE_NF4 are additions to ABI version 7: nothing a v7 caller already uses changed.
+ *   code (nibble 0..15, f32 rounding of the published decimals):
+ *     -1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635, -0.18477343022823334,
+ *     -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725, 0.24611230194568634, 0.33791524171829224,
+ *     0.44070982933044434, 0.5626170039176941, 0.7229568362236023, 1.0
+ *   Packing and absmax as for FP4 (even element in the high nibble, one f32 scale per block).  Dequant:
+ *   fp4_hip_dequantize_blockwise(..., table = FP4_TABLE_NF4, ...), out = RN_T(f32(code[nibble]) * absmax).
+ *
+ * fp4_hip_gemv_nf4: the batch-1 GEMV of fp4_hip_gemv over an NF4 weight; same arguments, shape coverage, bias rule
+ * (T(f32(T(sum)) + f32(bias)) for 16-bit T) and error codes.  The f32 code values are used as they are (f32 accumulation).
+ *
+ * fp4_hip_quantize_blockwise_nf4: arguments as fp4_hip_quantize_blockwise.  absmax = max|w|, x = w * (1/absmax) in f32,
+ *   nibble = #{ i : x > T[i] } over the 15 f32 midpoints T[i] = f32((code[i] + code[i+1]) / 2) (strict >; NaN -> 0, so an
+ *   all-zero block, 0 * inf, is 0x00 bytes and dequantises to -0.0: what bitsandbytes writes).
+ */
+FP4_HIP_API int fp4_hip_gemv_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out, int64_t M,
+                                 int64_t K, int blocksize, int dtype, void *stream);
+FP4_HIP_API int fp4_hip_quantize_blockwise_nf4(const void *w, int w_dtype, uint8_t *packed, float *absmax, int64_t n, int blocksize,
+                                               void *stream);
+
+/*
  * Tuning hook for benchmarks/sweeps: selects a kernel geometry by name
- * ("dequant", "gemv", "gemm_small", "gemm_wide" = rows per workgroup of the 17..64-row kernels (1 / 2 / 3 / 4 = 16 / 32 / 64 / 128, 5 = 16 with self-contained waves; 0 = off),
+ * ("dequant", "gemv", "gemv_nf4" (0 = 16-entry f32 table, 1 = 256-entry pair table), "gemm_small", "gemm_wide" = rows per workgroup of the 17..64-row kernels (1 / 2 / 3 / 4 = 16 / 32 / 64 / 128, 5 = 16 with self-contained waves; 0 = off),
  * "quantize": 1..999 = the persistent kernel with that many workgroups per CU, 1001 / 1002 / 1004 = the one-shot tiles kernel with 1 / 2 / 4 loads per lane).  variant < 0 (quantize: 0) restores the built-in heuristic.
  * Process-wide (relaxed atomics: safe to flip while other threads launch, each launch
  * reads it once); for sweeps and tests only, not part of the reference surface.

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""NF4 vs FP4 on one MI355X: per-launch HIP-event microseconds of dequant, batch-1 GEMV, NF4 dequant + hipBLASLt at batch 1 and the
+quantiser, at the decoder shapes; the GEMV's two LDS-table layouts (fp4_hip_set_variant("gemv_nf4", 0 / 1)); and a steady-state
+NF4 GEMV over a stack of distinct weights (no cache reuse) as a fraction of 8 TB/s.  Prints one JSON line.
+
+Timing as bench.py does it (its capture / time_replays helpers): R launches captured in one HIP graph, the median over replays,
+divided by R.  usage: python tools/nf4_bench.py [--reps 20] [--launches 20]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "torch-bnb-fp4_amd")]
+
+import torch  # noqa: E402
+
+import torch_bnb_fp4 as pkg  # noqa: E402
+from bench import capture, time_replays  # noqa: E402
+
+SHAPES = [(4096, 4096), (14336, 4096), (4096, 14336), (28672, 4096)]
+DT = {torch.float16: 0, torch.float32: 1, torch.bfloat16: 2}
+NAME = {torch.float16: "fp16", torch.float32: "f32", torch.bfloat16: "bf16"}
+TREE, NF4 = 1, 2
+BS = 64
+SPEC_BPS = 8e12
+
+
+def lib():
+    l = ctypes.CDLL(pkg.HIP_LIBRARY_PATH)
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    l.fp4_hip_dequantize_blockwise.argtypes = [vp, vp, vp, i32, i64, i32, i32, i32, vp]
+    for g in (l.fp4_hip_gemv, l.fp4_hip_gemv_nf4):
+        g.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+    for q in (l.fp4_hip_quantize_blockwise, l.fp4_hip_quantize_blockwise_nf4):
+        q.argtypes = [vp, i32, vp, vp, i64, i32, vp]
+    l.fp4_hip_set_variant.argtypes = [ctypes.c_char_p, i32]
+    return l
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--launches", type=int, default=20)
+    args = ap.parse_args()
+    L = lib()
+    dev = torch.device("cuda", 0)
+    s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(L.fp4_hip_last_error().decode())
+
+    def us(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        return round(time_replays(replay, args.reps, args.launches)[0], 2)
+
+    rows = []
+    for M, K in SHAPES:
+        n = M * K
+        torch.manual_seed(0)
+        w16 = (torch.randn(n, device=dev) * 0.02).to(torch.float16)
+        pk = {}
+        for qt, fn in (("fp4", L.fp4_hip_quantize_blockwise), ("nf4", L.fp4_hip_quantize_blockwise_nf4)):
+            packed = torch.empty(n // 2, dtype=torch.uint8, device=dev)
+            absmax = torch.empty(n // BS, dtype=torch.float32, device=dev)
+            check(fn(p_(w16), DT[torch.float16], p_(packed), p_(absmax), n, BS, s()))
+            pk[qt] = (packed, absmax)
+        del w16
+        for dtype in (torch.bfloat16, torch.float16, torch.float32):
+            r = {"M": M, "K": K, "dtype": NAME[dtype]}
+            out = torch.empty(n, dtype=dtype, device=dev)
+            x = torch.randn(K, device=dev).to(dtype)
+            y = torch.empty(M, dtype=dtype, device=dev)
+            for qt, table in (("fp4", TREE), ("nf4", NF4)):
+                packed, absmax = pk[qt]
+                r[f"dequant_{qt}_us"] = us(lambda: check(L.fp4_hip_dequantize_blockwise(p_(packed), p_(absmax), p_(out), BS, n, DT[dtype], table, 0, s())))
+                g = L.fp4_hip_gemv if qt == "fp4" else L.fp4_hip_gemv_nf4
+                r[f"gemv_{qt}_us"] = us(lambda: check(g(p_(x), p_(packed), p_(absmax), None, p_(y), M, K, BS, DT[dtype], s())))
+            del out
+            packed, absmax = pk["nf4"]
+            x2 = x.view(1, K)
+            r["nf4_dequant_hipblaslt_batch1_us"] = us(lambda: pkg.ext.qlinear_nf4(x2, packed, absmax, M, K, BS))
+            r["gemv_nf4_over_fp4"] = round(r["gemv_nf4_us"] / r["gemv_fp4_us"], 3)
+            r["dequant_nf4_over_fp4"] = round(r["dequant_nf4_us"] / r["dequant_fp4_us"], 3)
+            r["gemv_nf4_speedup_vs_dequant_gemm"] = round(r["nf4_dequant_hipblaslt_batch1_us"] / r["gemv_nf4_us"], 2)
+            if dtype == torch.bfloat16:  # LDS-table layout ablation of the NF4 GEMV
+                for v in (0, 1):
+                    L.fp4_hip_set_variant(b"gemv_nf4", v)
+                    r[f"gemv_nf4_table{v}_us"] = us(lambda: check(L.fp4_hip_gemv_nf4(p_(x), p_(packed), p_(absmax), None, p_(y), M, K, BS, DT[dtype], s())))
+                L.fp4_hip_set_variant(b"gemv_nf4", -1)
+            w = (torch.randn(n, device=dev) * 0.02).to(dtype)
+            qp = torch.empty(n // 2, dtype=torch.uint8, device=dev)
+            qa = torch.empty(n // BS, dtype=torch.float32, device=dev)
+            for qt, fn in (("fp4", L.fp4_hip_quantize_blockwise), ("nf4", L.fp4_hip_quantize_blockwise_nf4)):
+                r[f"quantize_{qt}_us"] = us(lambda: check(fn(p_(w), DT[dtype], p_(qp), p_(qa), n, BS, s())))
+            r["quantize_nf4_over_fp4"] = round(r["quantize_nf4_us"] / r["quantize_fp4_us"], 3)
+            del w, qp, qa
+            rows.append(r)
+        del pk
+
+    # steady state: one launch per weight over a stack of distinct tall weights (~1.9 GB of NF4 bytes, far beyond the caches)
+    M, K, depth = 28672, 4096, 32
+    stack = [torch.randint(0, 256, (M * K // 2,), dtype=torch.uint8, device=dev) for _ in range(depth)]
+    scales = [torch.rand(M * K // BS, device=dev) for _ in range(depth)]
+    x = torch.randn(K, device=dev).to(torch.bfloat16)
+    y = torch.empty(M, dtype=torch.bfloat16, device=dev)
+    replay = capture(lambda: [check(L.fp4_hip_gemv_nf4(p_(x), p_(pk_), p_(am), None, p_(y), M, K, BS, 2, s())) for pk_, am in zip(stack, scales)])
+    per = time_replays(replay, args.reps, depth)[0]
+    bytes_per = M * K // 2 + M * K // BS * 4 + K * 2 + M * 2
+    steady = {"M": M, "K": K, "dtype": "bf16", "weights": depth, "us_per_weight": round(per, 2),
+              "TBps": round(bytes_per / (per * 1e-6) / 1e12, 2), "fraction_of_8TBps": round(bytes_per / (per * 1e-6) / SPEC_BPS, 3)}
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "blocksize": BS, "launches_per_graph": args.launches, "reps": args.reps,
+                      "rows": rows, "gemv_nf4_steady_state": steady}))
+
+
+if __name__ == "__main__":
+    main()

@@ -17,6 +17,7 @@ void set_gemv_variant(int v);
 void set_small_variant(int v);
 void set_wide_variant(int v);
 void set_quantize_variant(int v);
+void set_gemv_nf4_variant(int v);
 
 void set_error(const char *fmt, ...) {
     va_list ap;
@@ -54,7 +55,7 @@ extern "C" int fp4_hip_abi_version(void) { return FP4_HIP_ABI_VERSION; }
 extern "C" const char *fp4_hip_last_error(void) { return fp4::g_last_error; }
 
 extern "C" int fp4_hip_code_table(int table, float out16[16]) {
-    if ((table != FP4_TABLE_CODEBOOK && table != FP4_TABLE_TREE) || !out16) {
+    if ((table != FP4_TABLE_CODEBOOK && table != FP4_TABLE_TREE && table != FP4_TABLE_NF4) || !out16) {
         fp4::set_error("fp4_hip_code_table: bad argument");
         return FP4_ERR_INVALID_ARGUMENT;
     }
@@ -70,6 +71,10 @@ extern "C" int fp4_hip_set_variant(const char *kernel, int variant) {
     }
     if (kernel && !std::strcmp(kernel, "gemv")) {
         fp4::set_gemv_variant(variant);
+        return FP4_OK;
+    }
+    if (kernel && !std::strcmp(kernel, "gemv_nf4")) {
+        fp4::set_gemv_nf4_variant(variant);
         return FP4_OK;
     }
     if (kernel && !std::strcmp(kernel, "quantize")) {

@@ -58,11 +58,11 @@ __device__ __forceinline__ void store_vec(V *p, V v) {
 }
 
 // Whole tiles only: tile = kThreads * LOADS * kVals elements, aligned so that either the tile
-// is a whole number of quant blocks or lies inside one.
-template <int DT, int LOADS, bool NT>
-__global__ __launch_bounds__(kThreads) void dequant_tiles_kernel(const uint8_t *__restrict__ packed,
-                                                                  const float *__restrict__ absmax,
-                                                                  void *__restrict__ out, int bs_shift, int which_table) {
+// is a whole number of quant blocks or lies inside one.  NF4 = stage bitsandbytes' NF4 code instead of an FP4 table
+// (the only difference: what the 16 staging lanes write into the LUT).
+template <int DT, int LOADS, bool NT, bool NF4>
+__device__ __forceinline__ void dequant_tiles(const uint8_t *__restrict__ packed, const float *__restrict__ absmax,
+                                              void *__restrict__ out, int bs_shift, int which_table) {
     using Cfg = OutCfg<DT>;
     using load_t = typename Cfg::load_t;
     constexpr int kVals = Cfg::kVals;
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void dequant_tiles_kernel(const uint8_t *
         const int i = tid + r * kThreads;
         if (i < n_abs) s_absmax[i] = am_reg[r];
     }
-    if (tid < 16) s_lut[tid] = lut_entry(which_table, tid);
+    if (tid < 16) s_lut[tid] = NF4 ? nf4_lut_entry(tid) : lut_entry(which_table, tid);
     __syncthreads();
 
     // 3. decode + store
@@ -118,6 +118,19 @@ __global__ __launch_bounds__(kThreads) void dequant_tiles_kernel(const uint8_t *
             store_vec<NT>(reinterpret_cast<u32x4 *>(out) + (e_base + e_local) / 8, o);
         }
     }
+}
+
+template <int DT, int LOADS, bool NT>
+__global__ __launch_bounds__(kThreads) void dequant_tiles_kernel(const uint8_t *__restrict__ packed,
+                                                                  const float *__restrict__ absmax,
+                                                                  void *__restrict__ out, int bs_shift, int which_table) {
+    dequant_tiles<DT, LOADS, NT, false>(packed, absmax, out, bs_shift, which_table);
+}
+template <int DT, int LOADS, bool NT>
+__global__ __launch_bounds__(kThreads) void dequant_tiles_nf4_kernel(const uint8_t *__restrict__ packed,
+                                                                      const float *__restrict__ absmax,
+                                                                      void *__restrict__ out, int bs_shift, int which_table) {
+    dequant_tiles<DT, LOADS, NT, true>(packed, absmax, out, bs_shift, which_table);
 }
 
 // Anything the tile kernel does not take: ragged tails, unaligned pointers, block sizes that are
@@ -151,8 +164,12 @@ std::atomic<int> g_dequant_variant{-1};  // sweep hook: LOADS | NT << 8, or -1 =
 template <int DT, int LOADS, bool NT>
 void launch_tiles(const uint8_t *packed, const float *absmax, void *out, int bs_shift, int64_t tiles, int which_table,
                   hipStream_t stream) {
-    hipLaunchKernelGGL((dequant_tiles_kernel<DT, LOADS, NT>), dim3((unsigned)tiles), dim3(kThreads), 0, stream, packed,
-                       absmax, out, bs_shift, which_table);
+    if (which_table == FP4_TABLE_NF4)
+        hipLaunchKernelGGL((dequant_tiles_nf4_kernel<DT, LOADS, NT>), dim3((unsigned)tiles), dim3(kThreads), 0, stream, packed,
+                           absmax, out, bs_shift, which_table);
+    else
+        hipLaunchKernelGGL((dequant_tiles_kernel<DT, LOADS, NT>), dim3((unsigned)tiles), dim3(kThreads), 0, stream, packed,
+                           absmax, out, bs_shift, which_table);
 }
 
 template <int DT>
@@ -248,7 +265,7 @@ extern "C" int fp4_hip_dequantize_blockwise(const uint8_t *packed, const float *
                   blocksize);
         return FP4_ERR_INVALID_ARGUMENT;
     }
-    if (table != FP4_TABLE_CODEBOOK && table != FP4_TABLE_TREE) {
+    if (table != FP4_TABLE_CODEBOOK && table != FP4_TABLE_TREE && table != FP4_TABLE_NF4) {
         set_error("fp4_hip_dequantize_blockwise: unknown table %d", table);
         return FP4_ERR_INVALID_ARGUMENT;
     }

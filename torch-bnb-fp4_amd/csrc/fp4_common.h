@@ -17,12 +17,23 @@ namespace fp4 {
 
 static constexpr uint32_t kMagBits[2][8] = {{FP4_CODEBOOK_MAG_BITS}, {FP4_TREE_MAG_BITS}};
 
+// bitsandbytes' NF4 code (get_4bit_type('nf4'), the literals of dDequantizeNF4) rounded to f32, indexed by the nibble as is:
+// nibble 0 = -1.0, 7 = +0.0, 15 = +1.0 (no sign bit).  tests/nf4_ref.py restates it from the decimal spellings.
+#define FP4_NF4_BITS                                                                                                       \
+    0xBF800000u, 0xBF3239B1u, 0xBF066B30u, 0xBECA32A0u, 0xBE91A24Du, 0xBE3D353Fu, 0xBDBA7871u, 0x00000000u, 0x3DA2FAFFu,  \
+        0x3E24CAE3u, 0x3E7C04DDu, 0x3EAD033Au, 0x3EE1A4B8u, 0x3F1007ABu, 0x3F3913B3u, 0x3F800000u
+static constexpr uint32_t kNf4Bits[16] = {FP4_NF4_BITS};
+
 struct CodeTable {
     uint32_t bits[16];
 };
 
 inline CodeTable make_table(int which) {
     CodeTable t;
+    if (which == FP4_TABLE_NF4) {
+        for (int i = 0; i < 16; ++i) t.bits[i] = kNf4Bits[i];
+        return t;
+    }
     for (int i = 0; i < 8; ++i) {
         t.bits[i] = kMagBits[which][i];
         t.bits[i + 8] = kMagBits[which][i] | 0x80000000u;
@@ -48,6 +59,14 @@ __device__ __forceinline__ float lut_entry(int which, int idx) {
 static_assert(kMagBits[0][2] == kMagBits[1][2] && kMagBits[0][3] == kMagBits[1][3] && kMagBits[0][5] == kMagBits[1][5] &&
                   kMagBits[0][7] == kMagBits[1][7] && kMagBits[0][0] == 0 && kMagBits[1][0] == 0,
               "lut_entry assumes the two tables differ only at magnitudes 1, 4 and 6");
+
+// NF4 LUT entry from immediates only (select chain), for the same 16 staging lanes.
+__device__ __forceinline__ float nf4_lut_entry(int idx) {
+    uint32_t b = kNf4Bits[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) b = idx == i ? kNf4Bits[i] : b;
+    return __builtin_bit_cast(float, b);
+}
 
 // ---- status plumbing ---------------------------------------------------------------
 void set_error(const char *fmt, ...);

@@ -812,8 +812,8 @@ int default_variant16(int M, int K) {
 
 template <int DT>
 int run_generic(const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, int64_t M,
-                int64_t K, int blocksize, int mode, hipStream_t stream) {
-    const CodeTable tbl = make_table(FP4_TABLE_CODEBOOK);
+                int64_t K, int blocksize, int mode, hipStream_t stream, int table = FP4_TABLE_CODEBOOK) {
+    const CodeTable tbl = make_table(table);
     hipLaunchKernelGGL((gemv_generic_kernel<DT>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, W, absmax, bias,
                        residual, out, (int)M, K, blocksize, tbl, mode);
     return FP4_OK;
@@ -822,6 +822,16 @@ int run_generic(const void *x, const uint8_t *W, const float *absmax, const void
 }  // namespace
 
 void set_gemv_variant(int v) { g_gemv_variant.store(v, std::memory_order_relaxed); }
+
+// The generic kernel with another code table (the NF4 GEMV's path for irregular shapes, gemv_nf4.hip).
+int gemv_generic_table(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int64_t M, int64_t K,
+                       int blocksize, int dtype, int table, hipStream_t stream) {
+    switch (dtype) {
+        case FP4_DTYPE_F16: return run_generic<FP4_DTYPE_F16>(x, W, absmax, bias, nullptr, out, M, K, blocksize, 0, stream, table);
+        case FP4_DTYPE_BF16: return run_generic<FP4_DTYPE_BF16>(x, W, absmax, bias, nullptr, out, M, K, blocksize, 0, stream, table);
+        default: return run_generic<FP4_DTYPE_F32>(x, W, absmax, bias, nullptr, out, M, K, blocksize, 0, stream, table);
+    }
+}
 
 }  // namespace fp4
 

@@ -1,0 +1,252 @@
+// Fused batch-1 GEMV over an NF4 weight for gfx950 (MI355X):
+//     out[r] = sum_k x[k] * nf4[nib(r,k)] * absmax[(r*K+k)/bs]      (+ bias[r])
+//
+// Not in the reference (it has FP4 only).  The FP4 GEMV's table-free decode does not carry over: it relies on 12*code being
+// exact in 8 bits, and the NF4 values are not exact in fp16 or bf16 (one fp16-rounded code is ~2^-12 off per weight, outside
+// the f32-accumulation parity bar at small K).  So every weight is decoded through an f32 table in LDS and multiplied into
+// f32 copies of x, which keeps each code exact; x is widened to f32 once per lane and reused for all of its rows.
+//
+// Geometry: the register-x mapping of the FP4 f32 kernel (gemv32_regx_kernel): 256 threads, a half-wave per row, each lane
+// owns 32-weight chunks (one 16-byte load) at the same K positions for every row of its workgroup, K split into 1..4 bands
+// of 32 chunks, one wave per band.  x is requested before the weight stream and the load phase is branch-free (clamped
+// index + zero scale), as in gemv_fp4.hip.  Rows longer than 256 chunks (K > 8192) loop over 256-chunk slices of K.
+// Two table layouts (fp4_hip_set_variant("gemv_nf4", v); profiles/nf4_gemv_ablation.txt):
+//   0 = 16 f32 entries, one ds_read_b32 per weight (every read a broadcast among 16 consecutive dwords: conflict-free);
+//   1 = 256 f32 pairs indexed by the packed byte, one ds_read_b64 per two weights (half the LDS instructions, but the
+//       addresses of a wave are spread over 2 KiB, so reads can collide in banks).
+// Irregular shapes (K % 32 != 0, blocksize not a power of two >= 32 dividing K, unaligned operands) run the FP4 generic
+// kernel of gemv_fp4.hip with the NF4 table as its argument.
+#include <atomic>
+
+#include "gemv_common.h"
+
+namespace fp4 {
+
+int gemv_generic_table(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int64_t M, int64_t K,
+                       int blocksize, int dtype, int table, hipStream_t stream);
+
+namespace {
+
+// 8 consecutive activations (one 16-byte load of 16-bit x, two of f32) as f32
+template <int DT>
+__device__ __forceinline__ void load_x8(const void *x, int64_t i8, f32x4 &a, f32x4 &b) {
+    if constexpr (DT == FP4_DTYPE_F32) {
+        a = reinterpret_cast<const f32x4 *>(x)[2 * i8];
+        b = reinterpret_cast<const f32x4 *>(x)[2 * i8 + 1];
+    } else {
+        const u32x4 v = reinterpret_cast<const u32x4 *>(x)[i8];
+        a = f32x4{to_f32<DT>(uint16_t(v.x & 0xFFFFu)), to_f32<DT>(uint16_t(v.x >> 16)), to_f32<DT>(uint16_t(v.y & 0xFFFFu)),
+                  to_f32<DT>(uint16_t(v.y >> 16))};
+        b = f32x4{to_f32<DT>(uint16_t(v.z & 0xFFFFu)), to_f32<DT>(uint16_t(v.z >> 16)), to_f32<DT>(uint16_t(v.w & 0xFFFFu)),
+                  to_f32<DT>(uint16_t(v.w >> 16))};
+    }
+}
+
+template <int DT>
+__device__ __forceinline__ void store_nf4_row(void *out, const void *bias, int row, float sum) {
+    if constexpr (DT == FP4_DTYPE_F32) {
+        reinterpret_cast<float *>(out)[row] = bias ? sum + reinterpret_cast<const float *>(bias)[row] : sum;
+    } else {
+        store_row<DT>(reinterpret_cast<uint16_t *>(out), reinterpret_cast<const uint16_t *>(bias), nullptr, row, sum);
+    }
+}
+
+template <int DT, int KSPLIT, int G, int ITERS, bool PAIR>
+__global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ x, const uint8_t *__restrict__ W,
+                                                       const float *__restrict__ absmax, const void *__restrict__ bias,
+                                                       void *__restrict__ out, int M, int K, int bs_shift) {
+    constexpr int RG = 4 / KSPLIT;
+    constexpr int kRowsPerBlock = 2 * RG * ITERS;
+    constexpr int kBand = G * 32 * KSPLIT;  // chunks of K covered per pass
+    __shared__ float s_lut[PAIR ? 1 : 16];
+    __shared__ f32x2 s_pair[PAIR ? 256 : 1];
+    __shared__ float s_part[kRowsPerBlock][KSPLIT];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int kw = wave % KSPLIT, rw = wave / KSPLIT;
+    const int half = lane >> 5, l32 = lane & 31;
+    const int C = K >> 5;
+    const int row_base = blockIdx.x * kRowsPerBlock;
+    const u32x4 *Wv = reinterpret_cast<const u32x4 *>(W);
+    if constexpr (PAIR) {
+        s_pair[tid] = f32x2{nf4_lut_entry(tid >> 4), nf4_lut_entry(tid & 15)};  // byte -> (high nibble, low nibble)
+    } else {
+        if (tid < 16) s_lut[tid] = nf4_lut_entry(tid);
+    }
+
+    int rowi[ITERS], rclamp[ITERS];
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        rowi[it] = 2 * (it * RG + rw) + half;
+        const int row = row_base + rowi[it];
+        rclamp[it] = row < M ? row : M - 1;
+    }
+    float p[ITERS];
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) p[it] = 0.0f;
+
+    for (int cb = 0; cb < C; cb += kBand) {
+        int cidx[G];
+        bool live[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int c = cb + g * (32 * KSPLIT) + kw * 32 + l32;
+            live[g] = c < C;
+            cidx[g] = live[g] ? c : C - 1;
+        }
+        f32x4 xv[G][8];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) load_x8<DT>(x, int64_t(cidx[g]) * 4 + q, xv[g][2 * q], xv[g][2 * q + 1]);
+        }
+        u32x4 wq[ITERS][G];
+        float am[ITERS][G];
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int64_t chunk = int64_t(rclamp[it]) * C + cidx[g];
+                wq[it][g] = __builtin_nontemporal_load(Wv + chunk);
+                const float a = absmax[(chunk << 5) >> bs_shift];
+                am[it][g] = live[g] ? a : 0.0f;
+            }
+        }
+        if (cb == 0) __syncthreads();  // table visible (uniform: every thread runs the same passes)
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {  // weights 4q..4q+3 of the chunk = bytes 2q, 2q+1
+                    const uint32_t h = (wq[it][g][q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
+                    if constexpr (PAIR) {
+                        const f32x2 c01 = s_pair[h & 0xFFu], c23 = s_pair[h >> 8];
+                        s0 = __builtin_fmaf(c01.x, xv[g][q].x, s0);
+                        s1 = __builtin_fmaf(c01.y, xv[g][q].y, s1);
+                        s0 = __builtin_fmaf(c23.x, xv[g][q].z, s0);
+                        s1 = __builtin_fmaf(c23.y, xv[g][q].w, s1);
+                    } else {
+                        s0 = __builtin_fmaf(s_lut[(h >> 4) & 15u], xv[g][q].x, s0);
+                        s1 = __builtin_fmaf(s_lut[h & 15u], xv[g][q].y, s1);
+                        s0 = __builtin_fmaf(s_lut[(h >> 12) & 15u], xv[g][q].z, s0);
+                        s1 = __builtin_fmaf(s_lut[(h >> 8) & 15u], xv[g][q].w, s1);
+                    }
+                }
+                p[it] = __builtin_fmaf(s0 + s1, am[it][g], p[it]);
+            }
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+        float v = p[it];
+        v = dpp_add<0x128>(v);
+        v = dpp_add<0x124>(v);
+        v = dpp_add<0x122>(v);
+        v = dpp_add<0x121>(v);
+        v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));  // 32-lane row sum
+        if constexpr (KSPLIT == 1) {
+            const int row = row_base + rowi[it];
+            if (l32 == 0 && row < M) store_nf4_row<DT>(out, bias, row, v);
+        } else {
+            if (l32 == 0) s_part[rowi[it]][kw] = v;
+        }
+    }
+    if constexpr (KSPLIT > 1) {
+        __syncthreads();
+        if (tid < kRowsPerBlock) {
+            float t = 0.0f;
+#pragma unroll
+            for (int k = 0; k < KSPLIT; ++k) t += s_part[tid][k];
+            const int row = row_base + tid;
+            if (row < M) store_nf4_row<DT>(out, bias, row, t);
+        }
+    }
+}
+
+std::atomic<int> g_gemv_nf4_variant{-1};  // sweep hook: 0 = 16-entry table, 1 = pair table, -1 = default
+
+template <int DT, int KSPLIT, int G, int ITERS>
+void launch_nf4(bool pair, const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int M, int K,
+                int bs_shift, hipStream_t stream) {
+    constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
+    const dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block)), block(256);
+    if (pair)
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true>), grid, block, 0, stream, x, W, absmax, bias, out, M, K, bs_shift);
+    else
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false>), grid, block, 0, stream, x, W, absmax, bias, out, M, K, bs_shift);
+}
+
+template <int DT>
+void dispatch_nf4(bool pair, const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int M, int K,
+                  int bs_shift, hipStream_t stream) {
+    const int C = K >> 5;
+    const int ks = C <= 32 ? 1 : (C <= 64 ? 2 : 4);
+    // the x slice is re-read by every workgroup: amortise it over up to 4 row pairs per lane while >= ~256 workgroups remain
+    // (the FP4 f32 kernel's rule, gemv_fp4.hip dispatch32_regx)
+    int iters = 1;
+    while (iters < 4 && M / (2 * (4 / ks) * iters * 2) >= 256) iters *= 2;
+#define NF4_ITERS(KS, GG)                                                                                          \
+    switch (iters) {                                                                                               \
+        case 1: return launch_nf4<DT, KS, GG, 1>(pair, x, W, absmax, bias, out, M, K, bs_shift, stream);           \
+        case 2: return launch_nf4<DT, KS, GG, 2>(pair, x, W, absmax, bias, out, M, K, bs_shift, stream);           \
+        default: return launch_nf4<DT, KS, GG, 4>(pair, x, W, absmax, bias, out, M, K, bs_shift, stream);          \
+    }
+    if (C <= 32) { NF4_ITERS(1, 1) }
+    if (C <= 64) { NF4_ITERS(2, 1) }
+    if (C <= 128) { NF4_ITERS(4, 1) }
+    NF4_ITERS(4, 2)
+#undef NF4_ITERS
+}
+
+}  // namespace
+
+void set_gemv_nf4_variant(int v) { g_gemv_nf4_variant.store(v, std::memory_order_relaxed); }
+
+}  // namespace fp4
+
+extern "C" int fp4_hip_gemv_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out, int64_t M,
+                                int64_t K, int blocksize, int dtype, void *stream) {
+    using namespace fp4;
+    if (M < 0 || K < 0 || (K & 1) || blocksize < 2 || (blocksize & 1)) {
+        set_error("fp4_hip_gemv_nf4: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", (long long)M,
+                  (long long)K, blocksize);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    if (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16 && dtype != FP4_DTYPE_F32) {
+        set_error("fp4_hip_gemv_nf4: unsupported dtype %d", dtype);
+        return FP4_ERR_UNSUPPORTED;
+    }
+    if (M == 0) return FP4_OK;
+    if (!out || (K > 0 && (!x || !packed || !absmax))) {
+        set_error("fp4_hip_gemv_nf4: null pointer");
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    if (M > (int64_t(1) << 30) || K > (int64_t(1) << 30)) {
+        set_error("fp4_hip_gemv_nf4: M=%lld K=%lld too large", (long long)M, (long long)K);
+        return FP4_ERR_UNSUPPORTED;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int bs_shift = ilog2_exact(blocksize);
+    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
+    const bool fast = K > 0 && (K % 32) == 0 && bs_shift >= 5 && (K % blocksize) == 0 && (align & 15u) == 0;
+    if (fast) {
+        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
+        switch (dtype) {
+            case FP4_DTYPE_F16:
+                dispatch_nf4<FP4_DTYPE_F16>(pair, x, packed, absmax, bias, out, (int)M, (int)K, bs_shift, s);
+                break;
+            case FP4_DTYPE_BF16:
+                dispatch_nf4<FP4_DTYPE_BF16>(pair, x, packed, absmax, bias, out, (int)M, (int)K, bs_shift, s);
+                break;
+            default:
+                dispatch_nf4<FP4_DTYPE_F32>(pair, x, packed, absmax, bias, out, (int)M, (int)K, bs_shift, s);
+                break;
+        }
+    } else {
+        gemv_generic_table(x, packed, absmax, bias, out, M, K, blocksize, dtype, FP4_TABLE_NF4, s);
+    }
+    return check_launch("fp4_hip_gemv_nf4");
+}

@@ -13,7 +13,8 @@
 //   * launch / dtype failures raise instead of printf (csrc/dequant_fp4_optimized.cu:48-53,201-203);
 //   * qlinear_codebook* dequantise all M*N elements (the reference passes the BYTE count,
 //     csrc/torch_fp4.cpp:90,101, leaving half of the weight uninitialised).
-// Extra exports (not in the reference): gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
+// Extra exports (not in the reference): the NF4 ops (dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4, qlinear_nf4_bias,
+// quantize_nf4: bitsandbytes' second 4-bit code, same kernels' shapes and dispatch), gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -112,6 +113,14 @@ torch::Tensor dequantize_fp4_codebook(torch::Tensor A, torch::Tensor absmax, tor
     check_gpu_contiguous(codebook, "codebook");  // checked but unused, like the reference (its kernels use CODE_PARAM)
     torch::Tensor out = torch::empty({M, N}, torch::TensorOptions().dtype(to_torch(dtype)).device(A.device()));
     dequant_into(A, absmax, out, blocksize, n, FP4_TABLE_CODEBOOK);
+    return out;
+}
+
+torch::Tensor dequantize_nf4(torch::Tensor A, torch::Tensor absmax, int blocksize, int M, int N, ScalarTypeEnum o_type) {
+    check_gpu_contiguous(A, "A");
+    check_gpu_contiguous(absmax, "absmax");
+    torch::Tensor out = torch::empty({M, N}, torch::TensorOptions().dtype(to_torch(o_type)).device(A.device()));
+    dequant_into(A, absmax, out, blocksize, int64_t(M) * N, FP4_TABLE_NF4);
     return out;
 }
 
@@ -321,23 +330,32 @@ torch::Tensor qlinear_codebook_bias(torch::Tensor A_in, torch::Tensor A, torch::
     return qlinear_impl(A_in, A, absmax, M, N, blocksize, FP4_TABLE_CODEBOOK, bias);
 }
 
+torch::Tensor qlinear_nf4(torch::Tensor A_in, torch::Tensor A, torch::Tensor absmax, int M, int N, int blocksize) {
+    return qlinear_impl(A_in, A, absmax, M, N, blocksize, FP4_TABLE_NF4, c10::nullopt);
+}
+torch::Tensor qlinear_nf4_bias(torch::Tensor A_in, torch::Tensor A, torch::Tensor absmax, int M, int N, int blocksize, torch::Tensor bias) {
+    return qlinear_impl(A_in, A, absmax, M, N, blocksize, FP4_TABLE_NF4, bias);
+}
+
+// datatype == nullptr: the NF4 GEMV (its code is fixed; the FP4 ops take the reference's `datatype` tensor and ignore it)
 torch::Tensor gemv_impl(const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
-                        const torch::Tensor &datatype, int blocksize, ScalarTypeEnum dtype, const std::vector<uint32_t> &Bshape,
+                        const torch::Tensor *datatype, int blocksize, ScalarTypeEnum dtype, const std::vector<uint32_t> &Bshape,
                         const c10::optional<torch::Tensor> &bias) {
     check_gpu_contiguous(A, "A");
     check_gpu_contiguous(B, "B");
     check_gpu_contiguous(absmax, "absmax");
-    check_gpu_contiguous(datatype, "datatype");
+    if (datatype) check_gpu_contiguous(*datatype, "datatype");
+    const char *op = datatype ? "gemv_fp4" : "gemv_nf4";
     TORCH_CHECK(Bshape.size() == 2, "Bshape must be the [out_features, in_features] of the quantised weight");
     const int64_t m = Bshape[0], k = Bshape[1];
     const torch::ScalarType st = to_torch(dtype);
     // reference: per-dtype TORCH_CHECKs of csrc/gemv_fp4_optimized.cu:303-305,323-325,343-345
-    TORCH_CHECK(A.scalar_type() == st, "gemv_fp4: dtype argument (", st, ") must equal the activation dtype (", A.scalar_type(), ")");
+    TORCH_CHECK(A.scalar_type() == st, op, ": dtype argument (", st, ") must equal the activation dtype (", A.scalar_type(), ")");
     TORCH_CHECK(absmax.scalar_type() == torch::kFloat32, "Only fp32 absmax is supported");
-    TORCH_CHECK(datatype.scalar_type() == torch::kFloat32, "Only fp32 code is supported");
+    TORCH_CHECK(!datatype || datatype->scalar_type() == torch::kFloat32, "Only fp32 code is supported");
     TORCH_CHECK(B.dtype() == torch::kUInt8, "B must be uint8");
-    TORCH_CHECK(A.dim() == 2 || A.dim() == 3, "gemv_fp4: activation must be [1, K] or [1, 1, K]");
-    TORCH_CHECK(A.numel() == k && A.size(-1) == k, "gemv_fp4 is batch-1 only: activation has ", A.numel(),
+    TORCH_CHECK(A.dim() == 2 || A.dim() == 3, op, ": activation must be [1, K] or [1, 1, K]");
+    TORCH_CHECK(A.numel() == k && A.size(-1) == k, op, " is batch-1 only: activation has ", A.numel(),
                 " elements, in_features is ", k);
     TORCH_CHECK(B.numel() * 2 >= m * k, "B holds ", B.numel(), " bytes, ", m * k / 2, " needed");
     TORCH_CHECK(absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small for a ", m, "x", k, " weight");
@@ -352,18 +370,27 @@ torch::Tensor gemv_impl(const torch::Tensor &A, const torch::Tensor &B, const to
         bias_ptr = bias_c.data_ptr();
     }
     c10::DeviceGuard guard(A.device());
-    check_status(fp4_hip_gemv(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, out.data_ptr(), m, k,
-                              blocksize, (int)dtype, current_stream(A)));
+    const auto gemv = datatype ? fp4_hip_gemv : fp4_hip_gemv_nf4;
+    check_status(gemv(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, out.data_ptr(), m, k, blocksize, (int)dtype,
+                      current_stream(A)));
     return out;
 }
 
 torch::Tensor gemv_fp4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, torch::Tensor datatype, int blocksize,
                        ScalarTypeEnum dtype, std::vector<uint32_t> Bshape) {
-    return gemv_impl(A, B, absmax, datatype, blocksize, dtype, Bshape, c10::nullopt);
+    return gemv_impl(A, B, absmax, &datatype, blocksize, dtype, Bshape, c10::nullopt);
 }
 torch::Tensor gemv_fp4_bias(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, torch::Tensor datatype, int blocksize,
                             ScalarTypeEnum dtype, std::vector<uint32_t> Bshape, torch::Tensor bias) {
-    return gemv_impl(A, B, absmax, datatype, blocksize, dtype, Bshape, bias);
+    return gemv_impl(A, B, absmax, &datatype, blocksize, dtype, Bshape, bias);
+}
+torch::Tensor gemv_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, ScalarTypeEnum dtype,
+                       std::vector<uint32_t> Bshape) {
+    return gemv_impl(A, B, absmax, nullptr, blocksize, dtype, Bshape, c10::nullopt);
+}
+torch::Tensor gemv_nf4_bias(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, ScalarTypeEnum dtype,
+                            std::vector<uint32_t> Bshape, torch::Tensor bias) {
+    return gemv_impl(A, B, absmax, nullptr, blocksize, dtype, Bshape, bias);
 }
 
 // GEMV with a fused epilogue (fp4_hip_gemv_fused): bias, residual add, and - for a weight whose rows interleave a gate and an
@@ -513,19 +540,21 @@ torch::Tensor gemv_fp4_partial(torch::Tensor A, torch::Tensor B, torch::Tensor a
     return out;
 }
 
-// bitsandbytes-format FP4 quantisation of a float tensor: returns (packed uint8[ceil(n/2), 1], absmax float32[ceil(n/bs)])
-std::tuple<torch::Tensor, torch::Tensor> quantize_fp4(torch::Tensor W, int blocksize) {
+// bitsandbytes-format FP4 / NF4 quantisation of a float tensor: returns (packed uint8[ceil(n/2), 1], absmax float32[ceil(n/bs)])
+std::tuple<torch::Tensor, torch::Tensor> quantize_4bit(torch::Tensor W, int blocksize, bool nf4) {
     check_gpu_contiguous(W, "W");
-    const int dt = to_fp4_dtype(W.scalar_type(), "quantize_fp4");
+    const int dt = to_fp4_dtype(W.scalar_type(), nf4 ? "quantize_nf4" : "quantize_fp4");
     const int64_t n = W.numel();
     TORCH_CHECK(blocksize > 0, "blocksize must be positive");
     torch::Tensor packed = torch::empty({(n + 1) / 2, 1}, torch::TensorOptions().dtype(torch::kUInt8).device(W.device()));
     torch::Tensor absmax = torch::empty({(n + blocksize - 1) / blocksize}, torch::TensorOptions().dtype(torch::kFloat32).device(W.device()));
     c10::DeviceGuard guard(W.device());
-    check_status(fp4_hip_quantize_blockwise(W.data_ptr(), dt, packed.data_ptr<uint8_t>(), absmax.data_ptr<float>(), n, blocksize,
-                                            current_stream(W)));
+    const auto quantize = nf4 ? fp4_hip_quantize_blockwise_nf4 : fp4_hip_quantize_blockwise;
+    check_status(quantize(W.data_ptr(), dt, packed.data_ptr<uint8_t>(), absmax.data_ptr<float>(), n, blocksize, current_stream(W)));
     return {packed, absmax};
 }
+std::tuple<torch::Tensor, torch::Tensor> quantize_fp4(torch::Tensor W, int blocksize) { return quantize_4bit(W, blocksize, false); }
+std::tuple<torch::Tensor, torch::Tensor> quantize_nf4(torch::Tensor W, int blocksize) { return quantize_4bit(W, blocksize, true); }
 
 // ---- one-shot all-reduce plumbing (fp4_hip_comm_* / fp4_hip_allreduce_oneshot) ---------------------------------------
 // Buffers are identified by their device address (an int on the Python side); torch_bnb_fp4/comm.py owns their lifetime.
@@ -590,9 +619,10 @@ torch::Tensor allreduce_oneshot(torch::Tensor partial, std::vector<int64_t> peer
 }
 
 torch::Tensor code_table(const std::string &name) {
-    TORCH_CHECK(name == "codebook" || name == "tree", "code_table: name must be 'codebook' or 'tree'");
+    TORCH_CHECK(name == "codebook" || name == "tree" || name == "nf4", "code_table: name must be 'codebook', 'tree' or 'nf4'");
     torch::Tensor t = torch::empty({16}, torch::kFloat32);
-    check_status(fp4_hip_code_table(name == "tree" ? FP4_TABLE_TREE : FP4_TABLE_CODEBOOK, t.data_ptr<float>()));
+    const int table = name == "tree" ? FP4_TABLE_TREE : (name == "nf4" ? FP4_TABLE_NF4 : FP4_TABLE_CODEBOOK);
+    check_status(fp4_hip_code_table(table, t.data_ptr<float>()));
     return t;
 }
 
@@ -634,6 +664,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("allreduce_oneshot", &allreduce_oneshot,
           "one-shot all-reduce of f32 partials over peer-mapped slots: (partial, peers, rank, capacity, dtype, bias|None, residual|None, timeout_us)");
     m.def("quantize_fp4", &quantize_fp4, "blockwise FP4 quantiser: (W, blocksize) -> (packed, absmax)");
+    m.def("dequantize_nf4", &dequantize_nf4, "NF4 -> T dequant: (A, absmax, blocksize, M, N, o_type)");
+    m.def("gemv_nf4", &gemv_nf4, "fused batch-1 NF4 GEMV: (A, B, absmax, blocksize, dtype, Bshape)");
+    m.def("gemv_nf4_bias", &gemv_nf4_bias, "gemv_nf4 with the bias add fused into the epilogue: (A, B, absmax, blocksize, dtype, Bshape, bias)");
+    m.def("qlinear_nf4", &qlinear_nf4, "NF4 dequant + linear: (A_in, A, absmax, M, N, blocksize)");
+    m.def("qlinear_nf4_bias", &qlinear_nf4_bias, "NF4 dequant + linear + bias: (A_in, A, absmax, M, N, blocksize, bias)");
+    m.def("quantize_nf4", &quantize_nf4, "blockwise NF4 quantiser: (W, blocksize) -> (packed, absmax)");
     m.def("code_table", &code_table, "16-entry code table as a CPU float tensor");
     m.def("set_kernel_variant", &set_kernel_variant, "benchmark hook: select a kernel geometry");
     m.def("set_qlinear_gemm", &set_qlinear_gemm,

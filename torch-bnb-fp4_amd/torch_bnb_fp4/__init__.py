@@ -8,6 +8,7 @@ torch_bnb_fp4/__init__.py), backed by hand-written CDNA4 HIP kernels:
 * nn.Module shell     - :class:`TorchFP4Linear`           (reference :621-714)
 * model surgery       - :func:`recursively_replace_with_fp4_linear` and helpers (reference :717-922)
 
+Both bitsandbytes 4-bit codes are decoded: ``quant_type="fp4"`` (the reference's) and ``"nf4"`` (QLoRA's).
 bitsandbytes is optional: :mod:`torch_bnb_fp4.nn` provides attribute-compatible ``LinearFP4`` /
 ``Params4bit`` / ``QuantState`` and the quantiser runs on the GPU through this package.
 """
@@ -21,12 +22,15 @@ from .functional import (
     gemm_4bit_inference,
     gemm_4bit_inference_qtype,
     quantize_fp4,
+    dequantize_nf4,
+    gemv_nf4,
+    quantize_nf4,
 )
 from .comm import OneShotAllReduce
 from .fused import FusedFP4Linear
 from .graphs import GraphedStep
 from .linear import TorchFP4Linear
-from .nn import Linear4bit, LinearFP4, Params4bit, QuantState
+from .nn import Linear4bit, LinearFP4, LinearNF4, Params4bit, QuantState, nf4_code
 from .quant_data import QuantData
 from .serialization import fp4_linear_from_bnb_state, fp4_linear_to_bnb_state, load_fp4_layers, save_fp4_model
 from .surgery import (
@@ -68,5 +72,10 @@ __all__ = [
     "FusedFP4Linear",
     "OneShotAllReduce",
     "GraphedStep",
+    "dequantize_nf4",
+    "gemv_nf4",
+    "quantize_nf4",
+    "LinearNF4",
+    "nf4_code",
 ]
 __version__ = "0.1.0"

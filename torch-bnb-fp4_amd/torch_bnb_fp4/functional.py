@@ -67,3 +67,27 @@ def quantize_fp4(W: torch.Tensor, blocksize: int = 64) -> Tuple[torch.Tensor, to
 
     Stands in for ``bitsandbytes.functional.quantize_fp4`` (called by the reference at :775)."""
     return ext.quantize_fp4(W.contiguous(), blocksize)
+
+
+# ---- NF4 (bitsandbytes' quant_type="nf4"; not in the reference) -------------------------------------------------------------
+@torch.no_grad()
+def dequantize_nf4(qweight: torch.Tensor, absmax: torch.Tensor, blocksize: int, M: int, N: int,
+                   dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """NF4 -> ``dtype`` [M, N]: ``out = RN(code[nibble] * absmax)``."""
+    return ext.dequantize_nf4(qweight, absmax, blocksize, M, N, ScalarType.from_torch_dtype(dtype).value)
+
+
+@torch.no_grad()
+def gemv_nf4(A: torch.Tensor, B: torch.Tensor, absmax: torch.Tensor, blocksize: int, dtype: torch.dtype = torch.float16,
+             Bshape: Optional[Sequence[int]] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fused batch-1 GEMV ``A[1,K] @ W[M,K]^T (+ bias)`` over packed NF4 ``B`` (bias: ``T(T(sum) + bias)``)."""
+    qtype = ScalarType.from_torch_dtype(dtype).value
+    if bias is not None:
+        return ext.gemv_nf4_bias(A, B, absmax, blocksize, qtype, list(Bshape), bias)
+    return ext.gemv_nf4(A, B, absmax, blocksize, qtype, list(Bshape))
+
+
+@torch.no_grad()
+def quantize_nf4(W: torch.Tensor, blocksize: int = 64) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bitsandbytes-format blockwise NF4 quantisation on the GPU: ``(packed uint8[n/2, 1], absmax f32[n/bs])``."""
+    return ext.quantize_nf4(W.contiguous(), blocksize)

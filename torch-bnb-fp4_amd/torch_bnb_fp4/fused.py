@@ -69,6 +69,8 @@ class FusedFP4Linear(nn.Module):
         super().__init__()
         if epilogue not in (EPILOGUE_NONE, EPILOGUE_SILU_MUL_PAIRS):
             raise ValueError(f"unknown epilogue {epilogue}")
+        if getattr(quant_data, "nf4", False):
+            raise ValueError("FusedFP4Linear runs the FP4 fused-epilogue kernels; an NF4 weight cannot be decoded by them")
         if epilogue == EPILOGUE_SILU_MUL_PAIRS and quant_data.M % 2:
             raise ValueError("the gate|up epilogue needs an even number of weight rows")
         self.quant_data = quant_data
@@ -103,12 +105,16 @@ class FusedFP4Linear(nn.Module):
     def from_linear(cls, layer) -> "FusedFP4Linear":
         """From a :class:`TorchFP4Linear` (shares its packed weight)."""
         qd = layer.quant_data
+        if qd.nf4:
+            raise ValueError("FusedFP4Linear runs the FP4 fused-epilogue kernels; an NF4 weight cannot be decoded by them")
         return cls.from_packed(qd.A, qd.absmax, (qd.M, qd.N), qd.blocksize, qd.bias, dtype=getattr(qd.quant_state, "dtype", torch.float16))
 
     @classmethod
     def gate_up(cls, gate_layer, up_layer) -> "FusedFP4Linear":
         """From the gate and up :class:`TorchFP4Linear` of a gated MLP."""
         g, u = gate_layer.quant_data, up_layer.quant_data
+        if g.nf4 or u.nf4:
+            raise ValueError("FusedFP4Linear runs the FP4 fused-epilogue kernels; an NF4 weight cannot be decoded by them")
         if (g.M, g.N, g.blocksize) != (u.M, u.N, u.blocksize):
             raise ValueError("gate_up() needs two projections of the same shape and blocksize")
         return cls.gate_up_from_packed((g.A, g.absmax), (u.A, u.absmax), (g.M, g.N), g.blocksize, g.bias, u.bias)

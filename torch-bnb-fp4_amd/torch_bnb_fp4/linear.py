@@ -86,6 +86,8 @@ class TorchFP4Linear(nn.Module):
         from .parallel import concat_rows
 
         qds = [l.quant_data for l in layers]
+        if any(q.nf4 for q in qds):
+            raise ValueError("fuse() concatenates FP4 weights only; NF4 layers stay separate")
         bs = qds[0].blocksize
         if any(q.blocksize != bs or q.N != qds[0].N for q in qds):
             raise ValueError("fuse() needs layers with the same in_features and blocksize")

@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from ._ext import ext
-from .functional import quantize_fp4
+from .functional import quantize_fp4, quantize_nf4
 
 try:  # optional: accept genuine bitsandbytes layers too
     import bitsandbytes as _bnb  # type: ignore
@@ -35,8 +35,23 @@ def fp4_code() -> torch.Tensor:
     return ext.code_table("tree")
 
 
+def nf4_code() -> torch.Tensor:
+    """The 16-entry NF4 code as bitsandbytes stores it in ``quant_state.code`` (nibble 0 = -1.0, 7 = 0.0, 15 = 1.0; f32)."""
+    return ext.code_table("nf4")
+
+
+QUANT_TYPES = ("fp4", "nf4")
+
+
+def check_quant_type(quant_type) -> str:
+    """``quant_type`` if this package decodes it, else ValueError (an unknown code must never be decoded as FP4)."""
+    if quant_type not in QUANT_TYPES:
+        raise ValueError(f"unsupported quant_type {quant_type!r}: this package decodes {QUANT_TYPES}")
+    return quant_type
+
+
 class QuantState:
-    """Attribute-compatible subset of ``bitsandbytes.functional.QuantState`` (FP4, no nested absmax)."""
+    """Attribute-compatible subset of ``bitsandbytes.functional.QuantState`` (FP4 or NF4, no nested absmax)."""
 
     def __init__(self, absmax: torch.Tensor, shape, code: torch.Tensor, blocksize: int = 64,
                  dtype: torch.dtype = torch.float16, quant_type: str = "fp4"):
@@ -71,23 +86,27 @@ class Params4bit(nn.Parameter):
         return Params4bit(self.data.clone(), self.requires_grad, self.quant_state, self.blocksize, self.quant_type)
 
     @classmethod
-    def quantized_from(cls, dense: torch.Tensor, device, blocksize: int = 64) -> "Params4bit":
-        """Quantise like ``Params4bit.cuda()``: the weight is cast to fp16 first, then blockwise FP4."""
+    def quantized_from(cls, dense: torch.Tensor, device, blocksize: int = 64, quant_type: str = "fp4") -> "Params4bit":
+        """Quantise like ``Params4bit.cuda()``: the weight is cast to fp16 first, then blockwise FP4 or NF4."""
+        nf4 = check_quant_type(quant_type) == "nf4"
         w = dense.detach().contiguous().to(device=device, dtype=torch.float16)
-        packed, absmax = quantize_fp4(w, blocksize)
-        state = QuantState(absmax, dense.shape, fp4_code().to(device), blocksize, dense.dtype)
-        return cls(packed, False, state, blocksize, "fp4")
+        packed, absmax = (quantize_nf4 if nf4 else quantize_fp4)(w, blocksize)
+        code = (nf4_code() if nf4 else fp4_code()).to(device)
+        state = QuantState(absmax, dense.shape, code, blocksize, dense.dtype, quant_type)
+        return cls(packed, False, state, blocksize, quant_type)
 
 
 class LinearFP4(nn.Linear):
-    """Drop-in for ``bitsandbytes.nn.LinearFP4``: dense until it reaches a GPU, FP4 afterwards."""
+    """Drop-in for ``bitsandbytes.nn.LinearFP4``: dense until it reaches a GPU, FP4 afterwards.  ``quant_type="nf4"``
+    (what ``bitsandbytes.nn.Linear4bit(..., quant_type="nf4")`` means) quantises to NF4 instead."""
 
     def __init__(self, input_features: int, output_features: int, bias: bool = True,
-                 compute_dtype: Optional[torch.dtype] = None, blocksize: int = 64, device=None):
+                 compute_dtype: Optional[torch.dtype] = None, blocksize: int = 64, device=None, quant_type: str = "fp4"):
         super().__init__(input_features, output_features, bias, device=device)
         self.compute_dtype = compute_dtype
         self.blocksize = blocksize
-        self.weight = Params4bit(self.weight.data, False, None, blocksize, "fp4")
+        self.quant_type = check_quant_type(quant_type)
+        self.weight = Params4bit(self.weight.data, False, None, blocksize, quant_type)
 
     def _apply(self, fn, recurse=True):
         w = self._parameters.pop("weight")
@@ -98,9 +117,9 @@ class LinearFP4(nn.Linear):
         probe = fn(torch.empty(0, dtype=torch.float16, device=w.device))
         if getattr(w, "quant_state", None) is None:
             if probe.device.type == "cuda":
-                self._parameters["weight"] = Params4bit.quantized_from(w.data, probe.device, self.blocksize)
+                self._parameters["weight"] = Params4bit.quantized_from(w.data, probe.device, self.blocksize, self.quant_type)
             else:
-                self._parameters["weight"] = Params4bit(fn(w.data), False, None, self.blocksize, "fp4")
+                self._parameters["weight"] = Params4bit(fn(w.data), False, None, self.blocksize, self.quant_type)
         elif probe.device != w.device:
             w.quant_state.to(probe.device)
             self._parameters["weight"] = Params4bit(w.data.to(probe.device), False, w.quant_state, w.blocksize, w.quant_type)
@@ -110,6 +129,14 @@ class LinearFP4(nn.Linear):
         if getattr(self.weight, "quant_state", None) is None:
             return nn.functional.linear(x, self.weight.to(x.dtype), None if self.bias is None else self.bias.to(x.dtype))
         raise RuntimeError("LinearFP4 holds packed FP4 weights; wrap it in TorchFP4Linear to run it")
+
+
+class LinearNF4(LinearFP4):
+    """Drop-in for ``bitsandbytes.nn.LinearNF4``: ``LinearFP4`` with ``quant_type="nf4"``."""
+
+    def __init__(self, input_features: int, output_features: int, bias: bool = True,
+                 compute_dtype: Optional[torch.dtype] = None, blocksize: int = 64, device=None):
+        super().__init__(input_features, output_features, bias, compute_dtype, blocksize, device, quant_type="nf4")
 
 
 Linear4bit = LinearFP4

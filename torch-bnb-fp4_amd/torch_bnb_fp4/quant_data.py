@@ -13,6 +13,10 @@ numel == last dim, other ranks        ``qlinear``                        (:614-6
 everything else (batch or seq > 1)    ``qlinear`` = dequant + F.linear   (:616-617)
 ====================================  =========================================
 
+NF4 weights (``quant_state.quant_type == "nf4"``) take the same table with the NF4 ops: the GEMV row runs ``gemv_nf4``, every
+other row ``qlinear_nf4`` whatever ``use_codebook_dequant`` says (NF4 has one table), and ``small_batch_fused`` is ignored (the
+small-batch kernels decode FP4 only).  Any other ``quant_type`` is refused.
+
 Two extensions.  ``fuse_bias`` (ON by default) folds the post-GEMV ``out += bias`` into the kernel epilogue: the table above
 still holds and the result is bit-identical (``T(T(sum) + bias)``), there is just one launch fewer; ``fuse_bias=False`` runs the
 reference's two-step sequence literally.  ``small_batch_fused`` (OFF by default, because it changes the table's last row) sends
@@ -28,6 +32,7 @@ import torch
 from ._ext import ext
 from .dtypes import ScalarType
 from .functional import dequantize_fp4_codebook_invoke_qtype, dequantize_fp4_qtype
+from .nn import check_quant_type
 
 
 class QuantData:
@@ -36,6 +41,8 @@ class QuantData:
                  allow_reduced_precision_linear: Optional[bool] = False, fuse_bias: bool = True,
                  small_batch_fused: bool = False):
         self.use_codebook_dequant = use_codebook_dequant
+        self.quant_type = check_quant_type(getattr(state, "quant_type", "fp4"))
+        self.nf4 = self.quant_type == "nf4"
         self.A = A
         self.absmax = state.absmax.float()
         self.blocksize = state.blocksize
@@ -62,6 +69,10 @@ class QuantData:
         else:
             self.qlinear = self._dequant_linear
         self.dequantize = self._dequantize_codebook if use_codebook_dequant else self._dequantize_normal
+        if self.nf4:
+            if allow_reduced_precision_linear:
+                self.qlinear = self._qlinear_nf4
+            self.dequantize = self._dequantize_nf4
 
     def rebind(self, A: torch.Tensor, absmax: torch.Tensor, code: torch.Tensor, bias: Optional[torch.Tensor]) -> None:
         """Point the dispatcher at new storage for the packed weight / scales / code / bias (after a device move or a
@@ -89,6 +100,9 @@ class QuantData:
         return dequantize_fp4_codebook_invoke_qtype(self.A, self.absmax, self.code, self.blocksize, self.M, self.N,
                                                     self.numel, self.qtype)
 
+    def _dequantize_nf4(self) -> torch.Tensor:
+        return ext.dequantize_nf4(self.A, self.absmax, self.blocksize, self.M, self.N, self.qtype)
+
     def _dequantize_normal(self) -> torch.Tensor:
         return dequantize_fp4_qtype(self.A, self.absmax, self.blocksize, self.M, self.N, self.qtype)
 
@@ -98,6 +112,8 @@ class QuantData:
         # (plain stores; standalone dequantize() streams it out non-temporally), and one Python round trip is saved.
         if A.dtype != self.o_type:
             return torch.nn.functional.linear(A, self.dequantize(), self.bias)
+        if self.nf4:
+            return self._qlinear_nf4(A)
         return self._qlinear_low_precision_codebook(A) if self.use_codebook_dequant else self._qlinear_low_precision_normal(A)
 
     # -- fused paths -----------------------------------------------------------------------------
@@ -105,9 +121,18 @@ class QuantData:
         # the reference hands the packed [numel/2, 1] tensor over transposed (:486); it stays contiguous
         if self._B_t.data_ptr() != self.A.data_ptr():  # the packed tensor was replaced (e.g. a device move)
             self._B_t = self.A.t()
+        if self.nf4:
+            if bias is not None:
+                return ext.gemv_nf4_bias(A, self._B_t, self.absmax, self.blocksize, self.qtype, self._shape_list, bias)
+            return ext.gemv_nf4(A, self._B_t, self.absmax, self.blocksize, self.qtype, self._shape_list)
         if bias is not None:
             return ext.gemv_fp4_bias(A, self._B_t, self.absmax, self.code, self.blocksize, self.qtype, self._shape_list, bias)
         return ext.gemv_fp4(A, self._B_t, self.absmax, self.code, self.blocksize, self.qtype, self._shape_list)
+
+    def _qlinear_nf4(self, A: torch.Tensor) -> torch.Tensor:
+        if self.bias is None:
+            return ext.qlinear_nf4(A, self.A, self.absmax, self.M, self.N, self.blocksize)
+        return ext.qlinear_nf4_bias(A, self.A, self.absmax, self.M, self.N, self.blocksize, self.bias)
 
     def _qlinear_low_precision_normal(self, A: torch.Tensor) -> torch.Tensor:
         if self.bias is None:
@@ -146,7 +171,7 @@ class QuantData:
             return self.forward(A)
         # everything that is not a 2-D / 3-D single token with K % blocksize == 0 (:593-594, :614-617)
         rows = total // K
-        if self.small_batch_fused and 2 <= rows <= 128 and (
+        if self.small_batch_fused and not self.nf4 and 2 <= rows <= 128 and (
                 (A.dtype in (torch.float16, torch.bfloat16)
                  and ((self.blocksize == 64 and K % 64 == 0) or (rows <= 8 and K % self.blocksize == 0 and K % 32 == 0 and K <= 4096)))
                 or (A.dtype == torch.float32 and rows <= 8 and K % self.blocksize == 0)):  # f32: one f32 GEMV per row, up to 8 rows

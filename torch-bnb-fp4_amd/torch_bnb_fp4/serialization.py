@@ -9,6 +9,9 @@ A pre-quantised bitsandbytes checkpoint stores, per ``Linear4bit`` weight (key n
     <prefix>weight.quant_state.bitsandbytes__fp4     uint8  [len]          utf-8 JSON: quant_type, blocksize, dtype, shape
     <prefix>bias                                     (optional)
 
+An NF4 weight has the same entries with ``weight.quant_state.bitsandbytes__nf4``, ``"quant_type": "nf4"`` and the NF4 code as
+``quant_map``; on load the map must equal this package's NF4 table bit for bit (custom maps are refused, not decoded).
+
 The reference cannot load or save its layers at all (its wrapped module is hidden in a python list,
 torch_bnb_fp4/__init__.py:644); this module round-trips :class:`TorchFP4Linear` through exactly that format, so
 FP4 safetensors written by bitsandbytes/transformers load straight into the MI355X path without re-quantising.
@@ -22,9 +25,10 @@ from typing import Dict, Mapping
 import torch
 
 from .linear import TorchFP4Linear
-from .nn import LinearFP4, Params4bit, QuantState
+from .nn import LinearFP4, Params4bit, QuantState, nf4_code
 
 _STATE_KEY = "weight.quant_state.bitsandbytes__fp4"
+_STATE_KEYS = {"fp4": _STATE_KEY, "nf4": "weight.quant_state.bitsandbytes__nf4"}
 
 
 def _pack_json(d: dict) -> torch.Tensor:
@@ -35,13 +39,13 @@ def _unpack_json(t: torch.Tensor) -> dict:
     return json.loads(bytes(t.detach().cpu().to(torch.uint8).tolist()).decode("utf-8"))
 
 
-def _bnb_entries(prefix: str, packed, absmax, code, blocksize: int, shape, dtype, bias) -> Dict[str, torch.Tensor]:
-    meta = {"quant_type": "fp4", "blocksize": int(blocksize), "dtype": str(dtype).replace("torch.", ""), "shape": [int(shape[0]), int(shape[1])]}
+def _bnb_entries(prefix: str, packed, absmax, code, blocksize: int, shape, dtype, bias, quant_type: str = "fp4") -> Dict[str, torch.Tensor]:
+    meta = {"quant_type": quant_type, "blocksize": int(blocksize), "dtype": str(dtype).replace("torch.", ""), "shape": [int(shape[0]), int(shape[1])]}
     out = {
         prefix + "weight": packed.detach().cpu().reshape(-1, 1),
         prefix + "weight.absmax": absmax.detach().float().cpu(),
         prefix + "weight.quant_map": code.detach().float().cpu(),
-        prefix + _STATE_KEY: _pack_json(meta),
+        prefix + _STATE_KEYS[quant_type]: _pack_json(meta),
     }
     if bias is not None:
         out[prefix + "bias"] = bias.detach().cpu()
@@ -51,7 +55,8 @@ def _bnb_entries(prefix: str, packed, absmax, code, blocksize: int, shape, dtype
 def fp4_linear_to_bnb_state(layer: TorchFP4Linear, prefix: str = "") -> Dict[str, torch.Tensor]:
     """State-dict entries of one layer in bitsandbytes' 4-bit layout (tensors moved to the CPU)."""
     qd = layer.quant_data
-    return _bnb_entries(prefix, qd.A, qd.absmax, qd.code, qd.blocksize, (qd.M, qd.N), qd.quant_state.dtype, layer.bias)
+    return _bnb_entries(prefix, qd.A, qd.absmax, qd.code, qd.blocksize, (qd.M, qd.N), qd.quant_state.dtype, layer.bias,
+                        qd.quant_type)
 
 
 def fused_linear_to_bnb_state(layer, prefix: str = "", pair_prefixes=None, dtype=None) -> Dict[str, torch.Tensor]:
@@ -79,14 +84,16 @@ def fused_linear_to_bnb_state(layer, prefix: str = "", pair_prefixes=None, dtype
 
 def fp4_linear_from_bnb_state(state: Mapping[str, torch.Tensor], prefix: str = "", device="cuda",
                               use_codebook_dequant: bool = True, name: str = "") -> TorchFP4Linear:
-    """Build a :class:`TorchFP4Linear` from bitsandbytes-format entries (no re-quantisation)."""
+    """Build a :class:`TorchFP4Linear` from bitsandbytes-format entries (no re-quantisation); FP4 or NF4."""
     if prefix + "weight.nested_absmax" in state:
         raise ValueError("nested (double-quantised) absmax is not supported")
-    if prefix + _STATE_KEY not in state:
-        raise KeyError(f"{prefix + _STATE_KEY} not found: not a bitsandbytes FP4 weight (NF4 is not supported)")
-    meta = _unpack_json(state[prefix + _STATE_KEY])
-    if meta.get("quant_type") != "fp4":
-        raise ValueError(f"quant_type {meta.get('quant_type')!r} is not fp4")
+    found = [qt for qt, key in _STATE_KEYS.items() if prefix + key in state]
+    if len(found) != 1:
+        raise KeyError(f"{prefix + _STATE_KEY} (or its __nf4 twin) not found exactly once: not a bitsandbytes 4-bit weight")
+    quant_type = found[0]
+    meta = _unpack_json(state[prefix + _STATE_KEYS[quant_type]])
+    if meta.get("quant_type") != quant_type:
+        raise ValueError(f"quant_type {meta.get('quant_type')!r} does not match the entry's key ({quant_type})")
     M, K = (int(v) for v in meta["shape"])
     bs = int(meta["blocksize"])
     dev = torch.device(device)
@@ -95,10 +102,12 @@ def fp4_linear_from_bnb_state(state: Mapping[str, torch.Tensor], prefix: str = "
     code = state[prefix + "weight.quant_map"].to(dev).float().contiguous()
     if packed.dtype != torch.uint8 or packed.numel() != (M * K + 1) // 2 or absmax.numel() != -(-M * K // bs) or code.numel() != 16:
         raise ValueError("inconsistent FP4 state: packed/absmax/quant_map sizes do not match the recorded shape")
+    if quant_type == "nf4" and not torch.equal(code.cpu().view(torch.int32), nf4_code().view(torch.int32)):
+        raise ValueError(f"{prefix}weight.quant_map is not bitsandbytes' NF4 code: custom quant maps are not supported")
     bias = state.get(prefix + "bias")
     shell = LinearFP4(K, M, bias=bias is not None, device="meta")
-    qs = QuantState(absmax, (M, K), code, bs, getattr(torch, meta.get("dtype", "float16")))
-    shell._parameters["weight"] = Params4bit(packed, False, qs, bs, "fp4")
+    qs = QuantState(absmax, (M, K), code, bs, getattr(torch, meta.get("dtype", "float16")), quant_type)
+    shell._parameters["weight"] = Params4bit(packed, False, qs, bs, quant_type)
     if bias is not None:
         shell._parameters["bias"] = torch.nn.Parameter(bias.to(dev), requires_grad=False)
     return TorchFP4Linear(shell, use_codebook_dequant=use_codebook_dequant, name=name)
@@ -160,7 +169,7 @@ def load_fp4_layers(model: torch.nn.Module, path: str, device="cuda", use_codebo
     from safetensors.torch import load_file
 
     state = load_file(path)
-    prefixes = sorted(k[: -len(_STATE_KEY)] for k in state if k.endswith(_STATE_KEY))
+    prefixes = sorted(k[: -len(key)] for k in state for key in _STATE_KEYS.values() if k.endswith(key))
     consumed = set()
     for prefix in prefixes:
         parent_name, _, child = prefix.rstrip(".").rpartition(".")

@@ -22,14 +22,14 @@ log = logging.getLogger(__name__)
 
 
 @torch.no_grad()
-def swap_linear_with_bnb_linear(linear: nn.Linear, dtype=torch.float16) -> LinearFP4:
+def swap_linear_with_bnb_linear(linear: nn.Linear, dtype=torch.float16, quant_type: str = "fp4") -> LinearFP4:
     """New (still dense) ``LinearFP4`` holding clones of ``linear``'s weight and bias; it quantises
-    when moved to a GPU (reference :717-747)."""
+    when moved to a GPU (reference :717-747).  ``quant_type="nf4"`` (not in the reference) quantises to NF4."""
     # built on the meta device: nn.Linear.__init__ would otherwise allocate and randomly initialise a full dense
     # weight on the CPU only to have it replaced (18 s of a 7B model's 224 layers)
     fp4 = LinearFP4(input_features=linear.in_features, output_features=linear.out_features,
-                    bias=linear.bias is not None, compute_dtype=dtype, device="meta")
-    fp4.weight = Params4bit(linear.weight.data.clone().detach(), False, None, fp4.blocksize, "fp4")
+                    bias=linear.bias is not None, compute_dtype=dtype, device="meta", quant_type=quant_type)
+    fp4.weight = Params4bit(linear.weight.data.clone().detach(), False, None, fp4.blocksize, quant_type)
     if linear.bias is not None:
         fp4.bias = nn.Parameter(linear.bias.data.clone().detach(), requires_grad=False)
     fp4.requires_grad_(False)
@@ -49,6 +49,9 @@ def todevice_if_necessary(module, device):
         w = module.weight
         if not (w.data.device == torch.device(device) and w.data.dtype == torch.uint8):
             log.debug("layer was not quantised by the device move; quantising its weight directly")
+            if getattr(module, "quant_type", "fp4") == "nf4":
+                module.weight = Params4bit.quantized_from(w.data, device, module.blocksize, "nf4")
+                return module
             dense = w.data.to(device=device, dtype=torch.float16)
             packed, absmax = quantize_fp4(dense, module.blocksize)
             state = QuantState(absmax, dense.shape, fp4_code().to(device), module.blocksize, w.data.dtype)
@@ -61,10 +64,10 @@ def _device_is_gpu(device) -> bool:
     return kind == "cuda"
 
 
-def _to_fp4_linear(layer: nn.Module, device, as_dtype, use_codebook_dequant: bool, name: str) -> TorchFP4Linear:
-    """nn.Linear or FP4 layer -> TorchFP4Linear on ``device``."""
+def _to_fp4_linear(layer: nn.Module, device, as_dtype, use_codebook_dequant: bool, name: str, quant_type: str = "fp4") -> TorchFP4Linear:
+    """nn.Linear or FP4 layer -> TorchFP4Linear on ``device`` (a dense nn.Linear is quantised to ``quant_type``)."""
     if not isinstance(layer, FP4_LINEAR_TYPES):
-        layer = swap_linear_with_bnb_linear(layer, dtype=as_dtype)
+        layer = swap_linear_with_bnb_linear(layer, dtype=as_dtype, quant_type=quant_type)
     layer = layer.to(device)
     if getattr(layer.weight, "quant_state", None) is None:
         layer = todevice_if_necessary(layer, device)
@@ -81,6 +84,7 @@ def recursively_replace_with_fp4_linear(
     ignore_layer_names: List[str] = ["lm_head"],
     parent="",
     debug: bool = False,
+    quant_type: str = "fp4",
 ) -> Optional[T_Model]:
     """Replace every nn.Linear / FP4 linear below ``module`` by a :class:`TorchFP4Linear`.
 
@@ -89,6 +93,8 @@ def recursively_replace_with_fp4_linear(
     leaves plain nn.Linear alone; a root that is itself a Linear is converted and returned;
     ``named_children()`` dedupes shared modules, so a Linear object reused in several slots is
     swapped only in the first one (the reference's sanity model relies on exactly that).
+    ``quant_type`` (not in the reference): the code dense nn.Linear layers are quantised to, ``"fp4"`` or ``"nf4"``;
+    layers that are already 4-bit keep their own.
     """
     assert _device_is_gpu(device), "Device type must be cuda!"
     prefix = parent + "." if parent != "" else ""
@@ -107,19 +113,20 @@ def recursively_replace_with_fp4_linear(
                 continue
             if debug:
                 print(f"Replacing {'FP4 layer ' if is_fp4 else ''}{child_name} with TorchFP4Linear.")
-            module._modules[name] = _to_fp4_linear(child, device, as_dtype, use_codebook_dequant, child_name)
+            module._modules[name] = _to_fp4_linear(child, device, as_dtype, use_codebook_dequant, child_name, quant_type)
             swapped_dense |= not is_fp4
         elif isinstance(child, nn.Module):
             recursively_replace_with_fp4_linear(child, as_dtype=as_dtype, use_codebook_dequant=use_codebook_dequant,
                                                 device=device, return_final_module=False,
                                                 only_replace_bnb_layers=only_replace_bnb_layers,
-                                                ignore_layer_names=ignore_layer_names, parent=child_name, debug=debug)
+                                                ignore_layer_names=ignore_layer_names, parent=child_name, debug=debug,
+                                                quant_type=quant_type)
     if isinstance(module, (nn.Linear,) + FP4_LINEAR_TYPES):
         is_fp4 = isinstance(module, FP4_LINEAR_TYPES)
         if is_fp4 or not only_replace_bnb_layers:
             if debug:
                 print(f"Replacing {parent} with TorchFP4Linear.")
-            module = _to_fp4_linear(module, device, as_dtype, use_codebook_dequant, parent)
+            module = _to_fp4_linear(module, device, as_dtype, use_codebook_dequant, parent, quant_type)
             swapped_dense |= not is_fp4
         elif debug:
             print(f"Ignoring {parent}, as only_replace_bnb_layers=True")
@@ -134,10 +141,11 @@ def set_small_batch_fused(module: nn.Module, enabled: bool = True) -> int:
     (``enabled=True``) or back to the reference's dispatch, dequant + GEMM for every batch > 1
     (torch_bnb_fp4/__init__.py:592,616-617; the default, so that a converted model behaves like the reference's).
     Not part of the reference surface.  Returns the number of layers touched.  Batched decode through Mistral-7B shapes:
-    3 237 tok/s fused vs 963 tok/s through the reference dispatch at 8 sequences (profiles/)."""
+    3 237 tok/s fused vs 963 tok/s through the reference dispatch at 8 sequences (profiles/).  NF4 layers are left on
+    dequant + GEMM (the small-batch kernels decode FP4 only) and not counted."""
     n = 0
     for m in module.modules():
-        if isinstance(m, TorchFP4Linear):
+        if isinstance(m, TorchFP4Linear) and not m.quant_data.nf4:
             m.quant_data.small_batch_fused = bool(enabled)
             n += 1
     return n
@@ -173,6 +181,7 @@ def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_pr
         g, u, d, a = (getattr(child, n, None) for n in (gate, up, down, act))
         silu = isinstance(a, nn.SiLU) or "silu" in type(a).__name__.lower() or a is nn.functional.silu
         if (isinstance(g, TorchFP4Linear) and isinstance(u, TorchFP4Linear) and isinstance(d, nn.Module) and silu
+                and not (g.quant_data.nf4 or u.quant_data.nf4)  # the gate|up epilogue kernels decode FP4 only: NF4 stays unfused
                 and (g.quant_data.M, g.quant_data.N, g.quant_data.blocksize) == (u.quant_data.M, u.quant_data.N, u.quant_data.blocksize)
                 ):
             module._modules[name] = FusedGatedMLP(g, u, d, names=(gate, up))
