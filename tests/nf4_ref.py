@@ -5,7 +5,9 @@ bitsandbytes is not installed where these tests run, so its published constants 
 * CODE_DECIMAL - ``get_4bit_type('nf4')`` / the literals of ``dDequantizeNF4``; the f32 table is their f32 rounding.
 * THRESHOLD_DECIMAL - the literals of ``dQuantizeNF4``'s decision tree: the midpoints of neighbouring codes.
 Quantiser: absmax = max|w| per block, x = w * (1/absmax) in f32, nibble = #{i : x > T[i]} (strict), even element in the high
-nibble.  Dequant: out = RN_T(f32(code[nibble]) * absmax).
+nibble.  An odd length is padded with one 0.0 in the last block, ranked like any other element: the spare low nibble of the last
+byte is rank(0 * (1/absmax)) = 7 for a finite non-zero or an infinite scale, 0 for a zero or NaN one (bitsandbytes' blockwise
+quantiser zero-fills its last block and stores ceil(n/2) bytes of what it ranked).  Dequant: out = RN_T(f32(code[nibble]) * absmax).
 """
 from __future__ import annotations
 
@@ -87,12 +89,44 @@ def quantize(w: np.ndarray, blocksize: int):
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         absmax = np.max(np.abs(blocks), axis=1).astype(np.float32)
         inv = (np.float32(1.0) / absmax).astype(np.float32)
-        x = (blocks * inv[:, None]).astype(np.float32).ravel()[:n]
+        x = (blocks * inv[:, None]).astype(np.float32).ravel()[: n + n % 2]  # odd n: the zero pad of the last block is ranked too
     nib = rank(x)
-    if n % 2:
-        nib = np.concatenate([nib, np.zeros(1, np.uint8)])
     packed = ((nib[0::2] << 4) | nib[1::2]).astype(np.uint8)
     return packed, absmax
+
+
+def gemv_cell(M: int, K: int):
+    """(ks, G, iters) of the fast NF4 GEMV kernel for an (M, K) it takes: the rule of dispatch_nf4 (csrc/gemv_nf4.hip:185-200).
+    A workgroup covers 2 * (4 / ks) * iters rows and one pass G * 32 * ks chunks of 32 weights."""
+    C = K >> 5
+    ks = 1 if C <= 32 else (2 if C <= 64 else 4)
+    G = 1 if C <= 128 else 2
+    iters = 1
+    while iters < 4 and M // (2 * (4 // ks) * iters * 2) >= 256:
+        iters *= 2
+    return ks, G, iters
+
+
+def rows_per_workgroup(ks: int, iters: int) -> int:
+    return 2 * (4 // ks) * iters
+
+
+# (M, K) cases of tests/test_gpu_nf4_gemv.py: each of the 12 cells twice, once with M a multiple of its rows per workgroup and once
+# with a row tail; K with partial last passes (C not a multiple of G * 32 * ks) and several passes (K > 8192)
+GEMV_CELL_CASES = [
+    (64, 1024), (1023, 992),        # ks 1, G 1, iters 1
+    (4096, 1024), (4097, 800),      # ks 1, G 1, iters 2
+    (8192, 512), (8193, 736),       # ks 1, G 1, iters 4
+    (256, 2048), (2047, 1056),      # ks 2, G 1, iters 1
+    (2048, 2048), (2049, 1600),     # ks 2, G 1, iters 2
+    (4096, 2048), (4097, 1088),     # ks 2, G 1, iters 4
+    (512, 4096), (1023, 2080),      # ks 4, G 1, iters 1
+    (1024, 4096), (1025, 3104),     # ks 4, G 1, iters 2
+    (2048, 4096), (2049, 4064),     # ks 4, G 1, iters 4
+    (512, 8224), (1023, 32768),     # ks 4, G 2, iters 1
+    (1024, 14336), (1025, 8224),    # ks 4, G 2, iters 2
+    (2048, 32768), (4097, 4128),    # ks 4, G 2, iters 4
+]
 
 
 def unpack(packed: np.ndarray, n: int) -> np.ndarray:

@@ -6,7 +6,8 @@ must fall back to 64-bit addressing - silently and correctly, the reference take
 (/root/reference/csrc/gemv_fp4_optimized.cu:289-299 derives everything from Bshape).  Nothing below the boundary exercises those branches,
 so this file does: M x K = 262144 x 16384 = exactly 2^32, and 2^32 + one row.  EVERY output row is checked against the float64 product
 formed on the device by the pure-torch oracle (oracle/torch_cpu.py), which is tied to the C oracle on sampled rows (first, last and the
-rows on either side of each 2^31 / 2^32-byte offset boundary).  Same bar as tests/test_gpu_gemv.py."""
+rows on either side of each 2^31 / 2^32-byte offset boundary).  Same bar as tests/test_gpu_gemv.py.  The NF4 GEMV reads the same bytes
+with the NF4 code (its product tied to tests/nf4_ref.py), and the NF4 quantiser gets the repeated-pattern test of the FP4 one."""
 import numpy as np
 import pytest
 import torch
@@ -149,3 +150,67 @@ def test_quantiser_and_dequant_past_2_to_the_31_elements(dtype):
     o2 = out.view(reps, unit).view(torch.int16)
     want = o.dequantize(want_p, want_a, BS, unit, "bfloat16", "codebook")
     assert np.array_equal(o2[0].cpu().numpy().view(np.uint16), want) and bool((o2 == o2[0]).all())
+
+
+# ---- NF4 (csrc/gemv_nf4.hip, csrc/quantize_nf4.hip): 64-bit chunk and element indices -------------------------------------------------
+def test_nf4_gemv_at_and_beyond_2_pow_32_elements(huge):
+    """The same random bytes read as NF4 (every byte is a valid pair of NF4 codes): 2^32 and 2^32 + K weights, EVERY row against
+    the float64 product formed on the device with the NF4 code as the oracle's table, tied to the numpy restatement on the sampled
+    rows; f16, bf16 and f32, and the fused bias bit for bit."""
+    import nf4_ref as R
+    from test_gpu_nf4_gemv import check_bar, device_products
+
+    M_all, packed_d, absmax_d = huge
+    g = torch.Generator().manual_seed(98)
+    dtypes = (torch.bfloat16, torch.float16, torch.float32)
+    x32 = torch.randn(K, generator=g)
+    xs = [x32.to(dt).to(dev()) for dt in dtypes]
+    exact_d, scale_d = device_products(packed_d, absmax_d, M_all, K, BS, xs)
+    sample = _sample_rows(M_all)
+    p_rows = packed_d.view(M_all, K // 2)[torch.from_numpy(sample).to(dev())].cpu().numpy().reshape(-1)
+    a_rows = absmax_d.view(M_all, K // BS)[torch.from_numpy(sample).to(dev())].cpu().numpy().reshape(-1)
+    for i, x in enumerate(xs):
+        want, _ = R.gemv_exact(x.double().cpu().numpy(), p_rows, a_rows, len(sample), K, BS)
+        assert np.allclose(exact_d[i, torch.from_numpy(sample).to(dev())].cpu().numpy(), want, rtol=1e-11, atol=1e-13)
+    for M in (M_all - 1, M_all):
+        assert M * K >= 2**32
+        P, A = packed_d[: M * K // 2], absmax_d[: M * K // BS]
+        for i, dtype in enumerate(dtypes):
+            y = R.gemv(xs[i], P, A, M, K, BS)
+            _check(y, exact_d[i, :M], scale_d[i, :M], dtype, ("gemv_nf4", M))
+            if M == M_all:
+                bias = (torch.randn(M, generator=g) * 0.1).to(dtype).to(dev())
+                fused = R.gemv(xs[i], P, A, M, K, BS, bias=bias)
+                assert torch.equal(fused, (y.float() + bias.float()).to(dtype)), dtype
+            del y
+    del exact_d, scale_d
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_nf4_quantiser_and_dequant_past_2_to_the_31_elements(dtype):
+    """The NF4 quantiser on 2^31 + 2^22 elements (element offsets past 2^31, byte offsets of the f32 input past 2^33): one 2^20-element
+    pattern repeated must quantise to the pattern's bytes and scales repeated, the pattern's own result bit for bit the numpy
+    restatement's; the NF4 dequant of the huge result likewise the restated dequant of the pattern, repeated."""
+    import nf4_ref as R
+
+    free, _ = torch.cuda.mem_get_info()
+    unit, reps = 1 << 20, (1 << 11) + 4
+    n = unit * reps
+    if free < (n * (4 + torch.empty((), dtype=dtype).element_size()) + (4 << 30)):
+        pytest.skip("needs ~24 GiB of free device memory")
+    rng = np.random.default_rng(12)
+    pat = (rng.standard_normal(unit) * 10.0 ** rng.uniform(-2, 1, unit)).astype(np.float32)
+    pat[64:128] = 0.0
+    pat_t = torch.from_numpy(pat).to(dtype).to(dev())
+    want_p, want_a = R.quantize(pat_t.float().cpu().numpy(), BS)
+    w = pat_t.repeat(reps)
+    assert w.numel() == n and n > (1 << 31)
+    packed, absmax = R.quantize_dev(w, BS)
+    del w
+    p2, a2 = packed.view(reps, unit // 2), absmax.view(reps, unit // BS)
+    assert np.array_equal(p2[0].cpu().numpy(), want_p) and np.array_equal(a2[0].cpu().numpy(), want_a)
+    assert bool((p2 == p2[0]).all()) and bool((a2 == a2[0]).all())  # every repetition, the ones past 2^31 included
+    out = hipabi.dequantize(packed, absmax, BS, n, torch.bfloat16, table=R.TABLE_NF4)
+    o2 = out.view(reps, unit).view(torch.int16)
+    want = torch.from_numpy(R.dequantize_f32(want_p, want_a, BS, unit)).to(torch.bfloat16).view(torch.int16).numpy()
+    assert np.array_equal(o2[0].cpu().numpy(), want) and bool((o2 == o2[0]).all())

@@ -62,6 +62,34 @@ def test_dequant_past_2_31_elements():
     del out, packed
 
 
+_FULL = {}
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("variant", [-1, 1, 2, 4, 8, 16, 8 | 256, 2 | 256])
+def test_full_size_4096x4096_bit_exact_every_variant(dtype, variant):
+    """Every dequant geometry (LOADS | NT << 8) that the FP4 test runs, with the NF4 table (dequant_tiles_nf4_kernel<DT, LOADS, NT>)."""
+    n = 4096 * 4096
+    if "in" not in _FULL:
+        rng = np.random.default_rng(101)
+        packed = rng.integers(0, 256, n // 2, dtype=np.uint8)
+        am = (rng.random(n // 64, dtype=np.float32) * 0.1 + 0.01).astype(np.float32)
+        am[::97] = 0.0
+        _FULL["in"] = (packed, am, to_dev(packed), to_dev(am))
+    packed, am, P, A = _FULL["in"]
+    if dtype not in _FULL:
+        _FULL[dtype] = _round_to(R.dequantize_f32(packed, am, 64, n), dtype)
+    hipabi.set_variant("dequant", variant)
+    out = torch.empty(n, dtype=dtype, device=dev())
+    if dtype != torch.float32 and variant in (16, 8 | 256):  # not built for 16-bit output: refused, never computed
+        rc = hipabi.lib().fp4_hip_dequantize_blockwise(P.data_ptr(), A.data_ptr(), out.data_ptr(), 64, n, hipabi.DT[dtype], R.TABLE_NF4, 0, None)
+        assert rc == hipabi.ERR_INVALID and "unknown kernel variant" in hipabi.last_error()
+        return
+    hipabi.dequantize(P, A, 64, n, dtype, table=R.TABLE_NF4, out=out)
+    torch.cuda.synchronize()
+    assert np.array_equal(bits(out), _FULL[dtype])
+
+
 # ---- quantiser -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("bs", [32, 64, 4096])
@@ -98,6 +126,63 @@ def test_quantize_f32_random_thresholds_and_special_blocks(bs):
         assert (p.cpu().numpy() == want_p).all(), ragged
         assert _same_f32(a.cpu().numpy(), want_a), ragged
     assert (want_p[bs: 3 * bs // 2] == 0).all()  # the all-zero block: 0x00 bytes
+
+
+def _tail_lengths(bs):
+    return sorted({1, 3, 7, 9, bs - 1, bs + 1, 4095, 4097, 3 * 4096 - 1, 3 * 4096 + 1, 4096 + bs + 3, 3 * 4096 + bs + 3})
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("bs", [32, 64, 128, 256, 512, 1024, 2048, 4096])
+def test_quantize_odd_and_ragged_lengths(dtype, bs):
+    """Odd n leaves a spare low nibble in the last byte: the kernel ranks the zero it pads the last block with, as bitsandbytes does
+    (7 under a finite non-zero or an infinite scale, 0 under a zero or NaN one - tests/nf4_ref.py), and writes exactly ceil(n/2)
+    bytes.  Ragged lengths around the 4096-element tile, the last block plain, all zero, holding an inf, or holding a NaN."""
+    rng = np.random.default_rng(bs)
+    for n in _tail_lengths(bs):
+        last = (n - 1) // bs * bs
+        for tail in ("plain", "zero", "inf", "nan"):
+            w32 = (rng.standard_normal(n) * 0.05).astype(np.float32)
+            if tail == "zero":
+                w32[last:] = 0.0
+            elif tail == "inf":
+                w32[last + (n - last) // 2] = -np.inf
+            elif tail == "nan":
+                w32[n - 1] = np.nan
+            w = torch.from_numpy(w32).to(dtype)
+            want_p, want_a = R.quantize(w.float().numpy(), bs)
+            # packed with a guard region behind it: nothing past byte ceil(n/2) - 1 may be written
+            buf = torch.full((want_p.size + 64,), 0xA5, dtype=torch.uint8, device=dev())
+            absmax = torch.empty(want_a.size, dtype=torch.float32, device=dev())
+            rc = R.lib().fp4_hip_quantize_blockwise_nf4(hipabi._ptr(w.to(dev())), hipabi.DT[dtype], hipabi._ptr(buf), hipabi._ptr(absmax), n,
+                                                      bs, hipabi._stream())
+            assert rc == hipabi.OK, (rc, hipabi.last_error())
+            got = buf.cpu().numpy()
+            assert (got[: want_p.size] == want_p).all(), (n, tail, got[want_p.size - 2: want_p.size].tolist(), want_p[-2:].tolist())
+            assert (got[want_p.size:] == 0xA5).all(), (n, tail)
+            assert _same_f32(absmax.cpu().numpy(), want_a), (n, tail)
+            if n % 2:
+                pad = {"plain": 7, "zero": 0, "inf": 7, "nan": 0}[tail]  # scale finite, 0, inf, NaN
+                assert got[want_p.size - 1] & 15 == pad, (n, tail)
+
+
+def test_quantize_odd_length_first_case_and_the_torch_op():
+    """[0.5, 0.1, 0.3] at bs = 32 is F9 D7 (the pad ranks as 0.0 -> 7); the torch op returns [ceil(n/2), 1] bytes for an odd n and
+    its n dequantised values are the restatement's, bit for bit."""
+    for dtype in DTYPES:
+        p, a = R.quantize_dev(torch.tensor([0.5, 0.1, 0.3], dtype=dtype, device=dev()), 32)
+        assert p.cpu().numpy().tobytes() == bytes([0xF9, 0xD7]) and a.cpu().tolist() == [0.5], dtype
+    rng = np.random.default_rng(8)
+    for n in (1, 3, 4097, 65 * 64 + 1):
+        for dtype in DTYPES:
+            w = torch.from_numpy((rng.standard_normal(n) * 0.05).astype(np.float32)).to(dtype)
+            packed, absmax = pkg.quantize_nf4(w.to(dev()), 64)
+            assert tuple(packed.shape) == ((n + 1) // 2, 1) and packed.dtype == torch.uint8 and tuple(absmax.shape) == (-(-n // 64),)
+            want_p, want_a = R.quantize(w.float().numpy(), 64)
+            assert (packed.cpu().numpy().reshape(-1) == want_p).all() and _same_f32(absmax.cpu().numpy(), want_a), (n, dtype)
+            d = pkg.dequantize_nf4(packed, absmax, 64, 1, n, dtype)
+            assert tuple(d.shape) == (1, n)
+            assert (bits(d).reshape(-1) == _round_to(R.dequantize_f32(want_p, want_a, 64, n), dtype)).all(), (n, dtype)
 
 
 def test_quantize_dequant_quantize_is_a_fixed_point():
@@ -326,3 +411,51 @@ def test_fp4_only_paths_leave_nf4_alone():
     root.mlp = mlp
     assert pkg.fuse_gated_mlps(root) == 0 and root.mlp is mlp
     assert pkg.set_small_batch_fused(root) == 0 and not g.quant_data.small_batch_fused
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_nf4_unfused_bias_is_bit_identical_to_the_fused_call(dtype):
+    """fuse_bias=False (GEMV, then out += bias) against the default fused epilogue: T(T(sum) + bias) both ways, 2-D and 3-D tokens."""
+    fused, _ = _nf4_layer(K=4096, M=1024, seed=3)
+    x = torch.randn(1, 4096, device=dev()).to(dtype)
+    y_fused, y3_fused = fused(x), fused(x.view(1, 1, 4096))
+    fused.quant_data.fuse_bias = False
+    try:
+        assert torch.equal(bits_t(fused(x)), bits_t(y_fused))
+        assert torch.equal(bits_t(fused(x.view(1, 1, 4096))), bits_t(y3_fused))
+    finally:
+        fused.quant_data.fuse_bias = True
+    exact, scale = _restated(fused, x.float())
+    err = np.abs(y_fused.double().cpu().numpy() - exact)
+    assert (err <= 2.02 * HALF_ULP[dtype] * (np.abs(exact) + scale) + 1e-5 * scale + 1e-6).all()
+
+
+def test_nf4_single_token_with_k_not_a_multiple_of_the_blocksize_takes_qlinear_nf4(monkeypatch):
+    """One token whose K is not a multiple of the blocksize is not a GEMV row (quant_data.forward): it must run qlinear_nf4[_bias],
+    and give exactly what that op gives."""
+    from torch_bnb_fp4 import quant_data as qd_mod
+
+    calls = []
+
+    class Recording:
+        def __getattr__(self, name):
+            calls.append(name)
+            return getattr(pkg.ext, name)
+
+    for bias in (True, False):
+        layer, _ = _nf4_layer(K=96, M=256, bias=bias, seed=4)
+        qd = layer.quant_data
+        assert qd.blocksize == 64 and 96 % qd.blocksize
+        x = torch.randn(1, 96, device=dev(), dtype=torch.bfloat16)
+        layer(x)  # compute dtype set on the first call
+        calls.clear()
+        monkeypatch.setattr(qd_mod, "ext", Recording())
+        y = layer(x)
+        monkeypatch.undo()
+        assert calls == ["qlinear_nf4_bias" if bias else "qlinear_nf4"], calls
+        direct = (pkg.ext.qlinear_nf4_bias(x, qd.A, qd.absmax, qd.M, qd.N, qd.blocksize, qd.bias) if bias else
+                  pkg.ext.qlinear_nf4(x, qd.A, qd.absmax, qd.M, qd.N, qd.blocksize))
+        assert torch.equal(y, direct)
+        exact, scale = _restated(layer, x.float())
+        err = np.abs(y.double().cpu().numpy() - exact)
+        assert (err <= 2.02 * HALF_ULP[torch.bfloat16] * (np.abs(exact) + scale) + 1e-5 * scale + 1e-6).all()

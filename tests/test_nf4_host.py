@@ -74,6 +74,53 @@ def test_all_zero_block_is_zero_bytes_and_dequantises_to_minus_zero():
     assert (_bits(out) == 0x80000000).all()
 
 
+def test_odd_length_pads_with_a_ranked_zero():
+    """An odd n leaves the low nibble of the last byte spare; it holds rank(0.0 * (1/absmax)) of the last block's scale, as
+    bitsandbytes' quantiser (zero-filled last block, ceil(n/2) bytes stored) and the kernel write it - not a bare 0."""
+    packed, absmax = R.quantize(np.array([0.5, 0.1, 0.3], np.float32), 32)
+    assert packed.tobytes() == bytes([0xF9, 0xD7]) and absmax.tolist() == [0.5]
+    cases = [  # last block -> spare nibble
+        (np.float32(0.25), 7),     # finite, non-zero scale: 0 * 4 = 0 -> 7
+        (np.float32(np.inf), 7),   # infinite scale: 0 * 0 = 0 -> 7
+        (np.float32(0.0), 0),      # zero scale: 0 * inf = NaN -> 0
+        (np.float32(np.nan), 0),   # NaN scale: NaN -> 0
+        (np.float32(1e-40), 0),    # subnormal scale: 1/absmax overflows to inf, 0 * inf = NaN -> 0
+    ]
+    for bs in (32, 64, 4096):
+        for v, want in cases:
+            for n in (1, 3, bs + 1, 2 * bs - 1):
+                w = np.full(n, 0.01, np.float32)
+                w[(n - 1) // bs * bs:] = v  # the whole last block
+                p, a = R.quantize(w, bs)
+                assert p.size == (n + 1) // 2 and a.size == -(-n // bs)
+                assert p[-1] & 15 == want, (bs, float(v), n)
+                assert (R.unpack(p, n + 1)[:n] == R.unpack(R.quantize(np.append(w, np.float32(0)), bs)[0], n)).all()  # pad: its own byte
+    for n in (2, 64):  # even n: no pad nibble
+        p, _ = R.quantize(np.full(n, 0.5, np.float32), 32)
+        assert p.size == n // 2 and (p == 0xFF).all()
+
+
+def test_gemv_cases_reach_every_dispatch_cell():
+    """tests/test_gpu_nf4_gemv.py runs R.GEMV_CELL_CASES: under the restated rule of dispatch_nf4 they reach all 12 cells
+    (ks in 1, 2, 4; G = 2 only at ks = 4; iters in 1, 2, 4), each once with M a multiple of its rows per workgroup and once with
+    a row tail, and the K values include partial last passes and more than one pass."""
+    all_cells = {(ks, 1, it) for ks in (1, 2, 4) for it in (1, 2, 4)} | {(4, 2, it) for it in (1, 2, 4)}
+    seen = {}
+    for M, K in R.GEMV_CELL_CASES:
+        assert K % 32 == 0 and 0 < K <= 32768 and 0 < M
+        ks, G, it = R.gemv_cell(M, K)
+        seen.setdefault((ks, G, it), set()).add(M % R.rows_per_workgroup(ks, it) != 0)
+    assert set(seen) == all_cells and len(all_cells) == 12
+    assert all(v == {False, True} for v in seen.values()), seen
+    passes = [-(-(K >> 5) // (G * 32 * ks)) for M, K in R.GEMV_CELL_CASES for ks, G, _ in [R.gemv_cell(M, K)]]
+    partial = [(K >> 5) % (G * 32 * ks) != 0 for M, K in R.GEMV_CELL_CASES for ks, G, _ in [R.gemv_cell(M, K)]]
+    assert max(passes) >= 4 and sum(p > 1 for p in passes) >= 4 and sum(partial) >= 12
+    # the thresholds the cases sit on either side of (issue: iters 2 from 4096 / 2048 / 1024 rows, 4 from 8192 / 4096 / 2048)
+    for ks, K, lo2, lo4 in ((1, 1024, 4096, 8192), (2, 2048, 2048, 4096), (4, 4096, 1024, 2048)):
+        assert R.gemv_cell(lo2 - 1, K)[2] == 1 and R.gemv_cell(lo2, K)[2] == 2
+        assert R.gemv_cell(lo4 - 1, K)[2] == 2 and R.gemv_cell(lo4, K)[2] == 4
+
+
 # ---- C ABI (host-side paths only: no GPU work) ------------------------------------------------------------------------------------
 def test_abi_code_table():
     assert (_bits(R.code_table()) == _bits(R.CODE)).all()
