@@ -239,6 +239,19 @@ FP4_HIP_API int fp4_hip_quantize_blockwise_nf4(const void *w, int w_dtype, uint8
                                                void *stream);
 
 /*
+ * fp4_hip_gemm_small_nf4: fp4_hip_gemm_small over an NF4 weight, for 1..16 activation rows on the matrix cores:
+ *   out[b][r] = T( sum_k x[b][k] * code[nibble(r,k)] * absmax[(r*K+k)/64] + bias[r] )       (bias optional; added in f32, ONE rounding)
+ * Same argument conventions as fp4_hip_gemm_small.  The NF4 codes are exact in neither fp16 nor bf16, so every weight is fed to
+ * v_mfma_f32_16x16x32 twice, as hi = T(code) and lo = T(code - hi) (fp16: lo * 2^24 in a tile of its own, so that no subnormal
+ * input is relied on), both read from a 256-entry LDS table indexed by the packed byte; |hi + lo - code| <= 5.45e-6 |code|.
+ * Covered: 1 <= B <= 16, blocksize 64, K % 512 == 0 (K <= 2^24), fp16 / bf16, any M >= 1 up to 2^30 (M * K may pass 2^32:
+ * 64-bit addressing), x and packed 16-byte aligned.  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, out untouched - the
+ * caller uses NF4 dequant + GEMM.  FP4_OK without a launch for M == 0 or B == 0.  No fused epilogues, no 17+ rows.
+ */
+FP4_HIP_API int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
+                                       int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream);
+
+/*
  * Tuning hook for benchmarks/sweeps: selects a kernel geometry by name
  * ("dequant", "gemv", "gemv_nf4" (0 = 16-entry f32 table, 1 = 256-entry pair table), "gemm_small", "gemm_wide" = rows per workgroup of the 17..64-row kernels (1 / 2 / 3 / 4 = 16 / 32 / 64 / 128, 5 = 16 with self-contained waves; 0 = off),
  * "quantize": 1..999 = the persistent kernel with that many workgroups per CU, 1001 / 1002 / 1004 = the one-shot tiles kernel with 1 / 2 / 4 loads per lane).  variant < 0 (quantize: 0) restores the built-in heuristic.

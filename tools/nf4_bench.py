@@ -5,6 +5,12 @@ NF4 GEMV over a stack of distinct weights (no cache reuse) as a fraction of 8 TB
 
 Timing as bench.py does it (its capture / time_replays helpers): R launches captured in one HIP graph, the median over replays,
 divided by R.  usage: python tools/nf4_bench.py [--reps 20] [--launches 20]
+
+--small-batch: the 2..16-row regime instead (profiles/nf4_small_batch.json).  Per dtype (bf16, fp16), shape and row count
+(2 / 4 / 8 / 16), in one run on the same operands: (a) gemm_small_nf4, the fused matrix-core kernel; (b) qlinear_nf4, NF4 dequant +
+hipBLASLt - what these calls cost without the switch; (c) gemm_small_fp4 on the same bytes (the price of the NF4 decode and of the
+doubled matrix work); (d) gemv_nf4 once per row.  (a) and (b) also carry min / max / p10 / p90 over the replays, and each cell says
+whether (a) beats (b) by more than the two full ranges (max - min) together.
 """
 import argparse
 import ctypes
@@ -40,11 +46,64 @@ def lib():
     return l
 
 
+def small_batch(args):
+    L = lib()
+    L.fp4_hip_gemm_small_nf4.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+    dev = torch.device("cuda", 0)
+    s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(L.fp4_hip_last_error().decode())
+
+    def timed(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        med, samples = time_replays(replay, args.reps, args.launches)
+        q = sorted(samples)
+        return {"us": round(med, 2), "min_us": round(q[0], 2), "max_us": round(q[-1], 2), "p10_us": round(q[len(q) // 10], 2),
+                "p90_us": round(q[-1 - len(q) // 10], 2)}
+
+    cells = []
+    for M, K in SHAPES:
+        n = M * K
+        torch.manual_seed(0)
+        w16 = (torch.randn(n, device=dev) * 0.02).to(torch.float16)
+        packed = torch.empty(n // 2, dtype=torch.uint8, device=dev)
+        absmax = torch.empty(n // BS, dtype=torch.float32, device=dev)
+        check(L.fp4_hip_quantize_blockwise_nf4(p_(w16), DT[torch.float16], p_(packed), p_(absmax), n, BS, s()))
+        del w16
+        B_t = packed.view(-1, 1).t()
+        for dtype in (torch.bfloat16, torch.float16):
+            for rows in (2, 4, 8, 16):
+                x = torch.randn(rows, K, device=dev).to(dtype)
+                y = torch.empty(rows, M, dtype=dtype, device=dev)
+                a = timed(lambda: check(L.fp4_hip_gemm_small_nf4(p_(x), p_(packed), p_(absmax), None, p_(y), rows, M, K, BS, DT[dtype], s())))
+                b = timed(lambda: pkg.ext.qlinear_nf4(x, packed, absmax, M, K, BS))
+                c = timed(lambda: pkg.ext.gemm_small_fp4(x, B_t, absmax, BS, [M, K], None))
+                d = timed(lambda: [check(L.fp4_hip_gemv_nf4(p_(x[i]), p_(packed), p_(absmax), None, p_(y[i]), M, K, BS, DT[dtype], s()))
+                                   for i in range(rows)])
+                # the torch op on the same call, as QuantData issues it (allocation of the output included)
+                a_op = timed(lambda: pkg.ext.gemm_small_nf4(x, B_t, absmax, BS, [M, K], None))
+                spread = (a["max_us"] - a["min_us"]) + (b["max_us"] - b["min_us"])
+                cells.append({"M": M, "K": K, "dtype": NAME[dtype], "rows": rows, "gemm_small_nf4": a, "gemm_small_nf4_torch_op_us": a_op["us"],
+                              "qlinear_nf4": b, "gemm_small_fp4_us": c["us"], "gemv_nf4_x_rows_us": d["us"],
+                              "speedup_vs_qlinear_nf4": round(b["us"] / a["us"], 2), "nf4_over_fp4": round(a["us"] / c["us"], 3),
+                              "vs_gemv_x_rows": round(a["us"] / d["us"], 3), "spread_us": round(spread, 2),
+                              "beats_qlinear_nf4_beyond_spread": bool(b["us"] - a["us"] > spread)})
+        del packed, absmax
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "blocksize": BS, "launches_per_graph": args.launches, "reps": args.reps,
+                      "all_cells_beat_qlinear_nf4": all(c["beats_qlinear_nf4_beyond_spread"] for c in cells), "cells": cells}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--small-batch", action="store_true", help="the 2..16-row NF4 regime (profiles/nf4_small_batch.json)")
     args = ap.parse_args()
+    if args.small_batch:
+        return small_batch(args)
     L = lib()
     dev = torch.device("cuda", 0)
     s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731

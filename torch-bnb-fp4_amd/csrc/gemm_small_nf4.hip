@@ -1,0 +1,276 @@
+// Small-batch NF4 product for gfx950 (MI355X): 1..16 activation rows against one NF4 weight on the matrix cores,
+//     out[b][r] = T( sum_k x[b][k] * code[nib(r,k)] * absmax[(r*K+k)/64] + bias[r] )
+// The tile scheme is gemm16_mfma_kernel's (gemm_small_fp4.hip; its staging logic is copied here rather than shared, so that the
+// FP4 translation unit stays byte-identical): 8-wave workgroup per 16-row tile of W, the waves split K, row-contiguous 16-byte
+// weight loads staged through a wave-private LDS image, scales re-read from it as broadcasts, loads one pass ahead,
+// v_mfma_f32_16x16x32_{bf16,f16} with one instruction never straddling two scales, partial tiles meeting in LDS.
+//
+// What differs is the decode.  The FP4 kernel builds 12*|code| in 8 bits with v_perm; the 16 NF4 codes are arbitrary f32 values,
+// exact in neither bf16 nor fp16, and T(code) alone misses the project's error bar (|err| <= 1e-5 * sum|x*w| beside the final
+// rounding) by up to 31.6x in bf16 and 4.7x in fp16.  So every weight goes to the matrix cores TWICE:
+//     hi = T(code),  lo = T(code - hi)        |hi + lo - code| <= 5.45e-6 |code| (bf16), 1.05e-7 |code| (fp16)
+// as two instructions against the same activation fragment.  Both halves come from one 256-entry LDS table indexed by the packed
+// BYTE: entry = { hi(high nibble) | hi(low nibble) << 16 , lo(high nibble) | lo(low nibble) << 16 }, so one ds_read_b64 per byte
+// yields one A-fragment dword for each of the two instructions, in natural k order (element 2i is the HIGH nibble of byte i), and
+// the B side uses x as loaded.  The table is computed by the workgroup from the f32 codes with the kernel's own RNE conversions.
+//
+// fp16: most lo values are below fp16's smallest normal (6.1e-5).  Whether v_mfma_f32_16x16x32_f16 flushes subnormal inputs is not
+// documented, so this kernel does not depend on it: the fp16 table holds lo * 2^24 (every non-zero entry normal, none above 4096),
+// the lo instructions run into a tile of their own, and hi_tile + 2^-24 * lo_tile (exact scaling, one FMA per element) is formed
+// before the block's absmax is applied.  bf16 has f32's exponent range: both instructions share one accumulator.
+#include "gemv_common.h"
+
+namespace fp4 {
+
+namespace {
+
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+
+template <int DT>
+__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
+    if constexpr (DT == FP4_DTYPE_F16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+}
+
+// lo is stored times 2^kLoShift: 24 for fp16 (see above), 0 for bf16
+template <int DT>
+constexpr int kLoShift = DT == FP4_DTYPE_F16 ? 24 : 0;
+
+// (hi, lo) of one code in T: hi = RNE_T(code), lo = RNE_T((code - hi) * 2^kLoShift); code - hi is exact in f32
+template <int DT>
+__device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &lo) {
+    const float c = nf4_lut_entry(nibble);
+    hi = from_f32<DT>(c);
+    const float rest = c - to_f32<DT>(uint16_t(hi));
+    lo = from_f32<DT>(rest * float(1 << kLoShift<DT>));
+}
+
+// Workgroup = 8 waves = one 16-row tile of W; wave w owns quant blocks (p*8 + w)*NBW.. of pass p.  Lane (r = l & 15, kb = l >> 4)
+// supplies, per 64-weight block, the 8 packed bytes [8kb, 8kb + 8) of row r: k-sets {16kb + 8t + j}, t = 0, 1, each fed as hi and as
+// lo - four matrix instructions per block and tile.  The B operand is x[n = l & 15][64b + 16kb + 8t + j], from a wave-private LDS
+// image for <= XS rows (XS in {4, 8}), else straight from L2.  Weight image row stride 32*NBW + 32 bytes (the row's NBW scales
+// follow its bytes), x image row stride 128*NBW + 16, as in the FP4 kernel.
+template <int DT, int NBW, int XS>
+__global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
+                                                            const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
+                                                            uint16_t *out, int B, int M, int K) {
+    constexpr int kStageStride = 32 * NBW + 32;
+    constexpr int kXStride = 128 * NBW + 16;
+    constexpr int kWImageBytes = 8 * 16 * kStageStride;
+    constexpr int kXImageBytes = 8 * XS * kXStride;
+    constexpr int kImageBytes = kWImageBytes + kXImageBytes;
+    constexpr int kPartBytes = 8 * 256 * 4;
+    static_assert(XS == 0 || ((XS * NBW) % 8 == 0 && (XS & (XS - 1)) == 0), "x staging: whole 16-byte units per lane");
+    // the cross-wave partial sums reuse the images' storage after the K loop; the code table has storage of its own
+    __shared__ __attribute__((aligned(16))) uint8_t s_raw[kImageBytes > kPartBytes ? kImageBytes : kPartBytes];
+    __shared__ __attribute__((aligned(16))) u32x2 s_code[256];
+    uint8_t *s_w = s_raw;
+    uint8_t *s_x = s_raw + kWImageBytes;
+    float (*s_part)[256] = reinterpret_cast<float (*)[256]>(s_raw);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int r = lane & 15, kb = lane >> 4;
+    const int row0 = blockIdx.x * 16;
+    const int nblk = K >> 6;
+    const int passes = nblk / (8 * NBW);
+    const int64_t n_b = r < B ? r : B - 1;  // clamped rows / batch entries are computed, never stored
+    const u32x4 *x4 = reinterpret_cast<const u32x4 *>(x);
+
+    constexpr int kXUnits = XS ? XS * NBW / 8 : 1;  // 16-byte units of the x image per lane
+    constexpr int kLanesPerRow = 2 * NBW, kRowsPerInstr = 64 / kLanesPerRow, kInstr = (16 + kRowsPerInstr - 1) / kRowsPerInstr;
+    // 16 rows x NBW scales over 64 lanes (with NBW < 4 the upper lanes repeat rows: same address, same value)
+    const int srow = (lane / NBW) & 15, sj0 = lane % NBW;
+    u32x4 xstage[kXUnits];
+    u32x4 wstage[kInstr];
+    float amstage;
+    auto issue_staged = [&](int pass) {  // x first (L2), then the weight stream (HBM), then the scales; all branch-free
+        const int b0 = (pass * 8 + wave) * NBW;
+        if constexpr (XS > 0) {
+#pragma unroll
+            for (int i = 0; i < kXUnits; ++i) {
+                const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
+                const int64_t nn = n < B ? n : B - 1;
+                xstage[i] = x4[((nn * K + 64 * b0) >> 3) + c16];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kInstr; ++i) {
+            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;  // row of the tile this lane fetches
+            const int64_t row = row0 + (rr & 15) < M ? row0 + (rr & 15) : M - 1;
+            wstage[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(W) + ((row * K) >> 5) + 2 * b0 + (lane % kLanesPerRow));
+        }
+        const int64_t row = row0 + srow < M ? row0 + srow : M - 1;
+        amstage = absmax[row * nblk + b0 + sj0];
+    };
+    issue_staged(0);
+
+    // the byte table, once per workgroup, while the first pass's loads fly
+    if (tid < 256) {
+        uint32_t h0, l0, h1, l1;
+        split_code<DT>(tid >> 4, h0, l0);  // element 2i: the HIGH nibble
+        split_code<DT>(tid & 15, h1, l1);
+        s_code[tid] = u32x2{h0 | (h1 << 16), l0 | (l1 << 16)};
+    }
+    __syncthreads();
+    const uint8_t *code = reinterpret_cast<const uint8_t *>(s_code);
+
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int p = 0; p < passes; ++p) {
+        u32x4 xr[XS ? 1 : NBW][2];
+        if constexpr (XS == 0) {
+            const int b0 = (p * 8 + wave) * NBW;
+#pragma unroll
+            for (int j = 0; j < NBW; ++j) {
+                const int64_t e = n_b * K + 64 * (b0 + j) + 16 * kb;
+                xr[j][0] = x4[e >> 3];
+                xr[j][1] = x4[(e >> 3) + 1];
+            }
+        }
+        if (p > 0) __builtin_amdgcn_wave_barrier();  // the previous pass's reads are done before the image is rewritten
+        uint8_t *img = s_w + wave * 16 * kStageStride;
+#pragma unroll
+        for (int i = 0; i < kInstr; ++i) {
+            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
+            if (rr < 16) *reinterpret_cast<u32x4 *>(img + rr * kStageStride + 16 * (lane % kLanesPerRow)) = wstage[i];
+        }
+        reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW)[sj0] = amstage;
+        if constexpr (XS > 0) {
+            uint8_t *ximg = s_x + wave * XS * kXStride;
+#pragma unroll
+            for (int i = 0; i < kXUnits; ++i) {
+                const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
+                *reinterpret_cast<u32x4 *>(ximg + n * kXStride + 16 * c16) = xstage[i];  // natural k order
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (p + 1 < passes) issue_staged(p + 1);  // uniform; flies while this pass is decoded and multiplied
+
+        u32x2 wq[NBW];
+        float am[4][NBW];
+#pragma unroll
+        for (int j = 0; j < NBW; ++j) wq[j] = *reinterpret_cast<const u32x2 *>(img + r * kStageStride + 32 * j + 8 * kb);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const uint8_t *src = img + (kb * 4 + g) * kStageStride + 32 * NBW;
+            if constexpr (NBW % 4 == 0) {
+#pragma unroll
+                for (int j = 0; j < NBW; j += 4) {
+                    const f32x4 v = reinterpret_cast<const f32x4 *>(src)[j >> 2];
+                    am[g][j] = v.x, am[g][j + 1] = v.y, am[g][j + 2] = v.z, am[g][j + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NBW; ++j) am[g][j] = reinterpret_cast<const float *>(src)[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NBW; ++j) {
+            f32x4 tile = {0.0f, 0.0f, 0.0f, 0.0f}, tile_lo = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                u32x4 bfrag;
+                if constexpr (XS > 0)
+                    bfrag = *reinterpret_cast<const u32x4 *>(s_x + wave * XS * kXStride + (r & (XS - 1)) * kXStride + 128 * j + 32 * kb + 16 * t);
+                else
+                    bfrag = xr[j][t];
+                const uint32_t q = t == 0 ? wq[j].x : wq[j].y;
+                // byte d of q -> table entry at 8 * byte: dword d of the hi fragment and of the lo fragment
+                const u32x2 e0 = *reinterpret_cast<const u32x2 *>(code + ((q << 3) & 0x7F8u));
+                const u32x2 e1 = *reinterpret_cast<const u32x2 *>(code + ((q >> 5) & 0x7F8u));
+                const u32x2 e2 = *reinterpret_cast<const u32x2 *>(code + ((q >> 13) & 0x7F8u));
+                const u32x2 e3 = *reinterpret_cast<const u32x2 *>(code + ((q >> 21) & 0x7F8u));
+                const u32x4 a_hi = {e0.x, e1.x, e2.x, e3.x}, a_lo = {e0.y, e1.y, e2.y, e3.y};
+                tile = mfma16<DT>(a_hi, bfrag, tile);
+                if constexpr (kLoShift<DT> == 0)
+                    tile = mfma16<DT>(a_lo, bfrag, tile);
+                else
+                    tile_lo = mfma16<DT>(a_lo, bfrag, tile_lo);
+            }
+            if constexpr (kLoShift<DT> != 0) {
+                constexpr float kUnscale = 1.0f / float(1 << kLoShift<DT>);
+                tile.x = __builtin_fmaf(tile_lo.x, kUnscale, tile.x);
+                tile.y = __builtin_fmaf(tile_lo.y, kUnscale, tile.y);
+                tile.z = __builtin_fmaf(tile_lo.z, kUnscale, tile.z);
+                tile.w = __builtin_fmaf(tile_lo.w, kUnscale, tile.w);
+            }
+            acc.x = __builtin_fmaf(tile.x, am[0][j], acc.x);
+            acc.y = __builtin_fmaf(tile.y, am[1][j], acc.y);
+            acc.z = __builtin_fmaf(tile.z, am[2][j], acc.z);
+            acc.w = __builtin_fmaf(tile.w, am[3][j], acc.w);
+        }
+    }
+    __syncthreads();  // every wave is done with its image before the partials overwrite the storage
+    *reinterpret_cast<f32x4 *>(&s_part[wave][lane * 4]) = acc;
+    __syncthreads();
+    if (tid < 256) {
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) t += s_part[w][tid];
+        const int l = tid >> 2, reg = tid & 3;  // D layout: col = l & 15 (activation row), row = (l >> 4) * 4 + reg (weight row)
+        const int n = l & 15, row = row0 + (l >> 4) * 4 + reg;
+        if (row < M && n < B) store_small<DT>(out, bias, nullptr, n, row, M, t);
+    }
+}
+
+template <int DT, int NBW, int XS>
+void launch_nf4_mfma(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
+                     hipStream_t stream) {
+    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS>), dim3((unsigned)((M + 15) / 16)), dim3(512), 0, stream,
+                       reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
+                       reinterpret_cast<uint16_t *>(out), B, M, K);
+}
+
+template <int DT>
+void dispatch_nf4_mfma(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
+                       hipStream_t stream) {
+    const int units = K / 512;  // quant blocks per wave over the whole K
+    const int blocks = (M + 15) / 16;
+    // the FP4 kernel's rules: at most 4 blocks per wave and pass; x staged per wave in LDS always for <= 4 rows, for 5..8 rows only
+    // while the grid is a single round anyway (the larger image leaves fewer workgroups per CU)
+    if (units % 4 == 0) {
+        if (B <= 4) return launch_nf4_mfma<DT, 4, 4>(x, W, absmax, bias, out, B, M, K, stream);
+        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8>(x, W, absmax, bias, out, B, M, K, stream);
+        return launch_nf4_mfma<DT, 4, 0>(x, W, absmax, bias, out, B, M, K, stream);
+    }
+    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0>(x, W, absmax, bias, out, B, M, K, stream);
+    return launch_nf4_mfma<DT, 1, 0>(x, W, absmax, bias, out, B, M, K, stream);
+}
+
+}  // namespace
+}  // namespace fp4
+
+extern "C" int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
+                                      int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
+    using namespace fp4;
+    if (B < 0 || M < 0 || K <= 0 || blocksize <= 0) {
+        set_error("fp4_hip_gemm_small_nf4: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", (long long)B,
+                  (long long)M, (long long)K, blocksize);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
+    // the kernel addresses with 64-bit element offsets: M * K may pass 2^32; the bounds keep the int row / block arithmetic in range
+    if (B > 16 || blocksize != 64 || (K % 512) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) || (align & 15u) != 0 ||
+        M > (int64_t(1) << 30) || K > (int64_t(1) << 24)) {
+        set_error("fp4_hip_gemm_small_nf4: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..16 rows, blocksize 64, "
+                  "K %% 512 == 0, fp16 / bf16, 16-byte aligned x and packed); use dequant + GEMM",
+                  (long long)B, (long long)M, (long long)K, blocksize, dtype);
+        return FP4_ERR_UNSUPPORTED;
+    }
+    if (M == 0 || B == 0) return FP4_OK;
+    if (!x || !packed || !absmax || !out) {
+        set_error("fp4_hip_gemm_small_nf4: null pointer");
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dtype == FP4_DTYPE_F16)
+        dispatch_nf4_mfma<FP4_DTYPE_F16>(x, packed, absmax, bias, out, (int)B, (int)M, (int)K, s);
+    else
+        dispatch_nf4_mfma<FP4_DTYPE_BF16>(x, packed, absmax, bias, out, (int)B, (int)M, (int)K, s);
+    return check_launch("fp4_hip_gemm_small_nf4");
+}

@@ -15,7 +15,10 @@ everything else (batch or seq > 1)    ``qlinear`` = dequant + F.linear   (:616-6
 
 NF4 weights (``quant_state.quant_type == "nf4"``) take the same table with the NF4 ops: the GEMV row runs ``gemv_nf4``, every
 other row ``qlinear_nf4`` whatever ``use_codebook_dequant`` says (NF4 has one table), and ``small_batch_fused`` is ignored (the
-small-batch kernels decode FP4 only).  Any other ``quant_type`` is refused.
+FP4 small-batch kernels decode FP4 only).  NF4 has a switch of its own, ``small_batch_fused_nf4`` (OFF by default): 2..16 rows of
+fp16 / bf16 activations against a blocksize-64 weight with K % 512 == 0 go to ``gemm_small_nf4`` (the matrix-core kernel of
+csrc/gemm_small_nf4.hip) instead of dequant + GEMM; every other input goes where it goes without the switch, and an FP4 weight
+ignores it.  Any other ``quant_type`` is refused.
 
 Two extensions.  ``fuse_bias`` (ON by default) folds the post-GEMV ``out += bias`` into the kernel epilogue: the table above
 still holds and the result is bit-identical (``T(T(sum) + bias)``), there is just one launch fewer; ``fuse_bias=False`` runs the
@@ -39,7 +42,7 @@ class QuantData:
     def __init__(self, A: torch.Tensor, state, shape: Tuple[int, int], original_lin=None,
                  bias: Optional[torch.Tensor] = None, use_codebook_dequant: Optional[bool] = True,
                  allow_reduced_precision_linear: Optional[bool] = False, fuse_bias: bool = True,
-                 small_batch_fused: bool = False):
+                 small_batch_fused: bool = False, small_batch_fused_nf4: bool = False):
         self.use_codebook_dequant = use_codebook_dequant
         self.quant_type = check_quant_type(getattr(state, "quant_type", "fp4"))
         self.nf4 = self.quant_type == "nf4"
@@ -61,6 +64,8 @@ class QuantData:
         # opt-in: 2..128 activation rows go to the fused small-batch kernels instead of dequant + GEMM (the reference
         # always dequantises for batch > 1, :616-617; same result up to rounding, ~5x less HBM traffic)
         self.small_batch_fused = small_batch_fused
+        # opt-in, NF4 weights only: 2..16 rows go to the fused NF4 matrix-core kernel (4096 x 4096 bf16: see profiles/nf4_small_batch.json)
+        self.small_batch_fused_nf4 = small_batch_fused_nf4
         # per-call constants of the decode path, built once (224 calls per token in a 7B model)
         self._B_t = A.t()
         self._shape_list = [int(shape[0]), int(shape[1])]
@@ -176,4 +181,7 @@ class QuantData:
                  and ((self.blocksize == 64 and K % 64 == 0) or (rows <= 8 and K % self.blocksize == 0 and K % 32 == 0 and K <= 4096)))
                 or (A.dtype == torch.float32 and rows <= 8 and K % self.blocksize == 0)):  # f32: one f32 GEMV per row, up to 8 rows
             return ext.gemm_small_fp4(A.contiguous(), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
+        if self.small_batch_fused_nf4 and self.nf4 and 2 <= rows <= 16 and self.blocksize == 64 and K % 512 == 0 and (
+                A.dtype in (torch.float16, torch.bfloat16)):
+            return ext.gemm_small_nf4(A.contiguous(), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
         return self.qlinear(A)

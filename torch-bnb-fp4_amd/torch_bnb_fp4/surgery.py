@@ -136,17 +136,24 @@ def recursively_replace_with_fp4_linear(
         return module
 
 
-def set_small_batch_fused(module: nn.Module, enabled: bool = True) -> int:
+def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = False) -> int:
     """Route 2..128 activation rows of every :class:`TorchFP4Linear` below ``module`` to the fused small-batch kernels
     (``enabled=True``) or back to the reference's dispatch, dequant + GEMM for every batch > 1
     (torch_bnb_fp4/__init__.py:592,616-617; the default, so that a converted model behaves like the reference's).
     Not part of the reference surface.  Returns the number of layers touched.  Batched decode through Mistral-7B shapes:
     3 237 tok/s fused vs 963 tok/s through the reference dispatch at 8 sequences (profiles/).  NF4 layers are left on
-    dequant + GEMM (the small-batch kernels decode FP4 only) and not counted."""
+    dequant + GEMM (the FP4 small-batch kernels decode FP4 only) and not counted, unless ``nf4=True``: then every NF4 layer's
+    ``small_batch_fused_nf4`` is set as well - 2..16 rows of fp16 / bf16 activations go to the fused NF4 matrix-core kernel
+    (blocksize 64, K % 512 == 0; anything else stays on dequant + GEMM) - and those layers are counted too."""
     n = 0
     for m in module.modules():
-        if isinstance(m, TorchFP4Linear) and not m.quant_data.nf4:
+        if not isinstance(m, TorchFP4Linear):
+            continue
+        if not m.quant_data.nf4:
             m.quant_data.small_batch_fused = bool(enabled)
+            n += 1
+        elif nf4:
+            m.quant_data.small_batch_fused_nf4 = bool(enabled)
             n += 1
     return n
 
