@@ -252,8 +252,22 @@ FP4_HIP_API int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, con
                                        int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream);
 
 /*
+ * fp4_hip_gemm_wide_nf4: the same product for 1..128 activation rows, one pass over the packed weight per at most 64 rows
+ * (csrc/gemm_wide_nf4.hip): x is the A operand and the weight the B operand of v_mfma_f32_16x16x32, the hi / lo byte table of
+ * fp4_hip_gemm_small_nf4 decodes, and every decoded fragment is multiplied with all ceil(B / 16) <= 4 column tiles of x.
+ * f32 accumulation, bias added in f32, ONE rounding.  An addition to ABI version 7.
+ * Covered: 1 <= B <= 128, blocksize 64, K % 64 == 0 (K <= 2^24), fp16 / bf16, any M >= 1 up to 2^30 (M * K may pass 2^32),
+ * x and packed 16-byte aligned.  17..64 rows: one launch; 65..128 rows: two even chunks of at most 64 (two launches);
+ * 1..16 rows: fp4_hip_gemm_small_nf4 itself where K % 512 == 0 (bit-identical), else the one-tile form of this kernel.
+ * Deterministic (fixed summation order, no atomics), no allocation, no synchronisation: capturable.  Everything else:
+ * FP4_ERR_UNSUPPORTED, nothing launched, out untouched.  FP4_OK without a launch for M == 0 or B == 0.  No fused epilogues.
+ */
+FP4_HIP_API int fp4_hip_gemm_wide_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
+                                      int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream);
+
+/*
  * Tuning hook for benchmarks/sweeps: selects a kernel geometry by name
- * ("dequant", "gemv", "gemv_nf4" (0 = 16-entry f32 table, 1 = 256-entry pair table), "gemm_small", "gemm_wide" = rows per workgroup of the 17..64-row kernels (1 / 2 / 3 / 4 = 16 / 32 / 64 / 128, 5 = 16 with self-contained waves; 0 = off),
+ * ("dequant", "gemv", "gemv_nf4" (0 = 16-entry f32 table, 1 = 256-entry pair table), "gemm_wide_nf4" (1 / 2 = 16 / 32 weight rows per workgroup), "gemm_small", "gemm_wide" = rows per workgroup of the 17..64-row kernels (1 / 2 / 3 / 4 = 16 / 32 / 64 / 128, 5 = 16 with self-contained waves; 0 = off),
  * "quantize": 1..999 = the persistent kernel with that many workgroups per CU, 1001 / 1002 / 1004 = the one-shot tiles kernel with 1 / 2 / 4 loads per lane).  variant < 0 (quantize: 0) restores the built-in heuristic.
  * Process-wide (relaxed atomics: safe to flip while other threads launch, each launch
  * reads it once); for sweeps and tests only, not part of the reference surface.

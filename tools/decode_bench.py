@@ -41,7 +41,7 @@ def fp4_bytes(m, k):
 
 
 def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epilogues=False, batch=1,
-                   reference_dispatch=False, allreduce="dist", lm_head=True, seed=7, lean_glue=False, tensor_parallel=None):
+                   reference_dispatch=False, allreduce="dist", lm_head=True, seed=7, lean_glue=False, tensor_parallel=None, nf4=False):
     """Builds the FP4 layers of a `cfg`-shaped decoder and returns (token_fn, h0, meta).
 
     world == 1: QuantData dispatchers (the product's single-GPU path).  world > 1: Column/RowParallelFP4Linear
@@ -61,12 +61,14 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
         absmax = (torch.rand(m * k // BS, device=dev, generator=gen) * 0.02 + 0.002) * (0.25 if lean_glue else 1.0)
         return packed, absmax
 
-    code = pkg.ext.code_table("tree").to(dev)
+    code = pkg.ext.code_table("nf4" if nf4 else "tree").to(dev)
 
     def qd_of(packed, absmax, m, k):
-        state = pkg.QuantState(absmax, (m, k), code, BS)
+        # nf4 (single GPU, unfused layers only): the same random bytes read as NF4 codes, both NF4 switches on unless reference_dispatch
+        state = pkg.QuantState(absmax, (m, k), code, BS, quant_type="nf4" if nf4 else "fp4")
         return pkg.QuantData(packed, state, state.shape, original_lin=None, bias=None,
-                             small_batch_fused=not reference_dispatch)
+                             small_batch_fused=not reference_dispatch, small_batch_fused_nf4=nf4 and not reference_dispatch,
+                             wide_batch_fused_nf4=nf4 and not reference_dispatch)
 
     def linear(m, k, kind):
         if isinstance(m, (list, tuple)):  # fused rows
@@ -216,6 +218,7 @@ def main():
                     help="batch > 1 through dequant + GEMM like the reference, instead of the fused small-batch kernels")
     ap.add_argument("--allreduce", default="dist", choices=("dist", "oneshot"),
                     help="world > 1: torch.distributed all-reduce (RCCL) or the one-shot peer-slot kernel")
+    ap.add_argument("--nf4", action="store_true", help="NF4 weights instead of FP4 (single GPU, without --fuse / --epilogues)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--lean-glue", action="store_true",
                     help="attention stand-in as ONE elementwise launch and no rescale: what is left besides the FP4 Linears is minimal")
@@ -240,7 +243,7 @@ def main():
             dist.init_process_group(backend)
     dtype = getattr(torch, args.dtype)
     token, h0, meta = build_token_fn(cfg, dev, dtype, world, rank, fuse=args.fuse, epilogues=args.epilogues, batch=args.batch,
-                                     reference_dispatch=args.reference_dispatch, allreduce=args.allreduce, lean_glue=args.lean_glue)
+                                     reference_dispatch=args.reference_dispatch, allreduce=args.allreduce, lean_glue=args.lean_glue, nf4=args.nf4)
 
     def barrier():
         torch.cuda.synchronize()

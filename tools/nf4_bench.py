@@ -11,6 +11,13 @@ divided by R.  usage: python tools/nf4_bench.py [--reps 20] [--launches 20]
 hipBLASLt - what these calls cost without the switch; (c) gemm_small_fp4 on the same bytes (the price of the NF4 decode and of the
 doubled matrix work); (d) gemv_nf4 once per row.  (a) and (b) also carry min / max / p10 / p90 over the replays, and each cell says
 whether (a) beats (b) by more than the two full ranges (max - min) together.
+
+--wide-batch: the 17..128-row regime (profiles/nf4_wide_batch.json).  Per dtype, shape (the four decoder shapes and 4096 x 11008)
+and row count (17 / 32 / 48 / 64 / 96 / 128; K = 11008 also 2 / 8 / 16), in one run on the same operands: (a) gemm_wide_nf4, the
+one-pass kernel, under its own heuristic and with 16 / 32 weight rows per workgroup forced (fp4_hip_set_variant("gemm_wide_nf4",
+1 / 2)); (b) qlinear_nf4; (c) ceil(rows / 16) launches of gemm_small_nf4 (K % 512 == 0 only); (d) gemm_small_fp4 on the same
+bytes, for orientation.  (a), (b), (c) carry min / max over the replays; a cell is won where (a) beats (b) AND (c), each by more than
+the two full ranges together.  --revision names the tree the figures belong to.
 """
 import argparse
 import ctypes
@@ -96,14 +103,88 @@ def small_batch(args):
                       "all_cells_beat_qlinear_nf4": all(c["beats_qlinear_nf4_beyond_spread"] for c in cells), "cells": cells}))
 
 
+WIDE_SHAPES = SHAPES + [(4096, 11008)]
+
+
+def wide_batch(args):
+    L = lib()
+    sig = [ctypes.c_void_p] * 5 + [ctypes.c_int64] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+    L.fp4_hip_gemm_small_nf4.argtypes = sig
+    L.fp4_hip_gemm_wide_nf4.argtypes = sig
+    dev = torch.device("cuda", 0)
+    s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def check(rc):
+        if rc:
+            raise RuntimeError(L.fp4_hip_last_error().decode())
+
+    def timed(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        med, samples = time_replays(replay, args.reps, args.launches)
+        q = sorted(samples)
+        return {"us": round(med, 2), "min_us": round(q[0], 2), "max_us": round(q[-1], 2)}
+
+    def beyond(new, base):  # new beats base by more than the two replay-to-replay ranges together
+        spread = (new["max_us"] - new["min_us"]) + (base["max_us"] - base["min_us"])
+        return bool(base["us"] - new["us"] > spread)
+
+    cells = []
+    for M, K in WIDE_SHAPES:
+        n = M * K
+        torch.manual_seed(0)
+        w16 = (torch.randn(n, device=dev) * 0.02).to(torch.float16)
+        packed = torch.empty(n // 2, dtype=torch.uint8, device=dev)
+        absmax = torch.empty(n // BS, dtype=torch.float32, device=dev)
+        check(L.fp4_hip_quantize_blockwise_nf4(p_(w16), DT[torch.float16], p_(packed), p_(absmax), n, BS, s()))
+        del w16
+        B_t = packed.view(-1, 1).t()
+        for dtype in (torch.bfloat16, torch.float16):
+            for rows in ([2, 8, 16] if K % 512 else []) + [17, 32, 48, 64, 96, 128]:
+                x = torch.randn(rows, K, device=dev).to(dtype)
+                y = torch.empty(rows, M, dtype=dtype, device=dev)
+                wide = lambda: check(L.fp4_hip_gemm_wide_nf4(p_(x), p_(packed), p_(absmax), None, p_(y), rows, M, K, BS, DT[dtype], s()))  # noqa: E731
+                a = timed(wide)
+                forced = {}
+                for v in (1, 2):
+                    L.fp4_hip_set_variant(b"gemm_wide_nf4", v)
+                    forced[v] = timed(wide)["us"]
+                L.fp4_hip_set_variant(b"gemm_wide_nf4", -1)
+                b = timed(lambda: pkg.ext.qlinear_nf4(x, packed, absmax, M, K, BS))
+                cell = {"M": M, "K": K, "dtype": NAME[dtype], "rows": rows, "gemm_wide_nf4": a, "rows16_per_workgroup_us": forced[1],
+                        "rows32_per_workgroup_us": forced[2], "qlinear_nf4": b, "speedup_vs_qlinear_nf4": round(b["us"] / a["us"], 2)}
+                won = beyond(a, b)
+                if K % 512 == 0:
+                    c = timed(lambda: [check(L.fp4_hip_gemm_small_nf4(p_(x[i:i + 16]), p_(packed), p_(absmax), None, p_(y[i:i + 16]),
+                                                                      min(16, rows - i), M, K, BS, DT[dtype], s()))
+                                       for i in range(0, rows, 16)])
+                    cell["gemm_small_nf4_chunks_of_16"] = c
+                    cell["speedup_vs_chunks_of_16"] = round(c["us"] / a["us"], 2)
+                    won = won and beyond(a, c)
+                d = timed(lambda: pkg.ext.gemm_small_fp4(x, B_t, absmax, BS, [M, K], None))
+                cell["gemm_small_fp4_us"] = d["us"]
+                cell["nf4_over_fp4"] = round(a["us"] / d["us"], 3)
+                cell["gemm_wide_nf4_torch_op_us"] = timed(lambda: pkg.ext.gemm_wide_nf4(x, B_t, absmax, BS, [M, K], None))["us"]
+                cell["beats_every_baseline_beyond_spread"] = won
+                cells.append(cell)
+        del packed, absmax
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "revision": args.revision, "blocksize": BS, "launches_per_graph": args.launches,
+                      "reps": args.reps, "cells_won": sum(c["beats_every_baseline_beyond_spread"] for c in cells), "cells_total": len(cells),
+                      "cells": cells}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--small-batch", action="store_true", help="the 2..16-row NF4 regime (profiles/nf4_small_batch.json)")
+    ap.add_argument("--wide-batch", action="store_true", help="the 17..128-row NF4 regime (profiles/nf4_wide_batch.json)")
+    ap.add_argument("--revision", default="unknown", help="--wide-batch: the git revision the figures belong to, recorded as given")
     args = ap.parse_args()
     if args.small_batch:
         return small_batch(args)
+    if args.wide_batch:
+        return wide_batch(args)
     L = lib()
     dev = torch.device("cuda", 0)
     s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731

@@ -12,6 +12,7 @@ CSRC = os.path.join("torch-bnb-fp4_amd", "csrc")
 COMMON = [os.path.join(CSRC, "fp4_common.h"), os.path.join("torch-bnb-fp4_amd", "build.py")]  # code tables / conversions; compiler flags
 # kernel-name prefix (as it appears in profiles/rNN_traffic.json) -> the files its code object is compiled from
 KERNEL_SOURCES = {
+    "gemm_wide_nf4": [os.path.join(CSRC, "gemm_wide_nf4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
     "gemm_nf4": [os.path.join(CSRC, "gemm_small_nf4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
     "gemv_nf4": [os.path.join(CSRC, "gemv_nf4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
     "quantize_nf4": [os.path.join(CSRC, "quantize_nf4.hip")] + COMMON,

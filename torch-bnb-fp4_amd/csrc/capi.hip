@@ -18,6 +18,7 @@ void set_small_variant(int v);
 void set_wide_variant(int v);
 void set_quantize_variant(int v);
 void set_gemv_nf4_variant(int v);
+void set_wide_nf4_variant(int v);
 
 void set_error(const char *fmt, ...) {
     va_list ap;
@@ -75,6 +76,10 @@ extern "C" int fp4_hip_set_variant(const char *kernel, int variant) {
     }
     if (kernel && !std::strcmp(kernel, "gemv_nf4")) {
         fp4::set_gemv_nf4_variant(variant);
+        return FP4_OK;
+    }
+    if (kernel && !std::strcmp(kernel, "gemm_wide_nf4")) {
+        fp4::set_wide_nf4_variant(variant);
         return FP4_OK;
     }
     if (kernel && !std::strcmp(kernel, "quantize")) {

@@ -1,0 +1,325 @@
+// Wide-batch NF4 product for gfx950 (MI355X): up to 128 activation rows against one NF4 weight on the matrix cores, one pass over
+// the packed weight per at most 64 rows,
+//     out[b][r] = T( sum_k x[b][k] * code[nib(r,k)] * absmax[(r*K+k)/64] + bias[r] )
+// f32 accumulation, bias added in f32, one rounding to T.
+//
+// Operand roles are gemm_wide_fp4.hip's: x is the A operand, the weight the B operand of v_mfma_f32_16x16x32_{bf16,f16}, so a
+// lane's four accumulators of a tile belong to ONE weight row (D column = lane & 15) and four activation rows, and the block's
+// absmax is one scalar per lane and 64-weight block.  No instruction straddles two scales.
+//
+// The decode is gemm_small_nf4.hip's (copied, that file stays as it is): every weight goes to the matrix cores twice,
+//     hi = T(code),  lo = T(code - hi),
+// both halves from one 256-entry LDS table indexed by the packed BYTE (one ds_read_b64 per byte = one fragment dword of each half,
+// natural k order: element 2i is the HIGH nibble of byte i).  A decoded fragment pair is used for all NT column tiles of x:
+// 8 table reads per lane, weight row and block feed 4 * NT matrix instructions (the 2..16-row kernel: 8 reads for 4).
+// fp16 keeps that kernel's rule that no subnormal matrix input is relied on: the table holds lo * 2^24, the lo products run into a
+// tile of their own, and hi_tile + 2^-24 * lo_tile is formed exactly (one FMA per element) before the block's scale is applied.
+//
+// Work split: a workgroup of 8 waves owns RT 16-row tiles of W (RT in {1, 2}, chosen by M) and all NT <= 4 column tiles; the waves
+// split K in units of NBW blocks (unit u = pass * 8 + wave; NBW = 4 where K % 256 == 0, else 1; a ragged last pass leaves the
+// upper waves idle).  The weight unit and its scales are fetched one pass ahead with row-contiguous 16-byte loads and staged
+// through a wave-private LDS image; x fragments come straight from L2, one block ahead, and are shared by the RT row tiles.  The
+// row tiles are looped INSIDE a block so that only tile[NT] (fp16: two of them) is live beside acc[RT][NT].  The eight waves'
+// partial tiles meet in LDS and are added in a fixed order: deterministic, no atomics, no workspace.
+#include "gemv_common.h"
+
+#include <atomic>
+
+namespace fp4 {
+
+namespace {
+
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+
+template <int DT>
+__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
+    if constexpr (DT == FP4_DTYPE_F16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+}
+
+// lo is stored times 2^kLoShift: 24 for fp16 (see above), 0 for bf16
+template <int DT>
+constexpr int kLoShift = DT == FP4_DTYPE_F16 ? 24 : 0;
+
+// (hi, lo) of one code in T: hi = RNE_T(code), lo = RNE_T((code - hi) * 2^kLoShift); code - hi is exact in f32
+template <int DT>
+__device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &lo) {
+    const float c = nf4_lut_entry(nibble);
+    hi = from_f32<DT>(c);
+    const float rest = c - to_f32<DT>(uint16_t(hi));
+    lo = from_f32<DT>(rest * float(1 << kLoShift<DT>));
+}
+
+// Lane (r = l & 15, kb = l >> 4).  Instruction t = 0, 1 of a block takes k = 32t .. 32t + 31 in natural order: the B operand is the
+// packed dword [16t + 4kb, 16t + 4kb + 4) of weight row r (k = 32t + 8kb + j), the A operand x[16nt + r][64b + 32t + 8kb + j], so
+// one x load instruction reads 64 contiguous bytes per activation row.  D: lane holds out[16nt + 4kb + reg][row0 + 16rt + r].
+// Weight image (per wave): 16 * RT rows of stride 32 * NBW + 32 bytes, the row's NBW scales behind its bytes.
+template <int DT, int NT, int RT, int NBW>
+__global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
+                                                            const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
+                                                            uint16_t *out, int B, int M, int K) {
+    constexpr int kRows = 16 * RT;
+    constexpr int kStageStride = 32 * NBW + 32;
+    constexpr int kImageBytes = 8 * kRows * kStageStride;
+    constexpr int kTiles = RT * NT;
+    constexpr int kPartBytes = 4 * kTiles * 256 * 4;  // four slots: see the reduction below
+    // the cross-wave partial sums reuse the images' storage after the K loop; the code table has storage of its own
+    __shared__ __attribute__((aligned(16))) uint8_t s_raw[kImageBytes > kPartBytes ? kImageBytes : kPartBytes];
+    __shared__ __attribute__((aligned(16))) u32x2 s_code[256];
+    float (*s_part)[kTiles * 256] = reinterpret_cast<float (*)[kTiles * 256]>(s_raw);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int r = lane & 15, kb = lane >> 4;
+    const int64_t row0 = int64_t(blockIdx.x) * kRows;
+    const int nblk = K >> 6;
+    const int nunits = nblk / NBW;
+    const int passes = (nunits + 7) >> 3;
+    const u32x4 *x4 = reinterpret_cast<const u32x4 *>(x);
+
+    constexpr int kLanesPerRow = 2 * NBW, kRowsPerInstr = 64 / kLanesPerRow, kInstr = (kRows + kRowsPerInstr - 1) / kRowsPerInstr;
+    constexpr int kScaleInstr = (kRows * NBW + 63) / 64;  // with fewer than 64 scales the upper lanes repeat rows: same address, same value
+    u32x4 wstage[kInstr];
+    float amstage[kScaleInstr];
+    auto issue_staged = [&](int pass) {  // the weight stream (HBM), then the scales; branch-free, a unit past the end is clamped
+        const int u = pass * 8 + wave;
+        const int b0 = (u < nunits ? u : nunits - 1) * NBW;
+#pragma unroll
+        for (int i = 0; i < kInstr; ++i) {
+            const int rr = (i * kRowsPerInstr + lane / kLanesPerRow) % kRows;  // row of the workgroup's tiles this lane fetches
+            const int64_t row = row0 + rr < M ? row0 + rr : int64_t(M) - 1;
+            wstage[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(W) + ((row * K) >> 5) + 2 * b0 + (lane % kLanesPerRow));
+        }
+#pragma unroll
+        for (int i = 0; i < kScaleInstr; ++i) {
+            const int idx = i * 64 + lane, rr = (idx / NBW) % kRows;
+            const int64_t row = row0 + rr < M ? row0 + rr : int64_t(M) - 1;
+            amstage[i] = absmax[row * nblk + b0 + idx % NBW];
+        }
+    };
+    // the x fragments of one block: rows past B are clamped (computed, never stored)
+    int64_t xrow[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int n = 16 * nt + r;
+        xrow[nt] = int64_t(n < B ? n : B - 1) * K + 8 * kb;
+    }
+    auto load_x = [&](u32x4 (&xr)[NT][2], int blk) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int64_t e = (xrow[nt] + 64 * int64_t(blk)) >> 3;
+            xr[nt][0] = x4[e];
+            xr[nt][1] = x4[e + 4];
+        }
+    };
+    issue_staged(0);
+
+    // the byte table, once per workgroup, while the first pass's loads fly
+    if (tid < 256) {
+        uint32_t h0, l0, h1, l1;
+        split_code<DT>(tid >> 4, h0, l0);  // element 2i: the HIGH nibble
+        split_code<DT>(tid & 15, h1, l1);
+        s_code[tid] = u32x2{h0 | (h1 << 16), l0 | (l1 << 16)};
+    }
+    __syncthreads();
+    const uint8_t *code = reinterpret_cast<const uint8_t *>(s_code);
+    uint8_t *img = s_raw + wave * kRows * kStageStride;
+
+    f32x4 acc[RT][NT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[rt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    for (int p = 0; p < passes; ++p) {
+        const int u = p * 8 + wave;
+        const bool active = u < nunits;  // wave-uniform
+        const int b0 = (active ? u : nunits - 1) * NBW;
+        u32x4 xcur[NT][2];
+        load_x(xcur, b0);
+        if (p > 0) __builtin_amdgcn_wave_barrier();  // the previous pass's reads are done before the image is rewritten
+#pragma unroll
+        for (int i = 0; i < kInstr; ++i) {
+            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
+            if (rr < kRows) *reinterpret_cast<u32x4 *>(img + rr * kStageStride + 16 * (lane % kLanesPerRow)) = wstage[i];
+        }
+#pragma unroll
+        for (int i = 0; i < kScaleInstr; ++i) {
+            const int idx = i * 64 + lane, rr = (idx / NBW) % kRows;
+            reinterpret_cast<float *>(img + rr * kStageStride + 32 * NBW)[idx % NBW] = amstage[i];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (p + 1 < passes) issue_staged(p + 1);  // uniform; flies while this pass is decoded and multiplied
+        if (!active) continue;
+
+#pragma unroll 1
+        for (int j = 0; j < NBW; ++j) {
+            u32x4 xnext[NT][2];
+            if (j + 1 < NBW) load_x(xnext, b0 + j + 1);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                const uint8_t *wrow = img + (16 * rt + r) * kStageStride;
+                const uint32_t wq[2] = {*reinterpret_cast<const uint32_t *>(wrow + 32 * j + 4 * kb),
+                                        *reinterpret_cast<const uint32_t *>(wrow + 32 * j + 16 + 4 * kb)};
+                const float am = reinterpret_cast<const float *>(wrow + 32 * NBW)[j];
+                f32x4 tile[NT], tile_lo[NT];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) tile[nt] = tile_lo[nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const uint32_t q = wq[t];
+                    // byte d of q -> table entry at 8 * byte: dword d of the hi fragment and of the lo fragment
+                    const u32x2 e0 = *reinterpret_cast<const u32x2 *>(code + ((q << 3) & 0x7F8u));
+                    const u32x2 e1 = *reinterpret_cast<const u32x2 *>(code + ((q >> 5) & 0x7F8u));
+                    const u32x2 e2 = *reinterpret_cast<const u32x2 *>(code + ((q >> 13) & 0x7F8u));
+                    const u32x2 e3 = *reinterpret_cast<const u32x2 *>(code + ((q >> 21) & 0x7F8u));
+                    const u32x4 b_hi = {e0.x, e1.x, e2.x, e3.x}, b_lo = {e0.y, e1.y, e2.y, e3.y};
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) {
+                        tile[nt] = mfma16<DT>(xcur[nt][t], b_hi, tile[nt]);
+                        if constexpr (kLoShift<DT> == 0)
+                            tile[nt] = mfma16<DT>(xcur[nt][t], b_lo, tile[nt]);
+                        else
+                            tile_lo[nt] = mfma16<DT>(xcur[nt][t], b_lo, tile_lo[nt]);
+                    }
+                }
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    f32x4 v = tile[nt];
+                    if constexpr (kLoShift<DT> != 0) {
+                        constexpr float kUnscale = 1.0f / float(1 << kLoShift<DT>);
+                        v.x = __builtin_fmaf(tile_lo[nt].x, kUnscale, v.x);
+                        v.y = __builtin_fmaf(tile_lo[nt].y, kUnscale, v.y);
+                        v.z = __builtin_fmaf(tile_lo[nt].z, kUnscale, v.z);
+                        v.w = __builtin_fmaf(tile_lo[nt].w, kUnscale, v.w);
+                    }
+                    acc[rt][nt].x = __builtin_fmaf(v.x, am, acc[rt][nt].x);
+                    acc[rt][nt].y = __builtin_fmaf(v.y, am, acc[rt][nt].y);
+                    acc[rt][nt].z = __builtin_fmaf(v.z, am, acc[rt][nt].z);
+                    acc[rt][nt].w = __builtin_fmaf(v.w, am, acc[rt][nt].w);
+                }
+            }
+            if (j + 1 < NBW) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) xcur[nt][0] = xnext[nt][0], xcur[nt][1] = xnext[nt][1];
+            }
+        }
+    }
+    // waves 4..7 park their tiles, waves 0..3 add their own on top (slot w: wave w + wave w + 4), then four slots are summed in order
+    __syncthreads();  // every wave is done with its image before the partials overwrite the storage
+    if (wave >= 4) {
+#pragma unroll
+        for (int i = 0; i < kTiles; ++i) *reinterpret_cast<f32x4 *>(&s_part[wave - 4][i * 256 + lane * 4]) = acc[i / NT][i % NT];
+    }
+    __syncthreads();
+    if (wave < 4) {
+#pragma unroll
+        for (int i = 0; i < kTiles; ++i) {
+            f32x4 *slot = reinterpret_cast<f32x4 *>(&s_part[wave][i * 256 + lane * 4]);
+            const f32x4 o = *slot, a = acc[i / NT][i % NT];
+            *slot = f32x4{a.x + o.x, a.y + o.y, a.z + o.z, a.w + o.w};
+        }
+    }
+    __syncthreads();
+    // thread -> (tile, activation row of the tile, weight row of the tile), consecutive threads on consecutive weight rows
+    for (int idx = tid; idx < kTiles * 256; idx += 512) {
+        const int tile = idx >> 8, e = idx & 255;
+        const int wr = e & 15, n_l = e >> 4;
+        const int src = tile * 256 + (((n_l >> 2) * 16 + wr) << 2) + (n_l & 3);  // lane (n_l >> 2) * 16 + wr, register n_l & 3
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) t += s_part[w][src];
+        const int n = 16 * (tile % NT) + n_l;
+        const int64_t row = row0 + 16 * (tile / NT) + wr;
+        if (row < M && n < B) store_small<DT>(out, bias, nullptr, n, (int)row, M, t);
+    }
+}
+
+std::atomic<int> g_wide_nf4_variant{-1};  // sweep hook: 1 / 2 = 16 / 32 weight rows per workgroup, anything else = the heuristic
+
+template <int DT, int NT, int RT, int NBW>
+void launch_wide_nf4(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
+                     hipStream_t stream) {
+    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW>), dim3((unsigned)((M + 16 * RT - 1) / (16 * RT))), dim3(512), 0, stream,
+                       reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
+                       reinterpret_cast<uint16_t *>(out), B, M, K);
+}
+
+template <int DT, int NT>
+void dispatch_wide_nf4_nt(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
+                          hipStream_t stream) {
+    // 32 weight rows per workgroup halve the x traffic from L2, the kernel's largest stream: taken once that still fills three
+    // quarters of the chip (the FP4 wide kernels' rule; measured here on either side of it, profiles/nf4_wide_batch.json)
+    const int v = g_wide_nf4_variant.load(std::memory_order_relaxed);
+    const bool rt2 = v == 2 || (v != 1 && M >= 24 * device_cu_count());
+    const bool nbw4 = K % 256 == 0;
+    if (rt2) {
+        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4>(x, W, absmax, bias, out, B, M, K, stream);
+        return launch_wide_nf4<DT, NT, 2, 1>(x, W, absmax, bias, out, B, M, K, stream);
+    }
+    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4>(x, W, absmax, bias, out, B, M, K, stream);
+    return launch_wide_nf4<DT, NT, 1, 1>(x, W, absmax, bias, out, B, M, K, stream);
+}
+
+// one launch: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
+template <int DT>
+void dispatch_wide_nf4(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
+                       hipStream_t stream) {
+    switch ((B + 15) / 16) {
+        case 1: return dispatch_wide_nf4_nt<DT, 1>(x, W, absmax, bias, out, B, M, K, stream);
+        case 2: return dispatch_wide_nf4_nt<DT, 2>(x, W, absmax, bias, out, B, M, K, stream);
+        case 3: return dispatch_wide_nf4_nt<DT, 3>(x, W, absmax, bias, out, B, M, K, stream);
+        default: return dispatch_wide_nf4_nt<DT, 4>(x, W, absmax, bias, out, B, M, K, stream);
+    }
+}
+
+}  // namespace
+
+void set_wide_nf4_variant(int v) { g_wide_nf4_variant.store(v, std::memory_order_relaxed); }
+
+}  // namespace fp4
+
+extern "C" int fp4_hip_gemm_wide_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
+                                     int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
+    using namespace fp4;
+    if (B < 0 || M < 0 || K <= 0 || blocksize <= 0) {
+        set_error("fp4_hip_gemm_wide_nf4: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", (long long)B,
+                  (long long)M, (long long)K, blocksize);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
+    // the kernel addresses with 64-bit element offsets: M * K may pass 2^32; the bounds keep the int row / block arithmetic in range
+    if (B > 128 || blocksize != 64 || (K % 64) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) || (align & 15u) != 0 ||
+        M > (int64_t(1) << 30) || K > (int64_t(1) << 24)) {
+        set_error("fp4_hip_gemm_wide_nf4: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..128 rows, blocksize 64, "
+                  "K %% 64 == 0, fp16 / bf16, 16-byte aligned x and packed); use dequant + GEMM",
+                  (long long)B, (long long)M, (long long)K, blocksize, dtype);
+        return FP4_ERR_UNSUPPORTED;
+    }
+    if (M == 0 || B == 0) return FP4_OK;
+    if (!x || !packed || !absmax || !out) {
+        set_error("fp4_hip_gemm_wide_nf4: null pointer");
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    // 1..16 rows on a K the 2..16-row kernel covers: that kernel, bit for bit
+    if (B <= 16 && K % 512 == 0) return fp4_hip_gemm_small_nf4(x, packed, absmax, bias, out, B, M, K, blocksize, dtype, stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int esize = 2;
+    // 65..128 rows: two even chunks of at most 64, one pass over the weight each
+    const int64_t first = B > 64 ? (B + 1) / 2 : B;
+    for (int64_t b0 = 0; b0 < B; b0 += first) {
+        const int rows = (int)(B - b0 < first ? B - b0 : first);
+        const void *xc = static_cast<const uint8_t *>(x) + b0 * K * esize;
+        void *oc = static_cast<uint8_t *>(out) + b0 * M * esize;
+        if (dtype == FP4_DTYPE_F16)
+            dispatch_wide_nf4<FP4_DTYPE_F16>(xc, packed, absmax, bias, oc, rows, (int)M, (int)K, s);
+        else
+            dispatch_wide_nf4<FP4_DTYPE_BF16>(xc, packed, absmax, bias, oc, rows, (int)M, (int)K, s);
+    }
+    return check_launch("fp4_hip_gemm_wide_nf4");
+}

@@ -13,7 +13,7 @@
 //   * launch / dtype failures raise instead of printf (csrc/dequant_fp4_optimized.cu:48-53,201-203);
 //   * qlinear_codebook* dequantise all M*N elements (the reference passes the BYTE count,
 //     csrc/torch_fp4.cpp:90,101, leaving half of the weight uninitialised).
-// Extra exports (not in the reference): the NF4 ops (dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4, qlinear_nf4_bias, gemm_small_nf4,
+// Extra exports (not in the reference): the NF4 ops (dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4, qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4,
 // quantize_nf4: bitsandbytes' second 4-bit code, same kernels' shapes and dispatch), gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -507,6 +507,38 @@ torch::Tensor gemm_small_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor abs
     return out;
 }
 
+// fused NF4 wide-batch product on the matrix cores (fp4_hip_gemm_wide_nf4): A [..., K] with 1..128 rows in total -> [..., m];
+// raises if the shape is not covered (blocksize 64, K % 64 == 0, fp16 / bf16).  One allocation (the output), no sync: capturable.
+torch::Tensor gemm_wide_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                             c10::optional<torch::Tensor> bias) {
+    check_gpu_contiguous(A, "A");
+    check_gpu_contiguous(B, "B");
+    check_gpu_contiguous(absmax, "absmax");
+    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
+    const int64_t m = Bshape[0], k = Bshape[1];
+    TORCH_CHECK(A.dim() >= 1 && A.size(-1) == k, "gemm_wide_nf4: last dim of the activation must be in_features = ", k);
+    const int64_t rows = A.numel() / k;
+    TORCH_CHECK(rows >= 1 && rows <= 128, "gemm_wide_nf4 covers 1..128 activation rows, got ", rows);
+    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
+    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
+    const int dt = to_fp4_dtype(A.scalar_type(), "gemm_wide_nf4");
+    auto shape = A.sizes().vec();
+    shape.back() = m;
+    torch::Tensor out = torch::empty(shape, A.options());
+    const void *bias_ptr = nullptr;
+    torch::Tensor bias_c;
+    if (bias.has_value()) {
+        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
+                    "] tensor of the activation dtype");
+        bias_c = bias->contiguous();
+        bias_ptr = bias_c.data_ptr();
+    }
+    c10::DeviceGuard guard(A.device());
+    check_status(fp4_hip_gemm_wide_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, out.data_ptr(), rows, m,
+                                        k, blocksize, dt, current_stream(A)));
+    return out;
+}
+
 // the small-batch product with the fused epilogues (fp4_hip_gemm_small_fused): A [..., K] with 1..128 rows -> [..., m] or [..., m / 2]
 torch::Tensor gemm_small_fp4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
                                    c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
@@ -702,6 +734,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("qlinear_nf4", &qlinear_nf4, "NF4 dequant + linear: (A_in, A, absmax, M, N, blocksize)");
     m.def("qlinear_nf4_bias", &qlinear_nf4_bias, "NF4 dequant + linear + bias: (A_in, A, absmax, M, N, blocksize, bias)");
     m.def("gemm_small_nf4", &gemm_small_nf4, "fused NF4 product for 1..16 activation rows: (A, B, absmax, blocksize, Bshape, bias|None)");
+    m.def("gemm_wide_nf4", &gemm_wide_nf4, "fused NF4 product for 1..128 activation rows: (A, B, absmax, blocksize, Bshape, bias|None)");
     m.def("quantize_nf4", &quantize_nf4, "blockwise NF4 quantiser: (W, blocksize) -> (packed, absmax)");
     m.def("code_table", &code_table, "16-entry code table as a CPU float tensor");
     m.def("set_kernel_variant", &set_kernel_variant, "benchmark hook: select a kernel geometry");

@@ -11,7 +11,8 @@ torch_bnb_fp4/__init__.py), backed by hand-written CDNA4 HIP kernels:
 Both bitsandbytes 4-bit codes are decoded: ``quant_type="fp4"`` (the reference's) and ``"nf4"`` (QLoRA's).
 NF4 runs a fused GEMV for one token and, behind ``set_small_batch_fused(model, True, nf4=True)`` (``QuantData.small_batch_fused_nf4``,
 off by default), a fused matrix-core kernel for 2..16 rows (``ext.gemm_small_nf4``; blocksize 64, in_features % 512 == 0, fp16 / bf16);
-everything else is NF4 dequant + GEMM.
+behind ``nf4_wide=True`` (``QuantData.wide_batch_fused_nf4``, off by default) a one-pass kernel for 17..64 rows, and for 2..16 rows where
+in_features % 512 != 0 (``ext.gemm_wide_nf4``; blocksize 64, in_features % 64 == 0, fp16 / bf16); everything else is NF4 dequant + GEMM.
 bitsandbytes is optional: :mod:`torch_bnb_fp4.nn` provides attribute-compatible ``LinearFP4`` /
 ``Params4bit`` / ``QuantState`` and the quantiser runs on the GPU through this package.
 """

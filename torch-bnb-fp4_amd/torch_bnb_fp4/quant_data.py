@@ -18,7 +18,10 @@ other row ``qlinear_nf4`` whatever ``use_codebook_dequant`` says (NF4 has one ta
 FP4 small-batch kernels decode FP4 only).  NF4 has a switch of its own, ``small_batch_fused_nf4`` (OFF by default): 2..16 rows of
 fp16 / bf16 activations against a blocksize-64 weight with K % 512 == 0 go to ``gemm_small_nf4`` (the matrix-core kernel of
 csrc/gemm_small_nf4.hip) instead of dequant + GEMM; every other input goes where it goes without the switch, and an FP4 weight
-ignores it.  Any other ``quant_type`` is refused.
+ignores it.  ``wide_batch_fused_nf4`` (OFF by default) does the same for 17..64 rows, and for 2..16 rows where K % 512 != 0,
+with K % 64 == 0: they go to ``gemm_wide_nf4`` (csrc/gemm_wide_nf4.hip, one pass over the packed weight).  The op itself takes up
+to 128 rows (two passes above 64); those lose to dequant + GEMM on an MI355X and are not routed (profiles/nf4_wide_batch.json).
+Any other ``quant_type`` is refused.
 
 Two extensions.  ``fuse_bias`` (ON by default) folds the post-GEMV ``out += bias`` into the kernel epilogue: the table above
 still holds and the result is bit-identical (``T(T(sum) + bias)``), there is just one launch fewer; ``fuse_bias=False`` runs the
@@ -42,7 +45,8 @@ class QuantData:
     def __init__(self, A: torch.Tensor, state, shape: Tuple[int, int], original_lin=None,
                  bias: Optional[torch.Tensor] = None, use_codebook_dequant: Optional[bool] = True,
                  allow_reduced_precision_linear: Optional[bool] = False, fuse_bias: bool = True,
-                 small_batch_fused: bool = False, small_batch_fused_nf4: bool = False):
+                 small_batch_fused: bool = False, small_batch_fused_nf4: bool = False,
+                 wide_batch_fused_nf4: bool = False):
         self.use_codebook_dequant = use_codebook_dequant
         self.quant_type = check_quant_type(getattr(state, "quant_type", "fp4"))
         self.nf4 = self.quant_type == "nf4"
@@ -66,6 +70,9 @@ class QuantData:
         self.small_batch_fused = small_batch_fused
         # opt-in, NF4 weights only: 2..16 rows go to the fused NF4 matrix-core kernel (4096 x 4096 bf16: see profiles/nf4_small_batch.json)
         self.small_batch_fused_nf4 = small_batch_fused_nf4
+        # opt-in, NF4 weights only: 17..64 rows (and 2..16 where K % 512 != 0) go to the one-pass NF4 kernel; 65..128 rows, which the
+        # kernel serves in two passes, measured slower than dequant + GEMM and stay there (profiles/nf4_wide_batch.json)
+        self.wide_batch_fused_nf4 = wide_batch_fused_nf4
         # per-call constants of the decode path, built once (224 calls per token in a 7B model)
         self._B_t = A.t()
         self._shape_list = [int(shape[0]), int(shape[1])]
@@ -184,4 +191,7 @@ class QuantData:
         if self.small_batch_fused_nf4 and self.nf4 and 2 <= rows <= 16 and self.blocksize == 64 and K % 512 == 0 and (
                 A.dtype in (torch.float16, torch.bfloat16)):
             return ext.gemm_small_nf4(A.contiguous(), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
+        if self.wide_batch_fused_nf4 and self.nf4 and self.blocksize == 64 and K % 64 == 0 and (
+                17 <= rows <= 64 or (2 <= rows <= 16 and K % 512 != 0)) and A.dtype in (torch.float16, torch.bfloat16):
+            return ext.gemm_wide_nf4(A.contiguous(), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
         return self.qlinear(A)

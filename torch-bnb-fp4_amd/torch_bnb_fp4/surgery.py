@@ -136,7 +136,7 @@ def recursively_replace_with_fp4_linear(
         return module
 
 
-def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = False) -> int:
+def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = False, nf4_wide: bool = False) -> int:
     """Route 2..128 activation rows of every :class:`TorchFP4Linear` below ``module`` to the fused small-batch kernels
     (``enabled=True``) or back to the reference's dispatch, dequant + GEMM for every batch > 1
     (torch_bnb_fp4/__init__.py:592,616-617; the default, so that a converted model behaves like the reference's).
@@ -144,7 +144,9 @@ def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = F
     3 237 tok/s fused vs 963 tok/s through the reference dispatch at 8 sequences (profiles/).  NF4 layers are left on
     dequant + GEMM (the FP4 small-batch kernels decode FP4 only) and not counted, unless ``nf4=True``: then every NF4 layer's
     ``small_batch_fused_nf4`` is set as well - 2..16 rows of fp16 / bf16 activations go to the fused NF4 matrix-core kernel
-    (blocksize 64, K % 512 == 0; anything else stays on dequant + GEMM) - and those layers are counted too."""
+    (blocksize 64, K % 512 == 0; anything else stays on dequant + GEMM) - and those layers are counted too.  ``nf4_wide=True``
+    sets every NF4 layer's ``wide_batch_fused_nf4``: 17..64 rows, and 2..16 rows where K % 512 != 0, go to the one-pass NF4
+    kernel (``ext.gemm_wide_nf4``; blocksize 64, K % 64 == 0); an NF4 layer is counted once whichever of the two is set."""
     n = 0
     for m in module.modules():
         if not isinstance(m, TorchFP4Linear):
@@ -152,8 +154,11 @@ def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = F
         if not m.quant_data.nf4:
             m.quant_data.small_batch_fused = bool(enabled)
             n += 1
-        elif nf4:
-            m.quant_data.small_batch_fused_nf4 = bool(enabled)
+        elif nf4 or nf4_wide:
+            if nf4:
+                m.quant_data.small_batch_fused_nf4 = bool(enabled)
+            if nf4_wide:
+                m.quant_data.wide_batch_fused_nf4 = bool(enabled)
             n += 1
     return n
 
