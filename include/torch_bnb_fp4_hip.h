@@ -246,7 +246,8 @@ FP4_HIP_API int fp4_hip_quantize_blockwise_nf4(const void *w, int w_dtype, uint8
  * input is relied on), both read from a 256-entry LDS table indexed by the packed byte; |hi + lo - code| <= 5.45e-6 |code|.
  * Covered: 1 <= B <= 16, blocksize 64, K % 512 == 0 (K <= 2^24), fp16 / bf16, any M >= 1 up to 2^30 (M * K may pass 2^32:
  * 64-bit addressing), x and packed 16-byte aligned.  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, out untouched - the
- * caller uses NF4 dequant + GEMM.  FP4_OK without a launch for M == 0 or B == 0.  No fused epilogues, no 17+ rows.
+ * caller uses NF4 dequant + GEMM.  FP4_OK without a launch for M == 0 or B == 0.  No 17+ rows; the fused epilogues are
+ * fp4_hip_gemm_fused_nf4's.
  */
 FP4_HIP_API int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                                        int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream);
@@ -260,10 +261,41 @@ FP4_HIP_API int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, con
  * x and packed 16-byte aligned.  17..64 rows: one launch; 65..128 rows: two even chunks of at most 64 (two launches);
  * 1..16 rows: fp4_hip_gemm_small_nf4 itself where K % 512 == 0 (bit-identical), else the one-tile form of this kernel.
  * Deterministic (fixed summation order, no atomics), no allocation, no synchronisation: capturable.  Everything else:
- * FP4_ERR_UNSUPPORTED, nothing launched, out untouched.  FP4_OK without a launch for M == 0 or B == 0.  No fused epilogues.
+ * FP4_ERR_UNSUPPORTED, nothing launched, out untouched.  FP4_OK without a launch for M == 0 or B == 0.  The fused epilogues are
+ * fp4_hip_gemm_fused_nf4's.
  */
 FP4_HIP_API int fp4_hip_gemm_wide_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                                       int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream);
+
+/*
+ * fp4_hip_gemv_fused_nf4: fp4_hip_gemv_fused over an NF4 weight - the batch-1 NF4 GEMV with the decode-step epilogues folded in,
+ * every intermediate rounded to T where the separate torch ops would round it.  An addition to ABI version 7.
+ *   EPILOGUE_NONE:            t = T(sum_r); if bias: t = T(t + bias[r]); if residual: t = T(t + residual[r]); out[r] = t.  out : T[M].
+ *                             The sum is fp4_hip_gemv_nf4's, bit for bit (f32: plain f32 adds, sum + bias, then + residual).
+ *   EPILOGUE_SILU_MUL_PAIRS:  rows 2i / 2i+1 are gate_i / up_i; g = T(sum_2i) (+bias), u = T(sum_2i+1) (+bias),
+ *                             s = T(g / (1 + exp(-g))), t = T(s * u); if residual: t = T(t + residual[i]); out[i] = t.  out : T[M/2].
+ * `residual` may alias `out`.  Covered: the fast path of fp4_hip_gemv_nf4 - K % 32 == 0, a power-of-two blocksize >= 32 dividing
+ * K, x and packed 16-byte aligned; all three dtypes for EPILOGUE_NONE, fp16 / bf16 for the gated one.  Everything else:
+ * FP4_ERR_UNSUPPORTED, nothing launched, out untouched - the caller runs fp4_hip_gemv_nf4 and the separate ops.  Unknown epilogue,
+ * or the gated one with an odd M ("even row count"): FP4_ERR_INVALID_ARGUMENT.  FP4_OK without a launch for M == 0.
+ */
+FP4_HIP_API int fp4_hip_gemv_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                       void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
+
+/*
+ * fp4_hip_gemm_fused_nf4: fp4_hip_gemm_small_fused over an NF4 weight, with the coverage and the forwarding of
+ * fp4_hip_gemm_wide_nf4 (1..128 rows, blocksize 64, K % 64 == 0, fp16 / bf16; 1..16 rows with K % 512 == 0 run the kernel of
+ * fp4_hip_gemm_small_nf4; 65..128 rows are two even chunks).  Rounding is F.linear's, then the epilogue as separate rounded ops:
+ *   EPILOGUE_NONE:            t = T(sum[b][r] + bias[r]); if residual: t = T(t + residual[b][r]).  out, residual : T[B, M].
+ *                             With residual == NULL the result equals fp4_hip_gemm_wide_nf4's bit for bit.
+ *   EPILOGUE_SILU_MUL_PAIRS:  g = T(sum_2i + bias_2i), u = T(sum_2i+1 + bias_2i+1), t = T(T(silu(g)) * u);
+ *                             if residual: t = T(t + residual[b][i]).  out, residual : T[B, M/2], M even.
+ * `residual` may alias `out`.  Deterministic, no allocation, no synchronisation: capturable.  Shapes outside the coverage:
+ * FP4_ERR_UNSUPPORTED, nothing launched, out untouched.  Unknown epilogue, or the gated one with an odd M ("even row count"):
+ * FP4_ERR_INVALID_ARGUMENT.  FP4_OK without a launch for M == 0 or B == 0.  An addition to ABI version 7.
+ */
+FP4_HIP_API int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                       void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
 
 /*
  * Tuning hook for benchmarks/sweeps: selects a kernel geometry by name

@@ -47,7 +47,7 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
     world == 1: QuantData dispatchers (the product's single-GPU path).  world > 1: Column/RowParallelFP4Linear
     (q/k/v/gate/up M-split without a gather, o/down K-split with one f32 all-reduce each: 2 all-reduces per layer).
     fuse: q|k|v and gate|up as one launch each (row concatenation).  epilogues: on top of that, silu(gate)*up and the
-    residual adds run in the GEMV epilogue (torch_bnb_fp4.fused).  tensor_parallel: None = (world > 1); True builds the tensor-parallel
+    residual adds run in the GEMV epilogue (torch_bnb_fp4.fused; with nf4 the layers are FusedNF4Linear).  tensor_parallel: None = (world > 1); True builds the tensor-parallel
     modules even for a one-rank group (bench.py's FP4_BENCH_FORCE_GROUP rehearsal of the N > 1 path through real RCCL on one GPU)."""
     import torch_bnb_fp4 as pkg
     from torch_bnb_fp4 import parallel as par
@@ -64,7 +64,7 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
     code = pkg.ext.code_table("nf4" if nf4 else "tree").to(dev)
 
     def qd_of(packed, absmax, m, k):
-        # nf4 (single GPU, unfused layers only): the same random bytes read as NF4 codes, both NF4 switches on unless reference_dispatch
+        # nf4 (single GPU): the same random bytes read as NF4 codes, both NF4 switches on unless reference_dispatch
         state = pkg.QuantState(absmax, (m, k), code, BS, quant_type="nf4" if nf4 else "fp4")
         return pkg.QuantData(packed, state, state.shape, original_lin=None, bias=None,
                              small_batch_fused=not reference_dispatch, small_batch_fused_nf4=nf4 and not reference_dispatch,
@@ -89,10 +89,11 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
         if epilogues and not tp:
             from torch_bnb_fp4 import fused
 
+            Fused = fused.FusedNF4Linear if nf4 else fused.FusedFP4Linear
             ly = dict(qkv=linear([H, KV, KV], H, "col"),
-                      o=fused.FusedFP4Linear.from_packed(*fp4_weight(H, H), (H, H), BS),
-                      gate_up=fused.FusedFP4Linear.gate_up_from_packed(fp4_weight(I, H), fp4_weight(I, H), (I, H), BS),
-                      down=fused.FusedFP4Linear.from_packed(*fp4_weight(H, I), (H, I), BS))
+                      o=Fused.from_packed(*fp4_weight(H, H), (H, H), BS),
+                      gate_up=Fused.gate_up_from_packed(fp4_weight(I, H), fp4_weight(I, H), (I, H), BS),
+                      down=Fused.from_packed(*fp4_weight(H, I), (H, I), BS))
         elif fuse and not tp:
             ly = dict(qkv=linear([H, KV, KV], H, "col"), o=linear(H, H, "row"), gate_up=linear([I, I], H, "col"),
                       down=linear(H, I, "row"))
@@ -218,7 +219,7 @@ def main():
                     help="batch > 1 through dequant + GEMM like the reference, instead of the fused small-batch kernels")
     ap.add_argument("--allreduce", default="dist", choices=("dist", "oneshot"),
                     help="world > 1: torch.distributed all-reduce (RCCL) or the one-shot peer-slot kernel")
-    ap.add_argument("--nf4", action="store_true", help="NF4 weights instead of FP4 (single GPU, without --fuse / --epilogues)")
+    ap.add_argument("--nf4", action="store_true", help="NF4 weights instead of FP4 (single GPU; with --epilogues the layers are FusedNF4Linear)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--lean-glue", action="store_true",
                     help="attention stand-in as ONE elementwise launch and no rescale: what is left besides the FP4 Linears is minimal")
@@ -272,6 +273,7 @@ def main():
             "allreduces_per_token": meta["allreduces_per_token"], "allreduce": args.allreduce if world > 1 else None,
             "tokens_per_s": round(args.batch / best, 1), "fp4_stream_gbps_per_gpu": round(per_token_fp4 / best / 1e9, 1),
             "hbm_floor_ms_per_token_at_8TBps": round((per_token_fp4 + meta["lm_head_bytes"]) / 8e12 * 1e3, 3),
+            "quant_type": "nf4" if args.nf4 else "fp4",
             "data": "synthetic random FP4 bytes + scales; attention replaced by identity; lm_head dense " + args.dtype,
         }), file=result_out, flush=True)
     if world > 1:

@@ -18,6 +18,14 @@ one-pass kernel, under its own heuristic and with 16 / 32 weight rows per workgr
 1 / 2)); (b) qlinear_nf4; (c) ceil(rows / 16) launches of gemm_small_nf4 (K % 512 == 0 only); (d) gemm_small_fp4 on the same
 bytes, for orientation.  (a), (b), (c) carry min / max over the replays; a cell is won where (a) beats (b) AND (c), each by more than
 the two full ranges together.  --revision names the tree the figures belong to.
+
+--fused: the decode epilogues (profiles/nf4_fused_epilogues.json), bf16, one run on the same operands.  (1) The plain calls the
+epilogue work touched - gemv_nf4, gemm_small_nf4 at 2 / 16 rows, gemm_wide_nf4 at 32 / 64 rows, 4096 x 4096 and 14336 x 4096 - through
+this tree's library and, with --baseline-lib, through another build of it (the parent commit's) loaded side by side; a cell is
+"within" where the medians differ by no more than the larger of the two replay-to-replay ranges.  (2) The fused ops against the
+unfused sequence they replace (the plain op, then torch's silu / mul / add) at the Mistral-7B shapes and 1 / 8 / 32 / 64 rows: the
+o projection with its residual add, gate|up with silu(g) * u, and gate|up + down with the residual; a cell is won where the fused
+form is ahead by more than both ranges together.
 """
 import argparse
 import ctypes
@@ -173,6 +181,106 @@ def wide_batch(args):
                       "cells": cells}))
 
 
+def fused_epilogues(args):
+    L = lib()
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    dev = torch.device("cuda", 0)
+    s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    dtype, dt = torch.bfloat16, DT[torch.bfloat16]
+    qtype = pkg.ScalarType.from_torch_dtype(dtype).value
+
+    def bind(l):
+        l.fp4_hip_gemv_nf4.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+        for f in (l.fp4_hip_gemm_small_nf4, l.fp4_hip_gemm_wide_nf4):
+            f.argtypes = [vp] * 5 + [i64] * 3 + [i32] * 2 + [vp]
+        return l
+
+    libs = {"this_tree": bind(L)}
+    if args.baseline_lib:
+        libs["baseline"] = bind(ctypes.CDLL(os.path.abspath(args.baseline_lib)))
+
+    def timed(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        med, samples = time_replays(replay, args.reps, args.launches)
+        q = sorted(samples)
+        return {"us": round(med, 2), "min_us": round(q[0], 2), "max_us": round(q[-1], 2)}
+
+    rng_of = lambda t: t["max_us"] - t["min_us"]  # noqa: E731
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def nf4_weight(M, K):
+        packed = torch.randint(0, 256, (M * K // 2,), dtype=torch.uint8, device=dev, generator=gen)
+        absmax = torch.rand(M * K // BS, device=dev, generator=gen) * 0.02 + 0.002
+        return packed, absmax
+
+    # (1) the plain calls, this tree's library and the baseline build side by side
+    plain = []
+    for M, K in ((4096, 4096), (14336, 4096)):
+        packed, absmax = nf4_weight(M, K)
+        x = torch.randn(64, K, device=dev).to(dtype)
+        y = torch.empty(64, M, dtype=dtype, device=dev)
+        calls = [("gemv_nf4", 1, lambda l: l.fp4_hip_gemv_nf4(p_(x), p_(packed), p_(absmax), None, p_(y), M, K, BS, dt, s()))]
+        for name, rows in (("gemm_small_nf4", 2), ("gemm_small_nf4", 16), ("gemm_wide_nf4", 32), ("gemm_wide_nf4", 64)):
+            calls.append((name, rows, lambda l, name=name, rows=rows: getattr(l, "fp4_hip_" + name)(
+                p_(x), p_(packed), p_(absmax), None, p_(y), rows, M, K, BS, dt, s())))
+        for name, rows, fn in calls:
+            cell = {"M": M, "K": K, "call": name, "rows": rows}
+            for tag, l in libs.items():
+                if fn(l):
+                    raise RuntimeError(l.fp4_hip_last_error().decode())
+                cell[tag] = timed(lambda: fn(l))
+            if "baseline" in cell:
+                margin = max(rng_of(cell["this_tree"]), rng_of(cell["baseline"]))
+                cell["margin_us"] = round(margin, 2)
+                cell["delta_us"] = round(cell["this_tree"]["us"] - cell["baseline"]["us"], 2)
+                cell["within_margin"] = bool(cell["delta_us"] <= margin)
+            plain.append(cell)
+        del packed, absmax
+
+    # (2) fused against the unfused sequence, Mistral-7B shapes
+    H, I = 4096, 14336
+    wo, wgu, wdn = nf4_weight(H, H), nf4_weight(2 * I, H), nf4_weight(H, I)
+    t_ = lambda w: w[0].view(-1, 1).t()  # noqa: E731
+    silu = torch.nn.functional.silu
+
+    def lin(w, shape, x):  # the unfused op QuantData issues for this row count
+        if x.shape[0] == 1:
+            return pkg.ext.gemv_nf4(x, t_(w), w[1], BS, qtype, shape)
+        return pkg.ext.gemm_wide_nf4(x, t_(w), w[1], BS, shape, None)
+
+    def fused_op(w, shape, x, res, epi):
+        op = pkg.ext.gemv_nf4_fused if x.shape[0] == 1 else pkg.ext.gemm_nf4_fused
+        return op(x, t_(w), w[1], BS, shape, None, res, epi)
+
+    def unfused_gate_up(h):
+        g, u = lin(wgu, [2 * I, H], h).split([I, I], dim=-1)
+        return silu(g) * u
+
+    cells = []
+    for rows in (1, 8, 32, 64):
+        h = torch.randn(rows, H, device=dev).to(dtype)
+        a = torch.randn(rows, I, device=dev).to(dtype)
+        legs = {
+            "o_proj_residual": (lambda: fused_op(wo, [H, H], h, h, 0), lambda: h + lin(wo, [H, H], h)),
+            "gate_up_silu_mul": (lambda: fused_op(wgu, [2 * I, H], h, None, 1), lambda: unfused_gate_up(h)),
+            "down_residual": (lambda: fused_op(wdn, [H, I], a, h, 0), lambda: h + lin(wdn, [H, I], a)),
+            "mlp_gate_up_down_residual": (lambda: fused_op(wdn, [H, I], fused_op(wgu, [2 * I, H], h, None, 1), h, 0),
+                                          lambda: h + lin(wdn, [H, I], unfused_gate_up(h))),
+        }
+        for leg, (f, u) in legs.items():
+            tf, tu = timed(f), timed(u)
+            spread = rng_of(tf) + rng_of(tu)
+            cells.append({"leg": leg, "rows": rows, "fused": tf, "unfused": tu, "saved_us": round(tu["us"] - tf["us"], 2),
+                          "speedup": round(tu["us"] / tf["us"], 3), "spread_us": round(spread, 2),
+                          "fused_ahead_beyond_spread": bool(tu["us"] - tf["us"] > spread)})
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "revision": args.revision, "dtype": "bf16", "blocksize": BS,
+                      "launches_per_graph": args.launches, "reps": args.reps,
+                      "baseline_lib": "the parent commit's library, same run" if args.baseline_lib else "not measured",
+                      "plain_calls": plain, "plain_calls_all_within_margin": (all(c["within_margin"] for c in plain) if args.baseline_lib else None),
+                      "fused_vs_unfused": cells}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -180,7 +288,11 @@ def main():
     ap.add_argument("--small-batch", action="store_true", help="the 2..16-row NF4 regime (profiles/nf4_small_batch.json)")
     ap.add_argument("--wide-batch", action="store_true", help="the 17..128-row NF4 regime (profiles/nf4_wide_batch.json)")
     ap.add_argument("--revision", default="unknown", help="--wide-batch: the git revision the figures belong to, recorded as given")
+    ap.add_argument("--fused", action="store_true", help="the fused NF4 decode epilogues (profiles/nf4_fused_epilogues.json)")
+    ap.add_argument("--baseline-lib", default=None, help="--fused: another build of libtorch_bnb_fp4_hip.so to time the plain calls of, side by side")
     args = ap.parse_args()
+    if args.fused:
+        return fused_epilogues(args)
     if args.small_batch:
         return small_batch(args)
     if args.wide_batch:

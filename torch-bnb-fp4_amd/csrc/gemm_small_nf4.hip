@@ -18,6 +18,11 @@
 // documented, so this kernel does not depend on it: the fp16 table holds lo * 2^24 (every non-zero entry normal, none above 4096),
 // the lo instructions run into a tile of their own, and hi_tile + 2^-24 * lo_tile (exact scaling, one FMA per element) is formed
 // before the block's absmax is applied.  bf16 has f32's exponent range: both instructions share one accumulator.
+//
+// Fused decode epilogues (fp4_hip_gemm_fused_nf4, 1..16 rows with K % 512 == 0): the FUSED instantiations take a residual and the
+// `mode` of gemm_small_fp4.hip.  The final pass over the LDS partials has one thread per (activation row, weight row); for the
+// gate|up epilogue the thread of an even weight row also sums its odd neighbour's partials (tid + 1) and stores the pair, the odd
+// thread stores nothing.  A compile-time choice: the plain entry point keeps its instantiations instruction for instruction.
 #include "gemv_common.h"
 
 namespace fp4 {
@@ -53,10 +58,12 @@ __device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &l
 // lo - four matrix instructions per block and tile.  The B operand is x[n = l & 15][64b + 16kb + 8t + j], from a wave-private LDS
 // image for <= XS rows (XS in {4, 8}), else straight from L2.  Weight image row stride 32*NBW + 32 bytes (the row's NBW scales
 // follow its bytes), x image row stride 128*NBW + 16, as in the FP4 kernel.
-template <int DT, int NBW, int XS>
+// FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
+// gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
+template <int DT, int NBW, int XS, bool FUSED>
 __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
-                                                            uint16_t *out, int B, int M, int K) {
+                                                            uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode) {
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kXStride = 128 * NBW + 16;
     constexpr int kWImageBytes = 8 * 16 * kStageStride;
@@ -214,35 +221,69 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
         for (int w = 0; w < 8; ++w) t += s_part[w][tid];
         const int l = tid >> 2, reg = tid & 3;  // D layout: col = l & 15 (activation row), row = (l >> 4) * 4 + reg (weight row)
         const int n = l & 15, row = row0 + (l >> 4) * 4 + reg;
-        if (row < M && n < B) store_small<DT>(out, bias, nullptr, n, row, M, t);
+        if constexpr (FUSED) {
+            if (mode & kModeSiluMulPairs) {
+                if (!(reg & 1)) {  // row0 is a multiple of 16: an even reg is an even weight row (gate), tid + 1 its up row
+                    float u = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < 8; ++w) u += s_part[w][tid + 1];
+                    if (row < M && n < B) store_small_silu_mul<DT>(out, bias, residual, n, row >> 1, M >> 1, t, u);
+                }
+            } else if (row < M && n < B) {
+                store_small<DT>(out, bias, residual, n, row, M, t);
+            }
+        } else {
+            if (row < M && n < B) store_small<DT>(out, bias, nullptr, n, row, M, t);
+        }
     }
 }
 
-template <int DT, int NBW, int XS>
-void launch_nf4_mfma(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
-                     hipStream_t stream) {
-    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS>), dim3((unsigned)((M + 15) / 16)), dim3(512), 0, stream,
-                       reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
-                       reinterpret_cast<uint16_t *>(out), B, M, K);
+struct SmallNf4Args {
+    const void *x;
+    const uint8_t *W;
+    const float *absmax;
+    const void *bias, *residual;
+    void *out;
+    int B, M, K, mode;
+    hipStream_t stream;
+};
+
+template <int DT, int NBW, int XS, bool FUSED>
+void launch_nf4_mfma(const SmallNf4Args &a) {
+    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
+                       reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
+                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode);
 }
 
-template <int DT>
-void dispatch_nf4_mfma(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
-                       hipStream_t stream) {
+template <int DT, bool FUSED>
+void dispatch_nf4_mfma(const SmallNf4Args &a) {
+    const int B = a.B, M = a.M, K = a.K;
     const int units = K / 512;  // quant blocks per wave over the whole K
     const int blocks = (M + 15) / 16;
     // the FP4 kernel's rules: at most 4 blocks per wave and pass; x staged per wave in LDS always for <= 4 rows, for 5..8 rows only
     // while the grid is a single round anyway (the larger image leaves fewer workgroups per CU)
     if (units % 4 == 0) {
-        if (B <= 4) return launch_nf4_mfma<DT, 4, 4>(x, W, absmax, bias, out, B, M, K, stream);
-        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8>(x, W, absmax, bias, out, B, M, K, stream);
-        return launch_nf4_mfma<DT, 4, 0>(x, W, absmax, bias, out, B, M, K, stream);
+        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED>(a);
+        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED>(a);
+        return launch_nf4_mfma<DT, 4, 0, FUSED>(a);
     }
-    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0>(x, W, absmax, bias, out, B, M, K, stream);
-    return launch_nf4_mfma<DT, 1, 0>(x, W, absmax, bias, out, B, M, K, stream);
+    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED>(a);
+    return launch_nf4_mfma<DT, 1, 0, FUSED>(a);
 }
 
 }  // namespace
+
+// the fused-epilogue form for fp4_hip_gemm_fused_nf4 (gemm_wide_nf4.hip), which has validated the arguments: 1..16 rows,
+// K % 512 == 0, fp16 / bf16, M even for the gate|up epilogue.  Launches only.
+void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
+                                 void *out, int B, int M, int K, int mode, hipStream_t stream) {
+    const SmallNf4Args a{x, W, absmax, bias, residual, out, B, M, K, mode, stream};
+    if (dtype == FP4_DTYPE_F16)
+        dispatch_nf4_mfma<FP4_DTYPE_F16, true>(a);
+    else
+        dispatch_nf4_mfma<FP4_DTYPE_BF16, true>(a);
+}
+
 }  // namespace fp4
 
 extern "C" int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
@@ -268,9 +309,10 @@ extern "C" int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, cons
         return FP4_ERR_INVALID_ARGUMENT;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const SmallNf4Args a{x, packed, absmax, bias, nullptr, out, (int)B, (int)M, (int)K, 0, s};
     if (dtype == FP4_DTYPE_F16)
-        dispatch_nf4_mfma<FP4_DTYPE_F16>(x, packed, absmax, bias, out, (int)B, (int)M, (int)K, s);
+        dispatch_nf4_mfma<FP4_DTYPE_F16, false>(a);
     else
-        dispatch_nf4_mfma<FP4_DTYPE_BF16>(x, packed, absmax, bias, out, (int)B, (int)M, (int)K, s);
+        dispatch_nf4_mfma<FP4_DTYPE_BF16, false>(a);
     return check_launch("fp4_hip_gemm_small_nf4");
 }

@@ -21,6 +21,12 @@
 // through a wave-private LDS image; x fragments come straight from L2, one block ahead, and are shared by the RT row tiles.  The
 // row tiles are looped INSIDE a block so that only tile[NT] (fp16: two of them) is live beside acc[RT][NT].  The eight waves'
 // partial tiles meet in LDS and are added in a fixed order: deterministic, no atomics, no workspace.
+//
+// Fused decode epilogues (fp4_hip_gemm_fused_nf4): the FUSED instantiations take a residual and the `mode` of gemm_wide_fp4.hip.  The
+// final pass has one thread per (tile, activation row, weight row); for the gate|up epilogue the thread of an even weight row also
+// sums its odd neighbour's partials (wr + 1 = src + 4, as wide_epilogue of gemm_wide_fp4.hip does) and stores the pair, odd rows
+// store nothing; row tiles are 16 rows and row0 is even, so a pair never straddles a tile.  A compile-time choice: the plain entry
+// point keeps its instantiations instruction for instruction.
 #include "gemv_common.h"
 
 #include <atomic>
@@ -57,10 +63,12 @@ __device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &l
 // packed dword [16t + 4kb, 16t + 4kb + 4) of weight row r (k = 32t + 8kb + j), the A operand x[16nt + r][64b + 32t + 8kb + j], so
 // one x load instruction reads 64 contiguous bytes per activation row.  D: lane holds out[16nt + 4kb + reg][row0 + 16rt + r].
 // Weight image (per wave): 16 * RT rows of stride 32 * NBW + 32 bytes, the row's NBW scales behind its bytes.
-template <int DT, int NT, int RT, int NBW>
+// FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
+// gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
+template <int DT, int NT, int RT, int NBW, bool FUSED>
 __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
-                                                            uint16_t *out, int B, int M, int K) {
+                                                            uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode) {
     constexpr int kRows = 16 * RT;
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kImageBytes = 8 * kRows * kStageStride;
@@ -236,90 +244,155 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
         for (int w = 0; w < 4; ++w) t += s_part[w][src];
         const int n = 16 * (tile % NT) + n_l;
         const int64_t row = row0 + 16 * (tile / NT) + wr;
-        if (row < M && n < B) store_small<DT>(out, bias, nullptr, n, (int)row, M, t);
+        if constexpr (FUSED) {
+            if (mode & kModeSiluMulPairs) {
+                if (!(wr & 1)) {  // an even weight row of the tile (gate); its up row is the next lane's column: src + 4
+                    float u = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) u += s_part[w][src + 4];
+                    if (row < M && n < B) store_small_silu_mul<DT>(out, bias, residual, n, (int)(row >> 1), M >> 1, t, u);
+                }
+            } else if (row < M && n < B) {
+                store_small<DT>(out, bias, residual, n, (int)row, M, t);
+            }
+        } else {
+            if (row < M && n < B) store_small<DT>(out, bias, nullptr, n, (int)row, M, t);
+        }
     }
 }
 
 std::atomic<int> g_wide_nf4_variant{-1};  // sweep hook: 1 / 2 = 16 / 32 weight rows per workgroup, anything else = the heuristic
 
-template <int DT, int NT, int RT, int NBW>
-void launch_wide_nf4(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
-                     hipStream_t stream) {
-    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW>), dim3((unsigned)((M + 16 * RT - 1) / (16 * RT))), dim3(512), 0, stream,
-                       reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
-                       reinterpret_cast<uint16_t *>(out), B, M, K);
+struct WideNf4Args {
+    const void *x;
+    const uint8_t *W;
+    const float *absmax;
+    const void *bias, *residual;
+    void *out;
+    int B, M, K, mode;
+    hipStream_t stream;
+};
+
+template <int DT, int NT, int RT, int NBW, bool FUSED>
+void launch_wide_nf4(const WideNf4Args &a) {
+    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512), 0,
+                       a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
+                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode);
 }
 
-template <int DT, int NT>
-void dispatch_wide_nf4_nt(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
-                          hipStream_t stream) {
+template <int DT, int NT, bool FUSED>
+void dispatch_wide_nf4_nt(const WideNf4Args &a) {
+    const int M = a.M, K = a.K;
     // 32 weight rows per workgroup halve the x traffic from L2, the kernel's largest stream: taken once that still fills three
     // quarters of the chip (the FP4 wide kernels' rule; measured here on either side of it, profiles/nf4_wide_batch.json)
     const int v = g_wide_nf4_variant.load(std::memory_order_relaxed);
     const bool rt2 = v == 2 || (v != 1 && M >= 24 * device_cu_count());
     const bool nbw4 = K % 256 == 0;
     if (rt2) {
-        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4>(x, W, absmax, bias, out, B, M, K, stream);
-        return launch_wide_nf4<DT, NT, 2, 1>(x, W, absmax, bias, out, B, M, K, stream);
+        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED>(a);
+        return launch_wide_nf4<DT, NT, 2, 1, FUSED>(a);
     }
-    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4>(x, W, absmax, bias, out, B, M, K, stream);
-    return launch_wide_nf4<DT, NT, 1, 1>(x, W, absmax, bias, out, B, M, K, stream);
+    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED>(a);
+    return launch_wide_nf4<DT, NT, 1, 1, FUSED>(a);
 }
 
 // one launch: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
-template <int DT>
-void dispatch_wide_nf4(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int B, int M, int K,
-                       hipStream_t stream) {
-    switch ((B + 15) / 16) {
-        case 1: return dispatch_wide_nf4_nt<DT, 1>(x, W, absmax, bias, out, B, M, K, stream);
-        case 2: return dispatch_wide_nf4_nt<DT, 2>(x, W, absmax, bias, out, B, M, K, stream);
-        case 3: return dispatch_wide_nf4_nt<DT, 3>(x, W, absmax, bias, out, B, M, K, stream);
-        default: return dispatch_wide_nf4_nt<DT, 4>(x, W, absmax, bias, out, B, M, K, stream);
+template <int DT, bool FUSED>
+void dispatch_wide_nf4(const WideNf4Args &a) {
+    switch ((a.B + 15) / 16) {
+        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED>(a);
+        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED>(a);
+        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED>(a);
+        default: return dispatch_wide_nf4_nt<DT, 4, FUSED>(a);
     }
 }
 
 }  // namespace
 
+void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
+                                 void *out, int B, int M, int K, int mode, hipStream_t stream);  // gemm_small_nf4.hip
+
 void set_wide_nf4_variant(int v) { g_wide_nf4_variant.store(v, std::memory_order_relaxed); }
 
 }  // namespace fp4
 
-extern "C" int fp4_hip_gemm_wide_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
-                                     int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
-    using namespace fp4;
+namespace fp4 {
+namespace {
+
+// fused = false: fp4_hip_gemm_wide_nf4.  fused = true: fp4_hip_gemm_fused_nf4 (same coverage and forwarding, plus residual / mode).
+int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
+                        const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode,
+                        void *stream) {
     if (B < 0 || M < 0 || K <= 0 || blocksize <= 0) {
-        set_error("fp4_hip_gemm_wide_nf4: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", (long long)B,
-                  (long long)M, (long long)K, blocksize);
+        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", name, (long long)B, (long long)M,
+                  (long long)K, blocksize);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    if ((mode & kModeSiluMulPairs) && (M & 1)) {
+        set_error("%s: the gate|up epilogue needs an even row count, got M=%lld", name, (long long)M);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
     // the kernel addresses with 64-bit element offsets: M * K may pass 2^32; the bounds keep the int row / block arithmetic in range
     if (B > 128 || blocksize != 64 || (K % 64) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) || (align & 15u) != 0 ||
         M > (int64_t(1) << 30) || K > (int64_t(1) << 24)) {
-        set_error("fp4_hip_gemm_wide_nf4: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..128 rows, blocksize 64, "
+        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..128 rows, blocksize 64, "
                   "K %% 64 == 0, fp16 / bf16, 16-byte aligned x and packed); use dequant + GEMM",
-                  (long long)B, (long long)M, (long long)K, blocksize, dtype);
+                  name, (long long)B, (long long)M, (long long)K, blocksize, dtype);
         return FP4_ERR_UNSUPPORTED;
     }
     if (M == 0 || B == 0) return FP4_OK;
     if (!x || !packed || !absmax || !out) {
-        set_error("fp4_hip_gemm_wide_nf4: null pointer");
+        set_error("%s: null pointer", name);
         return FP4_ERR_INVALID_ARGUMENT;
     }
-    // 1..16 rows on a K the 2..16-row kernel covers: that kernel, bit for bit
-    if (B <= 16 && K % 512 == 0) return fp4_hip_gemm_small_nf4(x, packed, absmax, bias, out, B, M, K, blocksize, dtype, stream);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    // 1..16 rows on a K the 2..16-row kernel covers: that kernel, bit for bit
+    if (B <= 16 && K % 512 == 0) {
+        if (!fused) return fp4_hip_gemm_small_nf4(x, packed, absmax, bias, out, B, M, K, blocksize, dtype, stream);
+        gemm_small_nf4_fused_launch(dtype, x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s);
+        return check_launch(name);
+    }
     const int esize = 2;
+    const int64_t M_out = (mode & kModeSiluMulPairs) ? M / 2 : M;
     // 65..128 rows: two even chunks of at most 64, one pass over the weight each
     const int64_t first = B > 64 ? (B + 1) / 2 : B;
     for (int64_t b0 = 0; b0 < B; b0 += first) {
         const int rows = (int)(B - b0 < first ? B - b0 : first);
-        const void *xc = static_cast<const uint8_t *>(x) + b0 * K * esize;
-        void *oc = static_cast<uint8_t *>(out) + b0 * M * esize;
+        const WideNf4Args a{static_cast<const uint8_t *>(x) + b0 * K * esize,
+                            packed,
+                            absmax,
+                            bias,
+                            residual ? static_cast<const uint8_t *>(residual) + b0 * M_out * esize : nullptr,
+                            static_cast<uint8_t *>(out) + b0 * M_out * esize,
+                            rows,
+                            (int)M,
+                            (int)K,
+                            mode,
+                            s};
         if (dtype == FP4_DTYPE_F16)
-            dispatch_wide_nf4<FP4_DTYPE_F16>(xc, packed, absmax, bias, oc, rows, (int)M, (int)K, s);
+            fused ? dispatch_wide_nf4<FP4_DTYPE_F16, true>(a) : dispatch_wide_nf4<FP4_DTYPE_F16, false>(a);
         else
-            dispatch_wide_nf4<FP4_DTYPE_BF16>(xc, packed, absmax, bias, oc, rows, (int)M, (int)K, s);
+            fused ? dispatch_wide_nf4<FP4_DTYPE_BF16, true>(a) : dispatch_wide_nf4<FP4_DTYPE_BF16, false>(a);
     }
-    return check_launch("fp4_hip_gemm_wide_nf4");
+    return check_launch(name);
+}
+
+}  // namespace
+}  // namespace fp4
+
+extern "C" int fp4_hip_gemm_wide_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
+                                     int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
+    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_wide_nf4", false, x, packed, absmax, bias, nullptr, out, B, M, K, blocksize, dtype, 0,
+                                    stream);
+}
+
+extern "C" int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                      void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
+    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
+        fp4::set_error("fp4_hip_gemm_fused_nf4: unknown epilogue %d", epilogue);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_fused_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
+                                    epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
 }

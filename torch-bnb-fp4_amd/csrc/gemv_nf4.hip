@@ -16,6 +16,11 @@
 //       addresses of a wave are spread over 2 KiB, so reads can collide in banks).
 // Irregular shapes (K % 32 != 0, blocksize not a power of two >= 32 dividing K, unaligned operands) run the FP4 generic
 // kernel of gemv_fp4.hip with the NF4 table as its argument.
+//
+// Fused decode epilogues (fp4_hip_gemv_fused_nf4): the FUSED instantiations take a residual and the `mode` of gemv_fp4.hip.  The
+// two half-waves of a wave already hold rows 2j and 2j + 1, row_base and the rows per workgroup are even, so a gate row and its
+// up row meet in one wave (KSPLIT == 1) or in neighbouring s_part rows (KSPLIT > 1) and the pair never straddles a workgroup.
+// The epilogue is a compile-time choice: the plain entry point keeps the instantiations it had, instruction for instruction.
 #include <atomic>
 
 #include "gemv_common.h"
@@ -42,19 +47,38 @@ __device__ __forceinline__ void load_x8(const void *x, int64_t i8, f32x4 &a, f32
     }
 }
 
+// `residual` may alias `out`: the element is read before it is written, by the same lane
 template <int DT>
-__device__ __forceinline__ void store_nf4_row(void *out, const void *bias, int row, float sum) {
+__device__ __forceinline__ void store_nf4_row(void *out, const void *bias, const void *residual, int row, float sum) {
     if constexpr (DT == FP4_DTYPE_F32) {
-        reinterpret_cast<float *>(out)[row] = bias ? sum + reinterpret_cast<const float *>(bias)[row] : sum;
+        float t = bias ? sum + reinterpret_cast<const float *>(bias)[row] : sum;
+        if (residual) t += reinterpret_cast<const float *>(residual)[row];
+        reinterpret_cast<float *>(out)[row] = t;
     } else {
-        store_row<DT>(reinterpret_cast<uint16_t *>(out), reinterpret_cast<const uint16_t *>(bias), nullptr, row, sum);
+        store_row<DT>(reinterpret_cast<uint16_t *>(out), reinterpret_cast<const uint16_t *>(bias),
+                      reinterpret_cast<const uint16_t *>(residual), row, sum);
     }
 }
 
-template <int DT, int KSPLIT, int G, int ITERS, bool PAIR>
+// the plain kernels promise the compiler that nothing else points into `out`; with a residual that may alias it they cannot
+template <bool FUSED>
+struct OutPtr {
+    typedef void *__restrict__ type;
+};
+template <>
+struct OutPtr<true> {
+    typedef void *type;
+};
+
+// FUSED = false: `residual` and `mode` are ignored (fp4_hip_gemv_nf4).  FUSED = true: the row epilogue adds the residual, and with
+// kModeSiluMulPairs (16-bit DT only, M even) rows (2i, 2i + 1) are a gate / up pair and out[i] = silu(gate_i) * up_i (+ residual[i]).
+template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED>
 __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ x, const uint8_t *__restrict__ W,
                                                        const float *__restrict__ absmax, const void *__restrict__ bias,
-                                                       void *__restrict__ out, int M, int K, int bs_shift) {
+                                                       typename OutPtr<FUSED>::type out, int M, int K, int bs_shift,
+                                                       const void *residual_arg, int mode) {  // new arguments last: the plain kernels keep their argument layout
+    const void *residual = FUSED ? residual_arg : nullptr;
+    [[maybe_unused]] const bool gated = FUSED && DT != FP4_DTYPE_F32 && (mode & kModeSiluMulPairs);
     constexpr int RG = 4 / KSPLIT;
     constexpr int kRowsPerBlock = 2 * RG * ITERS;
     constexpr int kBand = G * 32 * KSPLIT;  // chunks of K covered per pass
@@ -149,39 +173,74 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
         v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));  // 32-lane row sum
         if constexpr (KSPLIT == 1) {
             const int row = row_base + rowi[it];
-            if (l32 == 0 && row < M) store_nf4_row<DT>(out, bias, row, v);
+            if constexpr (FUSED && DT != FP4_DTYPE_F32) {
+                if (gated) {
+                    // the two half-waves hold the gate row (even, lanes 0..31) and the up row (odd) of one pair; M is even
+                    const float up = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
+                    if (lane == 0 && row < M)
+                        store_silu_mul<DT>(reinterpret_cast<uint16_t *>(out), reinterpret_cast<const uint16_t *>(bias),
+                                           reinterpret_cast<const uint16_t *>(residual), row >> 1, v, up);
+                    continue;
+                }
+            }
+            if (l32 == 0 && row < M) store_nf4_row<DT>(out, bias, residual, row, v);
         } else {
             if (l32 == 0) s_part[rowi[it]][kw] = v;
         }
     }
     if constexpr (KSPLIT > 1) {
         __syncthreads();
+        if constexpr (FUSED && DT != FP4_DTYPE_F32) {
+            if (gated) {
+                if (tid < kRowsPerBlock / 2) {  // rows 2 * tid (gate) and 2 * tid + 1 (up) of this workgroup; row_base and M are even
+                    float g = 0.0f, u = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < KSPLIT; ++k) g += s_part[2 * tid][k], u += s_part[2 * tid + 1][k];
+                    const int row = row_base + 2 * tid;
+                    if (row < M)
+                        store_silu_mul<DT>(reinterpret_cast<uint16_t *>(out), reinterpret_cast<const uint16_t *>(bias),
+                                           reinterpret_cast<const uint16_t *>(residual), row >> 1, g, u);
+                }
+                return;
+            }
+        }
         if (tid < kRowsPerBlock) {
             float t = 0.0f;
 #pragma unroll
             for (int k = 0; k < KSPLIT; ++k) t += s_part[tid][k];
             const int row = row_base + tid;
-            if (row < M) store_nf4_row<DT>(out, bias, row, t);
+            if (row < M) store_nf4_row<DT>(out, bias, residual, row, t);
         }
     }
 }
 
 std::atomic<int> g_gemv_nf4_variant{-1};  // sweep hook: 0 = 16-entry table, 1 = pair table, -1 = default
 
-template <int DT, int KSPLIT, int G, int ITERS>
-void launch_nf4(bool pair, const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int M, int K,
-                int bs_shift, hipStream_t stream) {
+struct Nf4Args {
+    const void *x;
+    const uint8_t *W;
+    const float *absmax;
+    const void *bias, *residual;
+    void *out;
+    int M, K, bs_shift, mode;
+    hipStream_t stream;
+};
+
+template <int DT, int KSPLIT, int G, int ITERS, bool FUSED>
+void launch_nf4(bool pair, const Nf4Args &a) {
     constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
-    const dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block)), block(256);
+    const dim3 grid((unsigned)((a.M + rows_per_block - 1) / rows_per_block)), block(256);
     if (pair)
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true>), grid, block, 0, stream, x, W, absmax, bias, out, M, K, bs_shift);
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED>), grid, block, 0, a.stream, a.x, a.W, a.absmax, a.bias,
+                           a.out, a.M, a.K, a.bs_shift, a.residual, a.mode);
     else
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false>), grid, block, 0, stream, x, W, absmax, bias, out, M, K, bs_shift);
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED>), grid, block, 0, a.stream, a.x, a.W, a.absmax, a.bias,
+                           a.out, a.M, a.K, a.bs_shift, a.residual, a.mode);
 }
 
-template <int DT>
-void dispatch_nf4(bool pair, const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int M, int K,
-                  int bs_shift, hipStream_t stream) {
+template <int DT, bool FUSED>
+void dispatch_nf4(bool pair, const Nf4Args &a) {
+    const int M = a.M, K = a.K;
     const int C = K >> 5;
     const int ks = C <= 32 ? 1 : (C <= 64 ? 2 : 4);
     // the x slice is re-read by every workgroup: amortise it over up to 4 row pairs per lane while >= ~256 workgroups remain
@@ -190,9 +249,9 @@ void dispatch_nf4(bool pair, const void *x, const uint8_t *W, const float *absma
     while (iters < 4 && M / (2 * (4 / ks) * iters * 2) >= 256) iters *= 2;
 #define NF4_ITERS(KS, GG)                                                                                          \
     switch (iters) {                                                                                               \
-        case 1: return launch_nf4<DT, KS, GG, 1>(pair, x, W, absmax, bias, out, M, K, bs_shift, stream);           \
-        case 2: return launch_nf4<DT, KS, GG, 2>(pair, x, W, absmax, bias, out, M, K, bs_shift, stream);           \
-        default: return launch_nf4<DT, KS, GG, 4>(pair, x, W, absmax, bias, out, M, K, bs_shift, stream);          \
+        case 1: return launch_nf4<DT, KS, GG, 1, FUSED>(pair, a);                                                  \
+        case 2: return launch_nf4<DT, KS, GG, 2, FUSED>(pair, a);                                                  \
+        default: return launch_nf4<DT, KS, GG, 4, FUSED>(pair, a);                                                 \
     }
     if (C <= 32) { NF4_ITERS(1, 1) }
     if (C <= 64) { NF4_ITERS(2, 1) }
@@ -207,46 +266,80 @@ void set_gemv_nf4_variant(int v) { g_gemv_nf4_variant.store(v, std::memory_order
 
 }  // namespace fp4
 
-extern "C" int fp4_hip_gemv_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out, int64_t M,
-                                int64_t K, int blocksize, int dtype, void *stream) {
-    using namespace fp4;
+namespace fp4 {
+namespace {
+
+// fused = false: fp4_hip_gemv_nf4 (irregular shapes run the generic kernel).  fused = true: fp4_hip_gemv_fused_nf4 (the fast path or
+// FP4_ERR_UNSUPPORTED with nothing launched).  `name` is the entry point the messages speak for.
+int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
+                   const void *residual, void *out, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream) {
     if (M < 0 || K < 0 || (K & 1) || blocksize < 2 || (blocksize & 1)) {
-        set_error("fp4_hip_gemv_nf4: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", (long long)M,
-                  (long long)K, blocksize);
+        set_error("%s: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", name, (long long)M, (long long)K,
+                  blocksize);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     if (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16 && dtype != FP4_DTYPE_F32) {
-        set_error("fp4_hip_gemv_nf4: unsupported dtype %d", dtype);
+        set_error("%s: unsupported dtype %d", name, dtype);
         return FP4_ERR_UNSUPPORTED;
+    }
+    if ((mode & kModeSiluMulPairs) && (M & 1)) {
+        set_error("%s: the gate|up epilogue needs an even row count, got M=%lld", name, (long long)M);
+        return FP4_ERR_INVALID_ARGUMENT;
     }
     if (M == 0) return FP4_OK;
     if (!out || (K > 0 && (!x || !packed || !absmax))) {
-        set_error("fp4_hip_gemv_nf4: null pointer");
+        set_error("%s: null pointer", name);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     if (M > (int64_t(1) << 30) || K > (int64_t(1) << 30)) {
-        set_error("fp4_hip_gemv_nf4: M=%lld K=%lld too large", (long long)M, (long long)K);
+        set_error("%s: M=%lld K=%lld too large", name, (long long)M, (long long)K);
         return FP4_ERR_UNSUPPORTED;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int bs_shift = ilog2_exact(blocksize);
     const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
     const bool fast = K > 0 && (K % 32) == 0 && bs_shift >= 5 && (K % blocksize) == 0 && (align & 15u) == 0;
+    if (fused && (!fast || ((mode & kModeSiluMulPairs) && dtype == FP4_DTYPE_F32))) {
+        set_error("%s: the fused epilogue is not available for M=%lld K=%lld blocksize=%d dtype=%d epilogue=%d (needs K %% 32 == 0, a "
+                  "power-of-two blocksize >= 32 that divides K, 16-byte aligned x and packed; the gate|up epilogue a 16-bit dtype); run "
+                  "the plain GEMV and apply the epilogue separately",
+                  name, (long long)M, (long long)K, blocksize, dtype, (mode & kModeSiluMulPairs) ? 1 : 0);
+        return FP4_ERR_UNSUPPORTED;
+    }
     if (fast) {
         const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
+        const Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s};
         switch (dtype) {
             case FP4_DTYPE_F16:
-                dispatch_nf4<FP4_DTYPE_F16>(pair, x, packed, absmax, bias, out, (int)M, (int)K, bs_shift, s);
+                fused ? dispatch_nf4<FP4_DTYPE_F16, true>(pair, a) : dispatch_nf4<FP4_DTYPE_F16, false>(pair, a);
                 break;
             case FP4_DTYPE_BF16:
-                dispatch_nf4<FP4_DTYPE_BF16>(pair, x, packed, absmax, bias, out, (int)M, (int)K, bs_shift, s);
+                fused ? dispatch_nf4<FP4_DTYPE_BF16, true>(pair, a) : dispatch_nf4<FP4_DTYPE_BF16, false>(pair, a);
                 break;
             default:
-                dispatch_nf4<FP4_DTYPE_F32>(pair, x, packed, absmax, bias, out, (int)M, (int)K, bs_shift, s);
+                fused ? dispatch_nf4<FP4_DTYPE_F32, true>(pair, a) : dispatch_nf4<FP4_DTYPE_F32, false>(pair, a);
                 break;
         }
     } else {
         gemv_generic_table(x, packed, absmax, bias, out, M, K, blocksize, dtype, FP4_TABLE_NF4, s);
     }
-    return check_launch("fp4_hip_gemv_nf4");
+    return check_launch(name);
+}
+
+}  // namespace
+}  // namespace fp4
+
+extern "C" int fp4_hip_gemv_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out, int64_t M,
+                                int64_t K, int blocksize, int dtype, void *stream) {
+    return fp4::gemv_nf4_entry("fp4_hip_gemv_nf4", false, x, packed, absmax, bias, nullptr, out, M, K, blocksize, dtype, 0, stream);
+}
+
+extern "C" int fp4_hip_gemv_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                      void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
+    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
+        fp4::set_error("fp4_hip_gemv_fused_nf4: unknown epilogue %d", epilogue);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    return fp4::gemv_nf4_entry("fp4_hip_gemv_fused_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
+                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
 }

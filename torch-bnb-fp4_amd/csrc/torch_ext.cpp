@@ -586,6 +586,62 @@ torch::Tensor gemm_small_fp4_fused(torch::Tensor A, torch::Tensor B, torch::Tens
     return out;
 }
 
+// the NF4 twins of gemv_fp4_fused / gemm_small_fp4_fused (fp4_hip_gemv_fused_nf4 / fp4_hip_gemm_fused_nf4): A [.., K] with `rows`
+// rows in total -> [.., m] or, for the gated epilogue, [.., m / 2].  One allocation (the output), no sync: capturable.
+torch::Tensor nf4_fused_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
+                             int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
+                             const c10::optional<torch::Tensor> &residual, int epilogue) {
+    check_gpu_contiguous(A, "A");
+    check_gpu_contiguous(B, "B");
+    check_gpu_contiguous(absmax, "absmax");
+    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
+    const int64_t m = Bshape[0], k = Bshape[1];
+    TORCH_CHECK(epilogue == FP4_EPILOGUE_NONE || epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS, op, ": unknown epilogue ", epilogue);
+    const int64_t m_out = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? m / 2 : m;
+    TORCH_CHECK(A.dim() >= 1 && k > 0 && A.size(-1) == k, op, ": last dim of the activation must be in_features = ", k);
+    const int64_t rows = A.numel() / k;
+    TORCH_CHECK(!gemv || rows == 1, op, " is batch-1 only: activation has ", A.numel(), " elements, in_features is ", k);
+    TORCH_CHECK(rows >= 1 && rows <= 128, op, " covers 1..128 activation rows, got ", rows);
+    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
+    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
+    TORCH_CHECK(B.device() == A.device() && absmax.device() == A.device(), "all tensors must be on one device");
+    const int dt = to_fp4_dtype(A.scalar_type(), op);
+    auto shape = A.sizes().vec();
+    shape.back() = m_out;
+    torch::Tensor out = torch::empty(shape, A.options());
+    const void *bias_ptr = nullptr, *res_ptr = nullptr;
+    torch::Tensor bias_c, res_c;
+    if (bias.has_value()) {
+        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
+                    "] tensor of the activation dtype");
+        bias_c = bias->contiguous();
+        bias_ptr = bias_c.data_ptr();
+    }
+    if (residual.has_value()) {
+        TORCH_CHECK(residual->is_cuda() && residual->numel() == rows * m_out && residual->scalar_type() == A.scalar_type() &&
+                        residual->device() == A.device(),
+                    "residual must hold ", rows * m_out, " elements of the activation dtype on the activation's device");
+        res_c = residual->contiguous();
+        res_ptr = res_c.data_ptr();
+    }
+    c10::DeviceGuard guard(A.device());
+    if (gemv)
+        check_status(fp4_hip_gemv_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(),
+                                            m, k, blocksize, dt, epilogue, current_stream(A)));
+    else
+        check_status(fp4_hip_gemm_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(),
+                                            rows, m, k, blocksize, dt, epilogue, current_stream(A)));
+    return out;
+}
+torch::Tensor gemv_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                             c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    return nf4_fused_impl("gemv_nf4_fused", true, A, B, absmax, blocksize, Bshape, bias, residual, epilogue);
+}
+torch::Tensor gemm_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                             c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    return nf4_fused_impl("gemm_nf4_fused", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue);
+}
+
 // f32 partial sums of a K-split shard: [1, m] float32 (see fp4_hip_gemv_partial)
 torch::Tensor gemv_fp4_partial(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape) {
     check_gpu_contiguous(A, "A");
@@ -735,6 +791,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("qlinear_nf4_bias", &qlinear_nf4_bias, "NF4 dequant + linear + bias: (A_in, A, absmax, M, N, blocksize, bias)");
     m.def("gemm_small_nf4", &gemm_small_nf4, "fused NF4 product for 1..16 activation rows: (A, B, absmax, blocksize, Bshape, bias|None)");
     m.def("gemm_wide_nf4", &gemm_wide_nf4, "fused NF4 product for 1..128 activation rows: (A, B, absmax, blocksize, Bshape, bias|None)");
+    m.def("gemv_nf4_fused", &gemv_nf4_fused,
+          "NF4 GEMV with a fused epilogue: (A, B, absmax, blocksize, Bshape, bias|None, residual|None, epilogue) ; epilogue 0 = bias/residual, "
+          "1 = silu(gate) * up over interleaved rows");
+    m.def("gemm_nf4_fused", &gemm_nf4_fused,
+          "fused NF4 product for 1..128 rows with an epilogue: (A, B, absmax, blocksize, Bshape, bias|None, residual|None, epilogue)");
     m.def("quantize_nf4", &quantize_nf4, "blockwise NF4 quantiser: (W, blocksize) -> (packed, absmax)");
     m.def("code_table", &code_table, "16-entry code table as a CPU float tensor");
     m.def("set_kernel_variant", &set_kernel_variant, "benchmark hook: select a kernel geometry");

@@ -31,7 +31,7 @@ from .functional import (
     quantize_nf4,
 )
 from .comm import OneShotAllReduce
-from .fused import FusedFP4Linear
+from .fused import FusedFP4Linear, FusedNF4Linear
 from .graphs import GraphedStep
 from .linear import TorchFP4Linear
 from .nn import Linear4bit, LinearFP4, LinearNF4, Params4bit, QuantState, nf4_code
@@ -74,6 +74,7 @@ __all__ = [
     "fuse_gated_mlps",
     "FusedGatedMLP",
     "FusedFP4Linear",
+    "FusedNF4Linear",
     "OneShotAllReduce",
     "GraphedStep",
     "dequantize_nf4",

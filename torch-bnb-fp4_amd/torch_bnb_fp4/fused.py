@@ -14,6 +14,9 @@ Every intermediate is rounded to the activation dtype exactly where the separate
 equals the unfused sequence bit for bit (``exp`` is the device library's, as in torch's silu).  2..128 activation rows
 (batched decode) take the same epilogues on the small-batch kernels (``fp4_hip_gemm_small_fused``); larger inputs, or shapes
 the fused kernels do not cover, run the unfused sequence through :class:`QuantData`.
+
+:class:`FusedNF4Linear` is the same layer over an NF4 weight (``fp4_hip_gemv_fused_nf4`` for one row,
+``fp4_hip_gemm_fused_nf4`` for 2..64 rows); :class:`FusedFP4Linear` itself refuses NF4 weights.
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import torch
 from torch import nn
 
 from ._ext import ext
-from .nn import QuantState, fp4_code
+from .nn import QuantState, fp4_code, nf4_code
 from .quant_data import QuantData
 
 EPILOGUE_NONE = 0
@@ -65,12 +68,24 @@ class FusedFP4Linear(nn.Module):
     ``epilogue == EPILOGUE_SILU_MUL_PAIRS``: the weight holds interleaved gate / up rows, ``forward(x)`` =
     ``silu(gate(x)) * up(x)`` with ``out_features`` = half the weight's rows."""
 
+    quant_type = "fp4"  # the code this class's kernels decode; a weight of the other code is refused
+
+    @classmethod
+    def _check_code(cls, *quant_datas) -> None:
+        for qd in quant_datas:
+            if getattr(qd, "quant_type", "fp4") != cls.quant_type:
+                raise ValueError(f"{cls.__name__} runs the {cls.quant_type.upper()} fused-epilogue kernels; an "
+                                 f"{getattr(qd, 'quant_type', 'fp4').upper()} weight cannot be decoded by them")
+
+    @classmethod
+    def _code(cls) -> torch.Tensor:
+        return fp4_code()
+
     def __init__(self, quant_data: QuantData, epilogue: int = EPILOGUE_NONE):
         super().__init__()
         if epilogue not in (EPILOGUE_NONE, EPILOGUE_SILU_MUL_PAIRS):
             raise ValueError(f"unknown epilogue {epilogue}")
-        if getattr(quant_data, "nf4", False):
-            raise ValueError("FusedFP4Linear runs the FP4 fused-epilogue kernels; an NF4 weight cannot be decoded by them")
+        self._check_code(quant_data)
         if epilogue == EPILOGUE_SILU_MUL_PAIRS and quant_data.M % 2:
             raise ValueError("the gate|up epilogue needs an even number of weight rows")
         self.quant_data = quant_data
@@ -88,7 +103,7 @@ class FusedFP4Linear(nn.Module):
     def from_packed(cls, packed, absmax, shape, blocksize: int = 64, bias: Optional[torch.Tensor] = None,
                     epilogue: int = EPILOGUE_NONE, dtype: torch.dtype = torch.float16) -> "FusedFP4Linear":
         """``dtype``: the dtype the weight was quantised from (checkpoint metadata only; the kernels follow the activation)."""
-        state = QuantState(absmax, shape, fp4_code().to(packed.device), blocksize, dtype)
+        state = QuantState(absmax, shape, cls._code().to(packed.device), blocksize, dtype, cls.quant_type)
         return cls(QuantData(packed, state, state.shape, original_lin=None, bias=bias), epilogue)
 
     @classmethod
@@ -105,16 +120,14 @@ class FusedFP4Linear(nn.Module):
     def from_linear(cls, layer) -> "FusedFP4Linear":
         """From a :class:`TorchFP4Linear` (shares its packed weight)."""
         qd = layer.quant_data
-        if qd.nf4:
-            raise ValueError("FusedFP4Linear runs the FP4 fused-epilogue kernels; an NF4 weight cannot be decoded by them")
+        cls._check_code(qd)
         return cls.from_packed(qd.A, qd.absmax, (qd.M, qd.N), qd.blocksize, qd.bias, dtype=getattr(qd.quant_state, "dtype", torch.float16))
 
     @classmethod
     def gate_up(cls, gate_layer, up_layer) -> "FusedFP4Linear":
         """From the gate and up :class:`TorchFP4Linear` of a gated MLP."""
         g, u = gate_layer.quant_data, up_layer.quant_data
-        if g.nf4 or u.nf4:
-            raise ValueError("FusedFP4Linear runs the FP4 fused-epilogue kernels; an NF4 weight cannot be decoded by them")
+        cls._check_code(g, u)
         if (g.M, g.N, g.blocksize) != (u.M, u.N, u.blocksize):
             raise ValueError("gate_up() needs two projections of the same shape and blocksize")
         return cls.gate_up_from_packed((g.A, g.absmax), (u.A, u.absmax), (g.M, g.N), g.blocksize, g.bias, u.bias)
@@ -178,3 +191,53 @@ class FusedFP4Linear(nn.Module):
     def extra_repr(self) -> str:
         kind = "silu(gate)*up" if self.epilogue == EPILOGUE_SILU_MUL_PAIRS else "linear(+residual)"
         return f"in_features={self.in_features}, out_features={self.out_features}, epilogue={kind}"
+
+
+class FusedNF4Linear(FusedFP4Linear):
+    """:class:`FusedFP4Linear` over an NF4 weight: same constructors and ``forward(x, residual=None)``.
+
+    One activation row runs ``fp4_hip_gemv_fused_nf4``; 2..64 rows of fp16 / bf16 against a blocksize-64 weight with
+    ``K % 64 == 0`` run ``fp4_hip_gemm_fused_nf4`` (the range in which the one-pass NF4 kernels are ahead of dequant + GEMM,
+    profiles/nf4_wide_batch.json); everything else, 65+ rows included, runs the unfused sequence through :class:`QuantData`
+    and torch's silu / mul / add.  An op that reports a shape as not covered is not tried again.  One measured cell is left out
+    of the fused residual add: more than 32 rows against rows of 8192 and more weights with the plain epilogue (a down
+    projection; profiles/nf4_fused_epilogues.json: 55.5 vs 56.5 us at 64 rows, inside the replay-to-replay ranges) - there the
+    op runs without the residual and torch adds it, the same bits."""
+
+    quant_type = "nf4"
+
+    @classmethod
+    def _code(cls) -> torch.Tensor:
+        return nf4_code()
+
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        qd = self.quant_data
+        K = x.shape[-1]
+        if not qd.compute_dtype_set and x.numel():
+            qd.set_compute_type(x)
+            if qd.bias is not None:
+                self._buffers["bias"] = qd.bias  # the buffer follows the cast to the compute dtype
+        if (self._fused_ok and x.numel() == K and K == self.in_features and x.ndim in (2, 3) and K % qd.blocksize == 0
+                and x.dtype == qd.o_type):
+            if not x.is_contiguous():
+                x = x.contiguous()
+            try:
+                return ext.gemv_nf4_fused(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual, self.epilogue)
+            except RuntimeError as exc:
+                if "not available" not in str(exc):
+                    raise
+                self._fused_ok = False  # shape outside the fused kernel's coverage: unfused sequence from now on
+        rows = x.numel() // K if K else 0
+        if (self._small_ok and 2 <= rows <= 64 and K == self.in_features and x.dtype == qd.o_type and x.dtype in (torch.float16, torch.bfloat16)
+                and qd.blocksize == 64 and K % 64 == 0):
+            # the one cell in which the fused residual add measured no gain: the add stays torch's (T(t + r) either way)
+            in_kernel = residual is not None and not (self.epilogue == EPILOGUE_NONE and rows > 32 and K >= 8192)
+            try:  # batched decode: the same epilogues on the matrix-core kernels
+                y = ext.gemm_nf4_fused(x.contiguous(), qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias,
+                                       residual if in_kernel else None, self.epilogue)
+                return y if in_kernel or residual is None else y + residual
+            except RuntimeError as exc:
+                if "not covered" not in str(exc):
+                    raise
+                self._small_ok = False
+        return self._unfused(x, residual)

@@ -44,7 +44,7 @@ def _bnb_entries(prefix: str, packed, absmax, code, blocksize: int, shape, dtype
     out = {
         prefix + "weight": packed.detach().cpu().reshape(-1, 1),
         prefix + "weight.absmax": absmax.detach().float().cpu(),
-        prefix + "weight.quant_map": code.detach().float().cpu(),
+        prefix + "weight.quant_map": code.detach().float().cpu().clone(),  # a gate|up pair shares one code tensor: one copy per entry
         prefix + _STATE_KEYS[quant_type]: _pack_json(meta),
     }
     if bias is not None:
@@ -60,7 +60,7 @@ def fp4_linear_to_bnb_state(layer: TorchFP4Linear, prefix: str = "") -> Dict[str
 
 
 def fused_linear_to_bnb_state(layer, prefix: str = "", pair_prefixes=None, dtype=None) -> Dict[str, torch.Tensor]:
-    """A :class:`~torch_bnb_fp4.fused.FusedFP4Linear` in bitsandbytes' layout.  A plain one (residual epilogue) is one entry under
+    """A :class:`~torch_bnb_fp4.fused.FusedFP4Linear` (or its NF4 subclass, written under the ``__nf4`` key) in bitsandbytes' layout.  A plain one (residual epilogue) is one entry under
     ``prefix``; a gate|up one is DE-INTERLEAVED into the two projections it was built from and written under ``pair_prefixes``
     (the rows are a load-time permutation of the bnb bytes, not a new format) - without names for the pair it cannot be saved."""
     from .fused import EPILOGUE_SILU_MUL_PAIRS, deinterleave_rows
@@ -69,7 +69,7 @@ def fused_linear_to_bnb_state(layer, prefix: str = "", pair_prefixes=None, dtype
     if dtype is None:  # the dtype the weight was quantised from, as its quant_state recorded it
         dtype = getattr(qd.quant_state, "dtype", torch.float16)
     if layer.epilogue != EPILOGUE_SILU_MUL_PAIRS:
-        return _bnb_entries(prefix, qd.A, qd.absmax, qd.code, qd.blocksize, (qd.M, qd.N), dtype, layer.bias)
+        return _bnb_entries(prefix, qd.A, qd.absmax, qd.code, qd.blocksize, (qd.M, qd.N), dtype, layer.bias, qd.quant_type)
     if not pair_prefixes:
         raise ValueError(f"{prefix or 'layer'}: a gate|up FusedFP4Linear can only be saved as its two projections; it is not inside a "
                          "FusedGatedMLP that remembers their names - save the unfused model (before fuse_gated_mlps) instead")
@@ -77,8 +77,8 @@ def fused_linear_to_bnb_state(layer, prefix: str = "", pair_prefixes=None, dtype
     bias = layer.bias
     bg = None if bias is None else bias.reshape(-1, 2)[:, 0].contiguous()
     bu = None if bias is None else bias.reshape(-1, 2)[:, 1].contiguous()
-    out = _bnb_entries(pair_prefixes[0], pg, ag, qd.code, qd.blocksize, shape, dtype, bg)
-    out.update(_bnb_entries(pair_prefixes[1], pu, au, qd.code, qd.blocksize, shape, dtype, bu))
+    out = _bnb_entries(pair_prefixes[0], pg, ag, qd.code, qd.blocksize, shape, dtype, bg, qd.quant_type)
+    out.update(_bnb_entries(pair_prefixes[1], pu, au, qd.code, qd.blocksize, shape, dtype, bu, qd.quant_type))
     return out
 
 

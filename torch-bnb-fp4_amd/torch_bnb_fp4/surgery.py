@@ -166,13 +166,14 @@ def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = F
 
 class FusedGatedMLP(nn.Module):
     """``down(silu(gate(x)) * up(x))`` with the gate and up projections as ONE launch whose epilogue applies the activation
-    and the product (:mod:`torch_bnb_fp4.fused`); what :func:`fuse_gated_mlps` puts in place of a Llama / Mistral style MLP."""
+    and the product (:mod:`torch_bnb_fp4.fused`); what :func:`fuse_gated_mlps` puts in place of a Llama / Mistral style MLP.
+    An NF4 gate / up pair becomes a :class:`~torch_bnb_fp4.fused.FusedNF4Linear`; a pair of different codes is refused."""
 
     def __init__(self, gate: TorchFP4Linear, up: TorchFP4Linear, down: nn.Module, names=("gate_proj", "up_proj")):
         super().__init__()
-        from .fused import FusedFP4Linear
+        from .fused import FusedFP4Linear, FusedNF4Linear
 
-        self.gate_up = FusedFP4Linear.gate_up(gate, up)
+        self.gate_up = (FusedNF4Linear if gate.quant_data.nf4 and up.quant_data.nf4 else FusedFP4Linear).gate_up(gate, up)
         self.down_proj = down
         # the two projections' names in the unfused model: save_fp4_model writes the interleaved weight back under them
         # (bitsandbytes layout, one entry per projection), so that the file loads into a fresh, unfused model
@@ -183,21 +184,24 @@ class FusedGatedMLP(nn.Module):
         return self.down_proj(self.gate_up(x))
 
 
-def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_proj", down: str = "down_proj", act: str = "act_fn") -> int:
+def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_proj", down: str = "down_proj", act: str = "act_fn",
+                    nf4: bool = False) -> int:
     """After :func:`recursively_replace_with_fp4_linear`: replace every sub-module that looks like a SiLU-gated MLP (children
     ``gate`` / ``up`` / ``down`` with the first two :class:`TorchFP4Linear` of equal shape, activation ``act`` a SiLU) by a
     :class:`FusedGatedMLP`.  Single-token calls then pay one launch for gate + up + activation + product instead of four; other
-    shapes run the unfused sequence.  Returns how many were replaced.  Not in the reference (its surface stops at the Linear)."""
+    shapes run the unfused sequence.  Returns how many were replaced.  Not in the reference (its surface stops at the Linear).
+    NF4 MLPs are left alone unless ``nf4=True`` (then their gate / up pair becomes a ``FusedNF4Linear``); a pair whose two
+    projections use different codes is never fused."""
     count = 0
     for name, child in list(module.named_children()):
         g, u, d, a = (getattr(child, n, None) for n in (gate, up, down, act))
         silu = isinstance(a, nn.SiLU) or "silu" in type(a).__name__.lower() or a is nn.functional.silu
         if (isinstance(g, TorchFP4Linear) and isinstance(u, TorchFP4Linear) and isinstance(d, nn.Module) and silu
-                and not (g.quant_data.nf4 or u.quant_data.nf4)  # the gate|up epilogue kernels decode FP4 only: NF4 stays unfused
+                and g.quant_data.nf4 == u.quant_data.nf4 and (nf4 or not g.quant_data.nf4)  # NF4 pairs on request, mixed pairs never
                 and (g.quant_data.M, g.quant_data.N, g.quant_data.blocksize) == (u.quant_data.M, u.quant_data.N, u.quant_data.blocksize)
                 ):
             module._modules[name] = FusedGatedMLP(g, u, d, names=(gate, up))
             count += 1
         else:
-            count += fuse_gated_mlps(child, gate, up, down, act)
+            count += fuse_gated_mlps(child, gate, up, down, act, nf4)
     return count
