@@ -298,6 +298,42 @@ FP4_HIP_API int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, con
                                        void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
 
 /*
+ * LoRA adapters beside an NF4 weight (QLoRA serving; an adapter cannot be merged into 4-bit weights without re-quantising them):
+ *   y = W_nf4 x + B (s * A x)        A : T[R, K],  B : T[M, R],  s = lora_alpha / r.        Not in the reference.
+ * Two steps, both accumulated in f32 in a fixed order (deterministic, no atomics), neither allocating nor synchronising (capturable).
+ * Additions to ABI version 7.
+ *
+ * fp4_hip_lora_down: the down projection,
+ *   t[b][j] = scale[j] * sum_k A[j][k] x[b][k],     written as f32 and never rounded to T.
+ * x : T[Bt, K], A : T[R, K] row-major, scale : float[R] (one factor per adapter row, so stacked adapters may differ), t : float[Bt, R].
+ * Covered: 1 <= Bt <= 64, R % 8 == 0 with 8 <= R <= 256 (pad A with zero rows), K % 8 == 0 (K <= 2^24), fp16 / bf16 / f32,
+ * x and A 16-byte aligned.  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, t untouched.  FP4_OK without a launch for Bt == 0.
+ *
+ * fp4_hip_gemv_lora_nf4 / fp4_hip_gemm_lora_nf4: fp4_hip_gemv_fused_nf4 / fp4_hip_gemm_fused_nf4 with the adapter term
+ *   delta[b][r] = sum_j f32(lora_B[r][j]) * t[b][j]
+ * added to the kernel's f32 row sum BEFORE anything is rounded (sum' = sum + delta, one f32 add); everything after that is the
+ * epilogue of the plain entry point, unchanged:
+ *   batch 1 (gemv):  T(sum'), then T(+ bias), then T(+ residual);         2+ rows (gemm):  T(sum' + bias), then T(+ residual);
+ *   EPILOGUE_SILU_MUL_PAIRS: the same change to the gate row and to the up row before their rounding.
+ * That is one rounding fewer than adding a separately rounded adapter output.  With lora_B == 0 or t == 0 the result equals the plain
+ * fused entry point's, value for value.  lora_B : T[M, R] row-major over the weight's own row order (for a gate|up weight: rows
+ * interleaved like the weight's), t : float[B, R] as written by fp4_hip_lora_down (float[R] for the GEMV), R as above.
+ * Covered: what fp4_hip_gemv_fused_nf4 covers (all three dtypes for EPILOGUE_NONE, fp16 / bf16 for the gated one), respectively
+ * what fp4_hip_gemm_fused_nf4 covers up to 64 rows; R % 8 == 0 with 8 <= R <= 256; lora_B and t 16-byte aligned.  Everything else:
+ * FP4_ERR_UNSUPPORTED, nothing launched, out untouched - the caller runs the plain fused op and adds the adapter separately.
+ * Unknown epilogue, the gated one with an odd M ("even row count"), a negative size: FP4_ERR_INVALID_ARGUMENT.  FP4_OK without a
+ * launch for M == 0 (or B == 0).  `residual` may alias `out`.
+ */
+FP4_HIP_API int fp4_hip_lora_down(const void *x, const void *A, const float *scale, float *t, int64_t Bt, int64_t R, int64_t K, int dtype,
+                                  void *stream);
+FP4_HIP_API int fp4_hip_gemv_lora_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                      const void *lora_B, const float *t, int64_t R, void *out, int64_t M, int64_t K, int blocksize,
+                                      int dtype, int epilogue, void *stream);
+FP4_HIP_API int fp4_hip_gemm_lora_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                      const void *lora_B, const float *t, int64_t R, void *out, int64_t B, int64_t M, int64_t K,
+                                      int blocksize, int dtype, int epilogue, void *stream);
+
+/*
  * Tuning hook for benchmarks/sweeps: selects a kernel geometry by name
  * ("dequant", "gemv", "gemv_nf4" (0 = 16-entry f32 table, 1 = 256-entry pair table), "gemm_wide_nf4" (1 / 2 = 16 / 32 weight rows per workgroup), "gemm_small", "gemm_wide" = rows per workgroup of the 17..64-row kernels (1 / 2 / 3 / 4 = 16 / 32 / 64 / 128, 5 = 16 with self-contained waves; 0 = off),
  * "quantize": 1..999 = the persistent kernel with that many workgroups per CU, 1001 / 1002 / 1004 = the one-shot tiles kernel with 1 / 2 / 4 loads per lane).  variant < 0 (quantize: 0) restores the built-in heuristic.

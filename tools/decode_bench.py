@@ -9,6 +9,8 @@ QuantData / tensor-parallel modules, eagerly and replayed from a HIP graph.  Att
 and is replaced by an identity on q (the GEMV traffic is what is being measured).
 
     python tools/decode_bench.py [--model mistral7b|llama3-8b] [--layers 32] [--tokens 64] [--fuse] [--epilogues]
+    python tools/decode_bench.py --nf4 --epilogues --lora 16 [--lora-unfused]    # QLoRA serving: random rank-16 adapters on q, k, v,
+                                                                              # o, gate, up and down of every layer
     torchrun --nproc-per-node N tools/decode_bench.py --model llama3-8b      # tensor parallel: q/k/v/gate/up M-split,
                                                                               # o/down K-split + all-reduce
 
@@ -41,14 +43,18 @@ def fp4_bytes(m, k):
 
 
 def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epilogues=False, batch=1,
-                   reference_dispatch=False, allreduce="dist", lm_head=True, seed=7, lean_glue=False, tensor_parallel=None, nf4=False):
+                   reference_dispatch=False, allreduce="dist", lm_head=True, seed=7, lean_glue=False, tensor_parallel=None, nf4=False,
+                   lora=0, lora_unfused=False):
     """Builds the FP4 layers of a `cfg`-shaped decoder and returns (token_fn, h0, meta).
 
     world == 1: QuantData dispatchers (the product's single-GPU path).  world > 1: Column/RowParallelFP4Linear
     (q/k/v/gate/up M-split without a gather, o/down K-split with one f32 all-reduce each: 2 all-reduces per layer).
     fuse: q|k|v and gate|up as one launch each (row concatenation).  epilogues: on top of that, silu(gate)*up and the
     residual adds run in the GEMV epilogue (torch_bnb_fp4.fused; with nf4 the layers are FusedNF4Linear).  tensor_parallel: None = (world > 1); True builds the tensor-parallel
-    modules even for a one-rank group (bench.py's FP4_BENCH_FORCE_GROUP rehearsal of the N > 1 path through real RCCL on one GPU)."""
+    modules even for a one-rank group (bench.py's FP4_BENCH_FORCE_GROUP rehearsal of the N > 1 path through real RCCL on one GPU).
+    lora (with nf4 and epilogues, single GPU): random adapters of that rank on q, k, v, o, gate, up and down of every layer, run by
+    LoRANF4Linear (down projection + the adapter term inside the fused kernels); lora_unfused: the same adapters as torch ops around
+    FusedNF4Linear (three small products, a scale and an add per adapted Linear - what the op surface offered before)."""
     import torch_bnb_fp4 as pkg
     from torch_bnb_fp4 import parallel as par
 
@@ -84,9 +90,59 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
         return par.RowParallelFP4Linear(packed, absmax, (m, k), BS, group=group, input_is_parallel=True, allreduce=allreduce,
                                         reduce_single_rank=(world == 1))
 
+    if lora and not (nf4 and epilogues and not tp):
+        raise ValueError("lora needs nf4 and epilogues on a single GPU")
+
+    def adapters(ms, k, interleave=False):
+        """Random adapters of rank `lora` for projections of ms[i] x k stacked into one weight's rows: (A [n r, k], B [sum m, n r]
+        block-structured - rows interleaved for gate|up - and one scale per adapter row)."""
+        r, n = lora, len(ms)
+        A = (torch.randn(n * r, k, device=dev, generator=gen) / k ** 0.5).to(dtype)
+        blocks = [(torch.randn(m, r, device=dev, generator=gen) * 0.05).to(dtype) for m in ms]
+        B = torch.zeros(sum(ms), n * r, dtype=dtype, device=dev)
+        if interleave:
+            for i, blk in enumerate(blocks):
+                B[i::n, i * r:(i + 1) * r] = blk
+        else:
+            row = 0
+            for i, blk in enumerate(blocks):
+                B[row:row + blk.shape[0], i * r:(i + 1) * r] = blk
+                row += blk.shape[0]
+        return A, B, torch.full((n * r,), 2.0, device=dev)
+
+    def with_adapter(layer, ms, k, interleave=False):
+        """`layer`: a FusedNF4Linear.  Fused: LoRANF4Linear over the same weight.  Unfused: the adapter as torch ops in the activation
+        dtype (peft's sequence) added to the rows of the fused base op, then the epilogue's own ops."""
+        from torch_bnb_fp4 import fused
+
+        A, B, sc = adapters(ms, k, interleave)
+        if not lora_unfused:
+            return fused.LoRANF4Linear.from_fused(layer, A, B, sc)
+        rows = fused.FusedNF4Linear(layer.quant_data, fused.EPILOGUE_NONE)
+        At, Bt, s_t = A.t().contiguous(), B.t().contiguous(), sc.to(dtype)
+        if layer.epilogue == fused.EPILOGUE_SILU_MUL_PAIRS:
+            def run(x, residual=None):
+                y = rows(x) + ((x @ At) * s_t) @ Bt
+                y = silu(y[..., 0::2]) * y[..., 1::2]
+                return y if residual is None else y + residual
+        else:
+            def run(x, residual=None):
+                return rows(x, residual) + ((x @ At) * s_t) @ Bt
+        return run
+
+    silu = torch.nn.functional.silu
     layers = []
     for _ in range(L):
-        if epilogues and not tp:
+        if epilogues and not tp and lora:
+            from torch_bnb_fp4 import fused, parallel
+
+            F4 = fused.FusedNF4Linear
+            pq, aq, (mq, kq) = parallel.concat_rows([(*fp4_weight(mi, H), (mi, H)) for mi in (H, KV, KV)], BS)
+            ly = dict(qkv=with_adapter(F4.from_packed(pq, aq, (mq, kq), BS), [H, KV, KV], H),
+                      o=with_adapter(F4.from_packed(*fp4_weight(H, H), (H, H), BS), [H], H),
+                      gate_up=with_adapter(F4.gate_up_from_packed(fp4_weight(I, H), fp4_weight(I, H), (I, H), BS), [I, I], H, interleave=True),
+                      down=with_adapter(F4.from_packed(*fp4_weight(H, I), (H, I), BS), [H], I))
+        elif epilogues and not tp:
             from torch_bnb_fp4 import fused
 
             Fused = fused.FusedNF4Linear if nf4 else fused.FusedFP4Linear
@@ -111,7 +167,6 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
         layers.append(ly)
     head = torch.nn.Linear(H, V, bias=False, device=dev, dtype=dtype) if lm_head else None
     h0 = torch.randn(batch, H, device=dev, generator=gen).to(dtype)
-    silu = torch.nn.functional.silu
     # stand-in for attention: keeps k and v live and dependent.  Default: five small launches (two sums, add, scale, add), about what
     # RoPE + cache append + attention cost a real decoder layer in launches; lean_glue: ONE elementwise launch, and no rescale of h
     # (the weights' scales keep magnitudes bounded instead) - the floor of everything that is not an FP4 Linear.
@@ -220,6 +275,10 @@ def main():
     ap.add_argument("--allreduce", default="dist", choices=("dist", "oneshot"),
                     help="world > 1: torch.distributed all-reduce (RCCL) or the one-shot peer-slot kernel")
     ap.add_argument("--nf4", action="store_true", help="NF4 weights instead of FP4 (single GPU; with --epilogues the layers are FusedNF4Linear)")
+    ap.add_argument("--lora", type=int, default=0, metavar="R",
+                    help="with --nf4 --epilogues: random rank-R LoRA adapters on q, k, v, o, gate, up and down of every layer (LoRANF4Linear)")
+    ap.add_argument("--lora-unfused", action="store_true",
+                    help="with --lora: the same adapters as torch ops around FusedNF4Linear instead of the fused LoRA kernels")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--lean-glue", action="store_true",
                     help="attention stand-in as ONE elementwise launch and no rescale: what is left besides the FP4 Linears is minimal")
@@ -244,7 +303,8 @@ def main():
             dist.init_process_group(backend)
     dtype = getattr(torch, args.dtype)
     token, h0, meta = build_token_fn(cfg, dev, dtype, world, rank, fuse=args.fuse, epilogues=args.epilogues, batch=args.batch,
-                                     reference_dispatch=args.reference_dispatch, allreduce=args.allreduce, lean_glue=args.lean_glue, nf4=args.nf4)
+                                     reference_dispatch=args.reference_dispatch, allreduce=args.allreduce, lean_glue=args.lean_glue, nf4=args.nf4,
+                                     lora=args.lora, lora_unfused=args.lora_unfused)
 
     def barrier():
         torch.cuda.synchronize()
@@ -274,6 +334,8 @@ def main():
             "tokens_per_s": round(args.batch / best, 1), "fp4_stream_gbps_per_gpu": round(per_token_fp4 / best / 1e9, 1),
             "hbm_floor_ms_per_token_at_8TBps": round((per_token_fp4 + meta["lm_head_bytes"]) / 8e12 * 1e3, 3),
             "quant_type": "nf4" if args.nf4 else "fp4",
+            "lora_rank": args.lora, "lora_path": (None if not args.lora else "torch ops around FusedNF4Linear" if args.lora_unfused
+                                                  else "LoRANF4Linear (down projection + fused adapter term)"),
             "data": "synthetic random FP4 bytes + scales; attention replaced by identity; lm_head dense " + args.dtype,
         }), file=result_out, flush=True)
     if world > 1:

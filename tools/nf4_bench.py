@@ -26,6 +26,13 @@ this tree's library and, with --baseline-lib, through another build of it (the p
 unfused sequence they replace (the plain op, then torch's silu / mul / add) at the Mistral-7B shapes and 1 / 8 / 32 / 64 rows: the
 o projection with its residual add, gate|up with silu(g) * u, and gate|up + down with the residual; a cell is won where the fused
 form is ahead by more than both ranges together.
+
+--lora: LoRA adapters beside NF4 weights (profiles/nf4_lora.json), the four decoder shapes, 1 / 8 / 32 / 64 rows, rank 16 / 64, bf16 and
+fp16, one run on the same operands, all through the torch ops as the layers issue them: (a) lora_down + gemv_nf4_lora / gemm_nf4_lora;
+(b) the parent's best - the fused NF4 op plus the adapter as torch ops in the activation dtype, ((x @ A^T) * s) @ B^T and an add;
+(c) the fused NF4 op alone (what the adapter costs on top).  The 28672-row shape runs the gate|up epilogue, where (b) has to take the
+plain rows, add and apply silu * up itself.  A cell is won where (a) is ahead of (b) by more than both replay-to-replay ranges together.
+--lora-ranks / --lora-rows replace the rank and row lists.
 """
 import argparse
 import ctypes
@@ -281,6 +288,55 @@ def fused_epilogues(args):
                       "fused_vs_unfused": cells}))
 
 
+def lora(args):
+    dev = torch.device("cuda", 0)
+    silu = torch.nn.functional.silu
+
+    def timed(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        med, samples = time_replays(replay, args.reps, args.launches)
+        q = sorted(samples)
+        return {"us": round(med, 2), "min_us": round(q[0], 2), "max_us": round(q[-1], 2)}
+
+    rng_of = lambda t: t["max_us"] - t["min_us"]  # noqa: E731
+    gen = torch.Generator(device=dev).manual_seed(0)
+    cells = []
+    for M, K in SHAPES:
+        packed = torch.randint(0, 256, (M * K // 2,), dtype=torch.uint8, device=dev, generator=gen)
+        absmax = torch.rand(M * K // BS, device=dev, generator=gen) * 0.02 + 0.002
+        B_t = packed.view(-1, 1).t()
+        epi = 1 if M == 28672 else 0  # the gate|up weight of the decoder
+        for dtype in (torch.bfloat16, torch.float16):
+            for R in args.lora_ranks:
+                A = (torch.randn(R, K, device=dev, generator=gen) / K ** 0.5).to(dtype)
+                lB = (torch.randn(M, R, device=dev, generator=gen) * 0.05).to(dtype)
+                sc = torch.full((R,), 2.0, device=dev)
+                At, lBt, s_t = A.t().contiguous(), lB.t().contiguous(), sc.to(dtype)
+                for rows in args.lora_rows:
+                    x = torch.randn(rows, K, device=dev, generator=gen).to(dtype)
+                    base_op = pkg.ext.gemv_nf4_fused if rows == 1 else pkg.ext.gemm_nf4_fused
+                    lora_op = pkg.ext.gemv_nf4_lora if rows == 1 else pkg.ext.gemm_nf4_lora
+                    fused = lambda: lora_op(x, B_t, absmax, BS, [M, K], None, None, epi, lB, pkg.ext.lora_down(x, A, sc))  # noqa: E731
+                    free = lambda: base_op(x, B_t, absmax, BS, [M, K], None, None, epi)  # noqa: E731
+                    if epi:
+                        def unfused():
+                            y = base_op(x, B_t, absmax, BS, [M, K], None, None, 0) + ((x @ At) * s_t) @ lBt
+                            return silu(y[..., 0::2]) * y[..., 1::2]
+                    else:
+                        unfused = lambda: base_op(x, B_t, absmax, BS, [M, K], None, None, 0) + ((x @ At) * s_t) @ lBt  # noqa: E731
+                    ta, tb, tc = timed(fused), timed(unfused), timed(free)
+                    spread = rng_of(ta) + rng_of(tb)
+                    cells.append({"M": M, "K": K, "epilogue": "silu_mul" if epi else "none", "dtype": NAME[dtype], "rank": R, "rows": rows,
+                                  "fused_down_plus_lora_op": ta, "fused_nf4_op_plus_torch_adapter": tb, "fused_nf4_op_alone": tc,
+                                  "adapter_cost_us": round(ta["us"] - tc["us"], 2), "saved_us": round(tb["us"] - ta["us"], 2),
+                                  "speedup": round(tb["us"] / ta["us"], 3), "spread_us": round(spread, 2),
+                                  "fused_ahead_beyond_spread": bool(tb["us"] - ta["us"] > spread)})
+        del packed, absmax
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "revision": args.revision, "blocksize": BS, "launches_per_graph": args.launches,
+                      "reps": args.reps, "cells_won": sum(c["fused_ahead_beyond_spread"] for c in cells), "cells_total": len(cells),
+                      "cells": cells}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -290,7 +346,13 @@ def main():
     ap.add_argument("--revision", default="unknown", help="--wide-batch: the git revision the figures belong to, recorded as given")
     ap.add_argument("--fused", action="store_true", help="the fused NF4 decode epilogues (profiles/nf4_fused_epilogues.json)")
     ap.add_argument("--baseline-lib", default=None, help="--fused: another build of libtorch_bnb_fp4_hip.so to time the plain calls of, side by side")
+    ap.add_argument("--lora", action="store_true", help="LoRA adapters beside NF4 weights, fused against torch ops (profiles/nf4_lora.json)")
+    ints = lambda v: [int(i) for i in v.split(",")]  # noqa: E731
+    ap.add_argument("--lora-ranks", type=ints, default=[16, 64], help="--lora: adapter ranks (multiples of 8), comma-separated")
+    ap.add_argument("--lora-rows", type=ints, default=[1, 8, 32, 64], help="--lora: activation row counts (1..64), comma-separated")
     args = ap.parse_args()
+    if args.lora:
+        return lora(args)
     if args.fused:
         return fused_epilogues(args)
     if args.small_batch:

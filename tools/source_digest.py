@@ -11,10 +11,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join("torch-bnb-fp4_amd", "csrc")
 COMMON = [os.path.join(CSRC, "fp4_common.h"), os.path.join("torch-bnb-fp4_amd", "build.py")]  # code tables / conversions; compiler flags
 # kernel-name prefix (as it appears in profiles/rNN_traffic.json) -> the files its code object is compiled from
+LORA = os.path.join(CSRC, "lora_nf4.h")  # the adapter term of the NF4 decode kernels' LORA instantiations
 KERNEL_SOURCES = {
-    "gemm_wide_nf4": [os.path.join(CSRC, "gemm_wide_nf4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
-    "gemm_nf4": [os.path.join(CSRC, "gemm_small_nf4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
-    "gemv_nf4": [os.path.join(CSRC, "gemv_nf4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
+    "gemm_wide_nf4": [os.path.join(CSRC, "gemm_wide_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
+    "gemm_nf4": [os.path.join(CSRC, "gemm_small_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
+    "gemv_nf4": [os.path.join(CSRC, "gemv_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
+    "lora_down": [os.path.join(CSRC, "lora_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
     "quantize_nf4": [os.path.join(CSRC, "quantize_nf4.hip")] + COMMON,
     "dequant_": [os.path.join(CSRC, "dequant_fp4.hip")] + COMMON,
     "gemv": [os.path.join(CSRC, "gemv_fp4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,

@@ -23,7 +23,12 @@
 // `mode` of gemm_small_fp4.hip.  The final pass over the LDS partials has one thread per (activation row, weight row); for the
 // gate|up epilogue the thread of an even weight row also sums its odd neighbour's partials (tid + 1) and stores the pair, the odd
 // thread stores nothing.  A compile-time choice: the plain entry point keeps its instantiations instruction for instruction.
+//
+// LoRA adapter term (fp4_hip_gemm_lora_nf4, 2..16 rows with K % 512 == 0): the LORA instantiations (always FUSED) add
+// delta[n][row] = sum_j f32(lora_B[row][j]) * lora_t[n][j] (lora_nf4.h) to the thread's finished f32 sum ahead of the epilogue, and
+// to the up row's likewise; lora_t = s * A x is lora_down_kernel's f32 output.
 #include "gemv_common.h"
+#include "lora_nf4.h"
 
 namespace fp4 {
 
@@ -60,10 +65,12 @@ __device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &l
 // follow its bytes), x image row stride 128*NBW + 16, as in the FP4 kernel.
 // FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
-template <int DT, int NBW, int XS, bool FUSED>
+template <int DT, int NBW, int XS, bool FUSED, bool LORA = false>
 __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
-                                                            uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode) {
+                                                            uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode,
+                                                            const uint16_t *lora_B, const float *lora_t, int R) {
+    static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kXStride = 128 * NBW + 16;
     constexpr int kWImageBytes = 8 * 16 * kStageStride;
@@ -227,9 +234,16 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
                     float u = 0.0f;
 #pragma unroll
                     for (int w = 0; w < 8; ++w) u += s_part[w][tid + 1];
-                    if (row < M && n < B) store_small_silu_mul<DT>(out, bias, residual, n, row >> 1, M >> 1, t, u);
+                    if (row < M && n < B) {
+                        if constexpr (LORA) {
+                            t += lora_delta<DT>(lora_B + int64_t(row) * R, lora_t + n * R, R);
+                            u += lora_delta<DT>(lora_B + int64_t(row + 1) * R, lora_t + n * R, R);
+                        }
+                        store_small_silu_mul<DT>(out, bias, residual, n, row >> 1, M >> 1, t, u);
+                    }
                 }
             } else if (row < M && n < B) {
+                if constexpr (LORA) t += lora_delta<DT>(lora_B + int64_t(row) * R, lora_t + n * R, R);
                 store_small<DT>(out, bias, residual, n, row, M, t);
             }
         } else {
@@ -246,16 +260,20 @@ struct SmallNf4Args {
     void *out;
     int B, M, K, mode;
     hipStream_t stream;
+    const void *lora_B = nullptr;  // LORA instantiations only
+    const float *lora_t = nullptr;
+    int R = 0;
 };
 
-template <int DT, int NBW, int XS, bool FUSED>
+template <int DT, int NBW, int XS, bool FUSED, bool LORA>
 void launch_nf4_mfma(const SmallNf4Args &a) {
-    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
+    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED, LORA>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
                        reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
-                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode);
+                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
+                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R);
 }
 
-template <int DT, bool FUSED>
+template <int DT, bool FUSED, bool LORA = false>
 void dispatch_nf4_mfma(const SmallNf4Args &a) {
     const int B = a.B, M = a.M, K = a.K;
     const int units = K / 512;  // quant blocks per wave over the whole K
@@ -263,12 +281,12 @@ void dispatch_nf4_mfma(const SmallNf4Args &a) {
     // the FP4 kernel's rules: at most 4 blocks per wave and pass; x staged per wave in LDS always for <= 4 rows, for 5..8 rows only
     // while the grid is a single round anyway (the larger image leaves fewer workgroups per CU)
     if (units % 4 == 0) {
-        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED>(a);
-        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED>(a);
-        return launch_nf4_mfma<DT, 4, 0, FUSED>(a);
+        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED, LORA>(a);
+        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED, LORA>(a);
+        return launch_nf4_mfma<DT, 4, 0, FUSED, LORA>(a);
     }
-    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED>(a);
-    return launch_nf4_mfma<DT, 1, 0, FUSED>(a);
+    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED, LORA>(a);
+    return launch_nf4_mfma<DT, 1, 0, FUSED, LORA>(a);
 }
 
 }  // namespace
@@ -282,6 +300,17 @@ void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, con
         dispatch_nf4_mfma<FP4_DTYPE_F16, true>(a);
     else
         dispatch_nf4_mfma<FP4_DTYPE_BF16, true>(a);
+}
+
+// the same with the adapter term, for fp4_hip_gemm_lora_nf4 (gemm_wide_nf4.hip), which has validated the adapter as well
+void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
+                                const void *lora_B, const float *lora_t, int R, void *out, int B, int M, int K, int mode,
+                                hipStream_t stream) {
+    const SmallNf4Args a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, lora_B, lora_t, R};
+    if (dtype == FP4_DTYPE_F16)
+        dispatch_nf4_mfma<FP4_DTYPE_F16, true, true>(a);
+    else
+        dispatch_nf4_mfma<FP4_DTYPE_BF16, true, true>(a);
 }
 
 }  // namespace fp4

@@ -27,7 +27,12 @@
 // sums its odd neighbour's partials (wr + 1 = src + 4, as wide_epilogue of gemm_wide_fp4.hip does) and stores the pair, odd rows
 // store nothing; row tiles are 16 rows and row0 is even, so a pair never straddles a tile.  A compile-time choice: the plain entry
 // point keeps its instantiations instruction for instruction.
+//
+// LoRA adapter term (fp4_hip_gemm_lora_nf4, 1..64 rows): the LORA instantiations (always FUSED) add
+// delta[n][row] = sum_j f32(lora_B[row][j]) * lora_t[n][j] (lora_nf4.h) to the thread's finished f32 sum ahead of the epilogue, and
+// to the up row's likewise; lora_t = s * A x is lora_down_kernel's f32 output.
 #include "gemv_common.h"
+#include "lora_nf4.h"
 
 #include <atomic>
 
@@ -65,10 +70,12 @@ __device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &l
 // Weight image (per wave): 16 * RT rows of stride 32 * NBW + 32 bytes, the row's NBW scales behind its bytes.
 // FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
-template <int DT, int NT, int RT, int NBW, bool FUSED>
+template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA = false>
 __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
-                                                            uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode) {
+                                                            uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode,
+                                                            const uint16_t *lora_B, const float *lora_t, int R) {
+    static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
     constexpr int kRows = 16 * RT;
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kImageBytes = 8 * kRows * kStageStride;
@@ -250,9 +257,16 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
                     float u = 0.0f;
 #pragma unroll
                     for (int w = 0; w < 4; ++w) u += s_part[w][src + 4];
-                    if (row < M && n < B) store_small_silu_mul<DT>(out, bias, residual, n, (int)(row >> 1), M >> 1, t, u);
+                    if (row < M && n < B) {
+                        if constexpr (LORA) {
+                            t += lora_delta<DT>(lora_B + row * R, lora_t + n * R, R);
+                            u += lora_delta<DT>(lora_B + (row + 1) * R, lora_t + n * R, R);
+                        }
+                        store_small_silu_mul<DT>(out, bias, residual, n, (int)(row >> 1), M >> 1, t, u);
+                    }
                 }
             } else if (row < M && n < B) {
+                if constexpr (LORA) t += lora_delta<DT>(lora_B + row * R, lora_t + n * R, R);
                 store_small<DT>(out, bias, residual, n, (int)row, M, t);
             }
         } else {
@@ -271,16 +285,20 @@ struct WideNf4Args {
     void *out;
     int B, M, K, mode;
     hipStream_t stream;
+    const void *lora_B = nullptr;  // LORA instantiations only
+    const float *lora_t = nullptr;
+    int R = 0;
 };
 
-template <int DT, int NT, int RT, int NBW, bool FUSED>
+template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA>
 void launch_wide_nf4(const WideNf4Args &a) {
-    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512), 0,
-                       a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
-                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode);
+    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED, LORA>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512),
+                       0, a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
+                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
+                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R);
 }
 
-template <int DT, int NT, bool FUSED>
+template <int DT, int NT, bool FUSED, bool LORA>
 void dispatch_wide_nf4_nt(const WideNf4Args &a) {
     const int M = a.M, K = a.K;
     // 32 weight rows per workgroup halve the x traffic from L2, the kernel's largest stream: taken once that still fills three
@@ -289,21 +307,21 @@ void dispatch_wide_nf4_nt(const WideNf4Args &a) {
     const bool rt2 = v == 2 || (v != 1 && M >= 24 * device_cu_count());
     const bool nbw4 = K % 256 == 0;
     if (rt2) {
-        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED>(a);
-        return launch_wide_nf4<DT, NT, 2, 1, FUSED>(a);
+        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED, LORA>(a);
+        return launch_wide_nf4<DT, NT, 2, 1, FUSED, LORA>(a);
     }
-    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED>(a);
-    return launch_wide_nf4<DT, NT, 1, 1, FUSED>(a);
+    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED, LORA>(a);
+    return launch_wide_nf4<DT, NT, 1, 1, FUSED, LORA>(a);
 }
 
 // one launch: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
-template <int DT, bool FUSED>
+template <int DT, bool FUSED, bool LORA = false>
 void dispatch_wide_nf4(const WideNf4Args &a) {
     switch ((a.B + 15) / 16) {
-        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED>(a);
-        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED>(a);
-        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED>(a);
-        default: return dispatch_wide_nf4_nt<DT, 4, FUSED>(a);
+        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED, LORA>(a);
+        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED, LORA>(a);
+        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED, LORA>(a);
+        default: return dispatch_wide_nf4_nt<DT, 4, FUSED, LORA>(a);
     }
 }
 
@@ -311,6 +329,9 @@ void dispatch_wide_nf4(const WideNf4Args &a) {
 
 void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
                                  void *out, int B, int M, int K, int mode, hipStream_t stream);  // gemm_small_nf4.hip
+void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
+                                const void *lora_B, const float *lora_t, int R, void *out, int B, int M, int K, int mode,
+                                hipStream_t stream);  // gemm_small_nf4.hip
 
 void set_wide_nf4_variant(int v) { g_wide_nf4_variant.store(v, std::memory_order_relaxed); }
 
@@ -320,10 +341,11 @@ namespace fp4 {
 namespace {
 
 // fused = false: fp4_hip_gemm_wide_nf4.  fused = true: fp4_hip_gemm_fused_nf4 (same coverage and forwarding, plus residual / mode).
+// lora = true (with fused): fp4_hip_gemm_lora_nf4, the fused form for at most 64 rows plus the adapter term.
 int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                         const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode,
-                        void *stream) {
-    if (B < 0 || M < 0 || K <= 0 || blocksize <= 0) {
+                        void *stream, bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0) {
+    if (B < 0 || M < 0 || K <= 0 || blocksize <= 0 || (lora && R < 0)) {
         set_error("%s: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", name, (long long)B, (long long)M,
                   (long long)K, blocksize);
         return FP4_ERR_INVALID_ARGUMENT;
@@ -334,19 +356,32 @@ int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8
     }
     const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
     // the kernel addresses with 64-bit element offsets: M * K may pass 2^32; the bounds keep the int row / block arithmetic in range
-    if (B > 128 || blocksize != 64 || (K % 64) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) || (align & 15u) != 0 ||
+    if (B > (lora ? 64 : 128) || blocksize != 64 || (K % 64) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) || (align & 15u) != 0 ||
         M > (int64_t(1) << 30) || K > (int64_t(1) << 24)) {
-        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..128 rows, blocksize 64, "
+        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..%d rows, blocksize 64, "
                   "K %% 64 == 0, fp16 / bf16, 16-byte aligned x and packed); use dequant + GEMM",
-                  name, (long long)B, (long long)M, (long long)K, blocksize, dtype);
+                  name, (long long)B, (long long)M, (long long)K, blocksize, dtype, lora ? 64 : 128);
         return FP4_ERR_UNSUPPORTED;
     }
     if (M == 0 || B == 0) return FP4_OK;
-    if (!x || !packed || !absmax || !out) {
+    if (!x || !packed || !absmax || !out || (lora && (!lora_B || !lora_t))) {
         set_error("%s: null pointer", name);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (lora) {
+        if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
+        if (B <= 16 && K % 512 == 0) {
+            gemm_small_nf4_lora_launch(dtype, x, packed, absmax, bias, residual, lora_B, lora_t, (int)R, out, (int)B, (int)M, (int)K, mode, s);
+            return check_launch(name);
+        }
+        const WideNf4Args a{x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s, lora_B, lora_t, (int)R};
+        if (dtype == FP4_DTYPE_F16)
+            dispatch_wide_nf4<FP4_DTYPE_F16, true, true>(a);
+        else
+            dispatch_wide_nf4<FP4_DTYPE_BF16, true, true>(a);
+        return check_launch(name);
+    }
     // 1..16 rows on a K the 2..16-row kernel covers: that kernel, bit for bit
     if (B <= 16 && K % 512 == 0) {
         if (!fused) return fp4_hip_gemm_small_nf4(x, packed, absmax, bias, out, B, M, K, blocksize, dtype, stream);
@@ -395,4 +430,15 @@ extern "C" int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, cons
     }
     return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_fused_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
                                     epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
+}
+
+extern "C" int fp4_hip_gemm_lora_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                     const void *lora_B, const float *t, int64_t R, void *out, int64_t B, int64_t M, int64_t K,
+                                     int blocksize, int dtype, int epilogue, void *stream) {
+    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
+        fp4::set_error("fp4_hip_gemm_lora_nf4: unknown epilogue %d", epilogue);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_lora_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
+                                    epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R);
 }

@@ -21,9 +21,16 @@
 // two half-waves of a wave already hold rows 2j and 2j + 1, row_base and the rows per workgroup are even, so a gate row and its
 // up row meet in one wave (KSPLIT == 1) or in neighbouring s_part rows (KSPLIT > 1) and the pair never straddles a workgroup.
 // The epilogue is a compile-time choice: the plain entry point keeps the instantiations it had, instruction for instruction.
+//
+// LoRA adapter term (fp4_hip_gemv_lora_nf4): the LORA instantiations (always FUSED) add delta[r] = sum_j f32(B[r][j]) * t[j] to the
+// row's f32 sum before it is rounded; t = s * A x is lora_down_kernel's f32 output (lora_nf4.hip).  The lanes of the half-wave that
+// owns the row with 8 * l32 < R request 16 bytes of B[row] and their t slice before the weight stream, as x is requested; their
+// partial deltas go through a second copy of the dpp chain (not through p[it]: the plain sum keeps its order and its bits) and
+// sum + delta is one f32 add.  With KSPLIT > 1 only the kw == 0 wave of a row carries the term, through a column of its own in s_part.
 #include <atomic>
 
 #include "gemv_common.h"
+#include "lora_nf4.h"
 
 namespace fp4 {
 
@@ -72,11 +79,14 @@ struct OutPtr<true> {
 
 // FUSED = false: `residual` and `mode` are ignored (fp4_hip_gemv_nf4).  FUSED = true: the row epilogue adds the residual, and with
 // kModeSiluMulPairs (16-bit DT only, M even) rows (2i, 2i + 1) are a gate / up pair and out[i] = silu(gate_i) * up_i (+ residual[i]).
-template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED>
+// LORA = true (with FUSED): delta[row] = sum_j lora_B[row][j] * lora_t[j] (R % 8 == 0, 8 <= R <= 256) is added to the f32 row sum first.
+template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED, bool LORA = false>
 __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ x, const uint8_t *__restrict__ W,
                                                        const float *__restrict__ absmax, const void *__restrict__ bias,
                                                        typename OutPtr<FUSED>::type out, int M, int K, int bs_shift,
-                                                       const void *residual_arg, int mode) {  // new arguments last: the plain kernels keep their argument layout
+                                                       const void *residual_arg, int mode,  // new arguments last: the plain kernels keep their argument layout
+                                                       const void *lora_B, const float *lora_t, int R) {
+    static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
     const void *residual = FUSED ? residual_arg : nullptr;
     [[maybe_unused]] const bool gated = FUSED && DT != FP4_DTYPE_F32 && (mode & kModeSiluMulPairs);
     constexpr int RG = 4 / KSPLIT;
@@ -84,7 +94,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
     constexpr int kBand = G * 32 * KSPLIT;  // chunks of K covered per pass
     __shared__ float s_lut[PAIR ? 1 : 16];
     __shared__ f32x2 s_pair[PAIR ? 256 : 1];
-    __shared__ float s_part[kRowsPerBlock][KSPLIT];
+    __shared__ float s_part[kRowsPerBlock][KSPLIT + (LORA && KSPLIT > 1 ? 1 : 0)];  // LORA: column KSPLIT holds the row's delta
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -109,6 +119,27 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
     float p[ITERS];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) p[it] = 0.0f;
+    // LORA: this lane's 8 columns of B for each of its rows and the matching slice of t, requested ahead of the weight stream
+    // (branch-free: a lane past R re-reads unit 0 against a zero t; waves with kw != 0 carry no adapter term)
+    // (B stays as loaded - 4 VGPRs per row in a 16-bit T - until the row's epilogue widens it)
+    constexpr int kLbRegs = DT == FP4_DTYPE_F32 ? 2 : 1;
+    [[maybe_unused]] u32x4 lb[LORA ? ITERS : 1][kLbRegs];
+    [[maybe_unused]] f32x4 lt[2];
+    if constexpr (LORA) {
+        if (kw == 0) {
+            const bool on = 8 * l32 < R;
+            const int j8 = on ? l32 : 0;
+            lt[0] = reinterpret_cast<const f32x4 *>(lora_t)[2 * j8];
+            lt[1] = reinterpret_cast<const f32x4 *>(lora_t)[2 * j8 + 1];
+            if (!on) lt[0] = lt[1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) {
+                const u32x4 *src = reinterpret_cast<const u32x4 *>(lora_B) + ((int64_t(rclamp[it]) * R >> 3) + j8) * kLbRegs;
+#pragma unroll
+                for (int q = 0; q < kLbRegs; ++q) lb[it][q] = src[q];
+            }
+        }
+    }
 
     for (int cb = 0; cb < C; cb += kBand) {
         int cidx[G];
@@ -171,6 +202,22 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
         v = dpp_add<0x122>(v);
         v = dpp_add<0x121>(v);
         v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));  // 32-lane row sum
+        if constexpr (LORA) {
+            if (kw == 0) {  // wave-uniform
+                f32x4 b0, b1;
+                lora_widen8<DT>(lb[it], b0, b1);
+                float d = lora_dot8(b0, b1, lt[0], lt[1], 0.0f);
+                d = dpp_add<0x128>(d);
+                d = dpp_add<0x124>(d);
+                d = dpp_add<0x122>(d);
+                d = dpp_add<0x121>(d);
+                d += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, d), 0x401F));  // the row's delta
+                if constexpr (KSPLIT == 1)
+                    v += d;  // sum' = sum + delta, one f32 add
+                else if (l32 == 0)
+                    s_part[rowi[it]][KSPLIT] = d;
+            }
+        }
         if constexpr (KSPLIT == 1) {
             const int row = row_base + rowi[it];
             if constexpr (FUSED && DT != FP4_DTYPE_F32) {
@@ -196,6 +243,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
                     float g = 0.0f, u = 0.0f;
 #pragma unroll
                     for (int k = 0; k < KSPLIT; ++k) g += s_part[2 * tid][k], u += s_part[2 * tid + 1][k];
+                    if constexpr (LORA) g += s_part[2 * tid][KSPLIT], u += s_part[2 * tid + 1][KSPLIT];
                     const int row = row_base + 2 * tid;
                     if (row < M)
                         store_silu_mul<DT>(reinterpret_cast<uint16_t *>(out), reinterpret_cast<const uint16_t *>(bias),
@@ -208,6 +256,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
             float t = 0.0f;
 #pragma unroll
             for (int k = 0; k < KSPLIT; ++k) t += s_part[tid][k];
+            if constexpr (LORA) t += s_part[tid][KSPLIT];
             const int row = row_base + tid;
             if (row < M) store_nf4_row<DT>(out, bias, residual, row, t);
         }
@@ -224,21 +273,24 @@ struct Nf4Args {
     void *out;
     int M, K, bs_shift, mode;
     hipStream_t stream;
+    const void *lora_B = nullptr;  // LORA instantiations only
+    const float *lora_t = nullptr;
+    int R = 0;
 };
 
-template <int DT, int KSPLIT, int G, int ITERS, bool FUSED>
+template <int DT, int KSPLIT, int G, int ITERS, bool FUSED, bool LORA>
 void launch_nf4(bool pair, const Nf4Args &a) {
     constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
     const dim3 grid((unsigned)((a.M + rows_per_block - 1) / rows_per_block)), block(256);
     if (pair)
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED>), grid, block, 0, a.stream, a.x, a.W, a.absmax, a.bias,
-                           a.out, a.M, a.K, a.bs_shift, a.residual, a.mode);
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED, LORA>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
+                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R);
     else
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED>), grid, block, 0, a.stream, a.x, a.W, a.absmax, a.bias,
-                           a.out, a.M, a.K, a.bs_shift, a.residual, a.mode);
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED, LORA>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
+                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R);
 }
 
-template <int DT, bool FUSED>
+template <int DT, bool FUSED, bool LORA = false>
 void dispatch_nf4(bool pair, const Nf4Args &a) {
     const int M = a.M, K = a.K;
     const int C = K >> 5;
@@ -249,9 +301,9 @@ void dispatch_nf4(bool pair, const Nf4Args &a) {
     while (iters < 4 && M / (2 * (4 / ks) * iters * 2) >= 256) iters *= 2;
 #define NF4_ITERS(KS, GG)                                                                                          \
     switch (iters) {                                                                                               \
-        case 1: return launch_nf4<DT, KS, GG, 1, FUSED>(pair, a);                                                  \
-        case 2: return launch_nf4<DT, KS, GG, 2, FUSED>(pair, a);                                                  \
-        default: return launch_nf4<DT, KS, GG, 4, FUSED>(pair, a);                                                 \
+        case 1: return launch_nf4<DT, KS, GG, 1, FUSED, LORA>(pair, a);                                            \
+        case 2: return launch_nf4<DT, KS, GG, 2, FUSED, LORA>(pair, a);                                            \
+        default: return launch_nf4<DT, KS, GG, 4, FUSED, LORA>(pair, a);                                           \
     }
     if (C <= 32) { NF4_ITERS(1, 1) }
     if (C <= 64) { NF4_ITERS(2, 1) }
@@ -270,9 +322,11 @@ namespace fp4 {
 namespace {
 
 // fused = false: fp4_hip_gemv_nf4 (irregular shapes run the generic kernel).  fused = true: fp4_hip_gemv_fused_nf4 (the fast path or
-// FP4_ERR_UNSUPPORTED with nothing launched).  `name` is the entry point the messages speak for.
+// FP4_ERR_UNSUPPORTED with nothing launched).  `name` is the entry point the messages speak for.  lora = true (with fused):
+// fp4_hip_gemv_lora_nf4, the fused form plus the adapter term.
 int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
-                   const void *residual, void *out, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream) {
+                   const void *residual, void *out, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream,
+                   bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0) {
     if (M < 0 || K < 0 || (K & 1) || blocksize < 2 || (blocksize & 1)) {
         set_error("%s: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", name, (long long)M, (long long)K,
                   blocksize);
@@ -286,8 +340,12 @@ int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *p
         set_error("%s: the gate|up epilogue needs an even row count, got M=%lld", name, (long long)M);
         return FP4_ERR_INVALID_ARGUMENT;
     }
+    if (lora && R < 0) {
+        set_error("%s: R=%lld (need R >= 0)", name, (long long)R);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
     if (M == 0) return FP4_OK;
-    if (!out || (K > 0 && (!x || !packed || !absmax))) {
+    if (!out || (K > 0 && (!x || !packed || !absmax)) || (lora && (!lora_B || !lora_t))) {
         set_error("%s: null pointer", name);
         return FP4_ERR_INVALID_ARGUMENT;
     }
@@ -305,6 +363,17 @@ int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *p
                   "the plain GEMV and apply the epilogue separately",
                   name, (long long)M, (long long)K, blocksize, dtype, (mode & kModeSiluMulPairs) ? 1 : 0);
         return FP4_ERR_UNSUPPORTED;
+    }
+    if (lora) {
+        if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
+        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
+        const Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s, lora_B, lora_t, (int)R};
+        switch (dtype) {
+            case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, true>(pair, a); break;
+            case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, true>(pair, a); break;
+            default: dispatch_nf4<FP4_DTYPE_F32, true, true>(pair, a); break;
+        }
+        return check_launch(name);
     }
     if (fast) {
         const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
@@ -342,4 +411,15 @@ extern "C" int fp4_hip_gemv_fused_nf4(const void *x, const uint8_t *packed, cons
     }
     return fp4::gemv_nf4_entry("fp4_hip_gemv_fused_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
                                epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
+}
+
+extern "C" int fp4_hip_gemv_lora_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                     const void *lora_B, const float *t, int64_t R, void *out, int64_t M, int64_t K, int blocksize,
+                                     int dtype, int epilogue, void *stream) {
+    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
+        fp4::set_error("fp4_hip_gemv_lora_nf4: unknown epilogue %d", epilogue);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    return fp4::gemv_nf4_entry("fp4_hip_gemv_lora_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
+                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R);
 }

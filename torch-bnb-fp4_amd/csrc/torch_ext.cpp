@@ -14,7 +14,7 @@
 //   * qlinear_codebook* dequantise all M*N elements (the reference passes the BYTE count,
 //     csrc/torch_fp4.cpp:90,101, leaving half of the weight uninitialised).
 // Extra exports (not in the reference): the NF4 ops (dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4, qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4,
-// quantize_nf4: bitsandbytes' second 4-bit code, same kernels' shapes and dispatch), gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
+// quantize_nf4: bitsandbytes' second 4-bit code, same kernels' shapes and dispatch; lora_down, gemv_nf4_lora, gemm_nf4_lora: LoRA adapters beside an NF4 weight), gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -590,7 +590,8 @@ torch::Tensor gemm_small_fp4_fused(torch::Tensor A, torch::Tensor B, torch::Tens
 // rows in total -> [.., m] or, for the gated epilogue, [.., m / 2].  One allocation (the output), no sync: capturable.
 torch::Tensor nf4_fused_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
                              int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
-                             const c10::optional<torch::Tensor> &residual, int epilogue) {
+                             const c10::optional<torch::Tensor> &residual, int epilogue, const torch::Tensor *lora_B = nullptr,
+                             const torch::Tensor *lora_t = nullptr) {
     check_gpu_contiguous(A, "A");
     check_gpu_contiguous(B, "B");
     check_gpu_contiguous(absmax, "absmax");
@@ -625,6 +626,22 @@ torch::Tensor nf4_fused_impl(const char *op, bool gemv, const torch::Tensor &A, 
         res_ptr = res_c.data_ptr();
     }
     c10::DeviceGuard guard(A.device());
+    if (lora_B) {  // the LoRA forms: lora_B [m, R] of the activation dtype over the weight's rows, lora_t [rows, R] float32 (lora_down)
+        check_gpu_contiguous(*lora_B, "lora_B");
+        check_gpu_contiguous(*lora_t, "t");
+        TORCH_CHECK(lora_B->dim() == 2 && lora_B->size(0) == m && lora_B->scalar_type() == A.scalar_type() && lora_B->device() == A.device(),
+                    op, ": lora_B must be a [", m, ", R] tensor of the activation dtype on the activation's device");
+        const int64_t R = lora_B->size(1);
+        TORCH_CHECK(lora_t->scalar_type() == torch::kFloat32 && lora_t->numel() == rows * R && lora_t->device() == A.device(), op,
+                    ": t must hold ", rows * R, " float32 elements (lora_down's output) on the activation's device");
+        if (gemv)
+            check_status(fp4_hip_gemv_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, lora_B->data_ptr(),
+                              lora_t->data_ptr<float>(), R, out.data_ptr(), m, k, blocksize, dt, epilogue, current_stream(A)));
+        else
+            check_status(fp4_hip_gemm_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, lora_B->data_ptr(),
+                              lora_t->data_ptr<float>(), R, out.data_ptr(), rows, m, k, blocksize, dt, epilogue, current_stream(A)));
+        return out;
+    }
     if (gemv)
         check_status(fp4_hip_gemv_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(),
                                             m, k, blocksize, dt, epilogue, current_stream(A)));
@@ -640,6 +657,37 @@ torch::Tensor gemv_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor abs
 torch::Tensor gemm_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
     return nf4_fused_impl("gemm_nf4_fused", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue);
+}
+
+// LoRA adapters beside an NF4 weight.  lora_down: t = scale * (x @ A^T) as float32 [rows, R] (fp4_hip_lora_down; x [.., K] with
+// 1..64 rows, A [R, K] of x's dtype, scale float32 [R]).  gemv_nf4_lora / gemm_nf4_lora: gemv_nf4_fused / gemm_nf4_fused with
+// lora_B @ t added to the f32 row sums before the rounding (fp4_hip_gemv_lora_nf4 / fp4_hip_gemm_lora_nf4).  One allocation each.
+torch::Tensor lora_down(torch::Tensor x, torch::Tensor A, torch::Tensor scale) {
+    check_gpu_contiguous(x, "x");
+    check_gpu_contiguous(A, "A");
+    check_gpu_contiguous(scale, "scale");
+    TORCH_CHECK(A.dim() == 2, "lora_down: A must be [R, in_features]");
+    const int64_t R = A.size(0), k = A.size(1);
+    TORCH_CHECK(x.dim() >= 1 && k > 0 && x.size(-1) == k, "lora_down: last dim of the activation must be in_features = ", k);
+    TORCH_CHECK(A.scalar_type() == x.scalar_type(), "lora_down: A must have the activation's dtype");
+    TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.numel() == R, "lora_down: scale must hold ", R, " float32 factors");
+    TORCH_CHECK(A.device() == x.device() && scale.device() == x.device(), "all tensors must be on one device");
+    const int64_t rows = x.numel() / k;
+    const int dt = to_fp4_dtype(x.scalar_type(), "lora_down");
+    torch::Tensor t = torch::empty({rows, R}, x.options().dtype(torch::kFloat32));
+    c10::DeviceGuard guard(x.device());
+    check_status(fp4_hip_lora_down(x.data_ptr(), A.data_ptr(), scale.data_ptr<float>(), t.data_ptr<float>(), rows, R, k, dt, current_stream(x)));
+    return t;
+}
+torch::Tensor gemv_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                            c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue, torch::Tensor lora_B,
+                            torch::Tensor t) {
+    return nf4_fused_impl("gemv_nf4_lora", true, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, &lora_B, &t);
+}
+torch::Tensor gemm_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                            c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue, torch::Tensor lora_B,
+                            torch::Tensor t) {
+    return nf4_fused_impl("gemm_nf4_lora", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, &lora_B, &t);
 }
 
 // f32 partial sums of a K-split shard: [1, m] float32 (see fp4_hip_gemv_partial)
@@ -796,6 +844,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "1 = silu(gate) * up over interleaved rows");
     m.def("gemm_nf4_fused", &gemm_nf4_fused,
           "fused NF4 product for 1..128 rows with an epilogue: (A, B, absmax, blocksize, Bshape, bias|None, residual|None, epilogue)");
+    m.def("lora_down", &lora_down, "LoRA down projection: (x, A [R, K], scale float32 [R]) -> t = scale * (x @ A^T), float32 [rows, R]");
+    m.def("gemv_nf4_lora", &gemv_nf4_lora,
+          "gemv_nf4_fused plus the adapter term lora_B @ t in f32 before the rounding: (A, B, absmax, blocksize, Bshape, bias|None, "
+          "residual|None, epilogue, lora_B [m, R], t float32 [1, R])");
+    m.def("gemm_nf4_lora", &gemm_nf4_lora,
+          "gemm_nf4_fused for 1..64 rows plus the adapter term: (A, B, absmax, blocksize, Bshape, bias|None, residual|None, epilogue, "
+          "lora_B [m, R], t float32 [rows, R])");
     m.def("quantize_nf4", &quantize_nf4, "blockwise NF4 quantiser: (W, blocksize) -> (packed, absmax)");
     m.def("code_table", &code_table, "16-entry code table as a CPU float tensor");
     m.def("set_kernel_variant", &set_kernel_variant, "benchmark hook: select a kernel geometry");

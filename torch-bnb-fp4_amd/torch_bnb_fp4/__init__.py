@@ -31,7 +31,7 @@ from .functional import (
     quantize_nf4,
 )
 from .comm import OneShotAllReduce
-from .fused import FusedFP4Linear, FusedNF4Linear
+from .fused import FusedFP4Linear, FusedNF4Linear, LoRANF4Linear
 from .graphs import GraphedStep
 from .linear import TorchFP4Linear
 from .nn import Linear4bit, LinearFP4, LinearNF4, Params4bit, QuantState, nf4_code
@@ -39,8 +39,10 @@ from .quant_data import QuantData
 from .serialization import fp4_linear_from_bnb_state, fp4_linear_to_bnb_state, load_fp4_layers, save_fp4_model
 from .surgery import (
     FusedGatedMLP,
+    attach_lora,
     check_if_name_contained_in_list,
     fuse_gated_mlps,
+    load_lora_adapter,
     recursively_replace_with_fp4_linear,
     set_small_batch_fused,
     swap_linear_with_bnb_linear,
@@ -82,5 +84,8 @@ __all__ = [
     "quantize_nf4",
     "LinearNF4",
     "nf4_code",
+    "LoRANF4Linear",
+    "attach_lora",
+    "load_lora_adapter",
 ]
 __version__ = "0.1.0"

@@ -17,9 +17,15 @@ the fused kernels do not cover, run the unfused sequence through :class:`QuantDa
 
 :class:`FusedNF4Linear` is the same layer over an NF4 weight (``fp4_hip_gemv_fused_nf4`` for one row,
 ``fp4_hip_gemm_fused_nf4`` for 2..64 rows); :class:`FusedFP4Linear` itself refuses NF4 weights.
+
+:class:`LoRANF4Linear` is a :class:`FusedNF4Linear` with a LoRA adapter beside the 4-bit weight (QLoRA serving: the adapter cannot
+be merged into NF4 without re-quantising): ``y = W x + B (s * A x)`` as two launches, the down projection ``t = s * A x`` in f32
+(``fp4_hip_lora_down``) and the same fused kernels with ``B t`` added to their f32 row sums before the rounding
+(``fp4_hip_gemv_lora_nf4`` / ``fp4_hip_gemm_lora_nf4``).
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -241,3 +247,193 @@ class FusedNF4Linear(FusedFP4Linear):
                     raise
                 self._small_ok = False
         return self._unfused(x, residual)
+
+
+LORA_RANK_MULTIPLE = 8  # the kernels read B and t in 16-byte units
+LORA_MAX_RANK = 256
+
+
+def lora_fused_ahead(rows: int, M: int, K: int, rank: int) -> bool:
+    """Where ``lora_down`` + the fused adapter op measured ahead of the fused NF4 op plus the adapter as torch ops by more than both
+    replay-to-replay ranges together (profiles/nf4_lora.json: Mistral-7B shapes, ranks 16..256, 1..64 rows, bf16 and fp16).  One
+    row: every cell.  2..64 rows: the per-thread FMA chain over the rank in the store loops grows with ``M * rows * rank`` while
+    torch's two dense products hardly do, so each rank band is trusted up to the largest ``M * rows * rank`` at which all of its
+    measured cells were ahead; past it cells were level or behind (28672 x 4096, rank 64, 64 rows: 138 vs 115 us; rank 256: 315 vs
+    125).  Against rows of 14336 weights torch's ``x @ A^T`` is slow and every cell was ahead, up to 4096 * 64 * 256."""
+    if rows == 1:
+        return True
+    if K >= 14336:
+        limit = 4096 * 64 * 256
+    elif rank <= 32:
+        limit = 14336 * 64 * 32
+    elif rank <= 128:
+        limit = 4096 * 64 * 64
+    else:
+        limit = 4096 * 8 * 256
+    return M * rows * rank <= limit
+
+
+def pad_adapter(lora_A: torch.Tensor, lora_B: torch.Tensor, scale: torch.Tensor):
+    """Zero rows of A, zero columns of B and zero factors up to the next multiple of 8 of the rank.  Exact: a padded row of A gives
+    t = 0 and a padded column of B multiplies it by 0."""
+    r = lora_A.shape[0]
+    pad = -r % LORA_RANK_MULTIPLE
+    if pad:
+        lora_A = torch.cat([lora_A, lora_A.new_zeros(pad, lora_A.shape[1])], 0)
+        lora_B = torch.cat([lora_B, lora_B.new_zeros(lora_B.shape[0], pad)], 1)
+        scale = torch.cat([scale, scale.new_zeros(pad)], 0)
+    return lora_A.contiguous(), lora_B.contiguous(), scale.contiguous()
+
+
+def stack_gate_up_adapters(gate_adapter, up_adapter):
+    """``(A, B, scaling)`` of a gate and an up projection -> one adapter over the row-interleaved gate|up weight: A stacked to
+    ``[r_g + r_u, K]``, B block-structured and row-interleaved like the weight (row 2i = ``[B_gate[i], 0]``, row 2i + 1 =
+    ``[0, B_up[i]]``), one scale per adapter row."""
+    (Ag, Bg, sg), (Au, Bu, su) = gate_adapter, up_adapter
+    if Bg.shape[0] != Bu.shape[0] or Ag.shape[1] != Au.shape[1] or Ag.shape[0] != Bg.shape[1] or Au.shape[0] != Bu.shape[1]:
+        raise ValueError("gate and up adapters must be (A [r, K], B [M, r]) pairs of two projections of the same [M, K] shape")
+    rg, ru, M = Ag.shape[0], Au.shape[0], Bg.shape[0]
+    A = torch.cat([Ag, Au.to(Ag)], 0)
+    B = Bg.new_zeros(M, 2, rg + ru)
+    B[:, 0, :rg] = Bg
+    B[:, 1, rg:] = Bu.to(Bg)
+    scale = torch.cat([torch.full((rg,), float(sg)), torch.full((ru,), float(su))]).to(device=Ag.device, dtype=torch.float32)
+    return A, B.reshape(2 * M, rg + ru), scale
+
+
+def lora_scaling(r: int, lora_alpha: float, use_rslora: bool = False) -> float:
+    """peft's factor: ``alpha / r``, or ``alpha / sqrt(r)`` with rank-stabilised LoRA."""
+    return float(lora_alpha) / (math.sqrt(r) if use_rslora else r)
+
+
+class LoRANF4Linear(FusedNF4Linear):
+    """A :class:`FusedNF4Linear` with a LoRA adapter: ``forward(x, residual=None)`` = epilogue of ``W x + B (s * A x)``.
+
+    ``lora_A`` is ``[r, K]``, ``lora_B`` ``[M, r]`` over the weight's own rows (``M`` = all rows of an interleaved gate|up weight),
+    ``scale`` a float or a float32 ``[r]`` tensor (one factor per adapter row).  Any rank works: A, B and the scales are zero-padded
+    to a multiple of 8 here, which is exact.  The adapter follows the activation dtype (cast once per dtype from the tensors as attached).  Dropout is a
+    training-time device; this layer is inference-only and has none.
+
+    One activation row runs ``lora_down`` + ``gemv_nf4_lora``, 2..64 rows ``lora_down`` + ``gemm_nf4_lora``: the adapter term joins
+    the f32 row sum before anything is rounded, one rounding fewer than peft's sequence.  Whatever the fused ops do not cover (65+
+    rows, ranks above 256, shapes the NF4 fused kernels refuse), and the 2..64-row cells in which they did not measure ahead
+    (:func:`lora_fused_ahead`: large ``M * rows * rank``), runs the base through the parent's kernels and the adapter in torch
+    in f32, ``(x.float() @ A.float().T * scale) @ B.float().T``, added before one cast."""
+
+    def __init__(self, quant_data: QuantData, epilogue: int, lora_A: torch.Tensor, lora_B: torch.Tensor, scale):
+        super().__init__(quant_data, epilogue)
+        if lora_A.ndim != 2 or lora_B.ndim != 2 or lora_A.shape[1] != self.in_features or lora_B.shape != (int(quant_data.M), lora_A.shape[0]):
+            raise ValueError(f"adapter shapes {tuple(lora_A.shape)} / {tuple(lora_B.shape)} do not fit a [{int(quant_data.M)}, "
+                             f"{self.in_features}] weight (need A [r, K] and B [M, r])")
+        self.rank = int(lora_A.shape[0])
+        dev = self.qweight.device
+        if not torch.is_tensor(scale):
+            scale = torch.full((self.rank,), float(scale))
+        if scale.numel() != self.rank:
+            raise ValueError(f"scale must be one factor or one per adapter row ({self.rank}), got {scale.numel()}")
+        A, B, sc = pad_adapter(lora_A.detach().to(dev), lora_B.detach().to(dev), scale.detach().reshape(-1).to(device=dev, dtype=torch.float32))
+        self.register_buffer("lora_A", A, persistent=True)
+        self.register_buffer("lora_B", B, persistent=True)
+        self.register_buffer("lora_scale", sc, persistent=True)
+        self._lora_ok = A.shape[0] <= LORA_MAX_RANK  # cleared as well when lora_down reports a shape as not covered
+        self._cast = {}  # activation dtype -> (A, B) in that dtype
+
+    # -- constructors ------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_fused(cls, layer: FusedNF4Linear, lora_A, lora_B, scale) -> "LoRANF4Linear":
+        """From a :class:`FusedNF4Linear` (shares its packed weight); ``lora_B`` covers the weight's own (interleaved) rows."""
+        cls._check_code(layer.quant_data)
+        return cls(layer.quant_data, layer.epilogue, lora_A, lora_B, scale)
+
+    @classmethod
+    def from_linear(cls, layer, lora_A, lora_B, scaling) -> "LoRANF4Linear":
+        """From an NF4 :class:`TorchFP4Linear` (shares its packed weight) and one adapter."""
+        return cls.from_fused(FusedNF4Linear.from_linear(layer), lora_A, lora_B, scaling)
+
+    @classmethod
+    def gate_up(cls, gate_layer, up_layer, gate_adapter, up_adapter) -> "LoRANF4Linear":
+        """From the gate and up :class:`TorchFP4Linear` of a gated MLP and their ``(A, B, scaling)`` adapters."""
+        return cls.gate_up_from_fused(FusedNF4Linear.gate_up(gate_layer, up_layer), gate_adapter, up_adapter)
+
+    @classmethod
+    def gate_up_from_fused(cls, layer: FusedNF4Linear, gate_adapter, up_adapter) -> "LoRANF4Linear":
+        if layer.epilogue != EPILOGUE_SILU_MUL_PAIRS:
+            raise ValueError("gate_up_from_fused() needs a gate|up layer (FusedNF4Linear.gate_up)")
+        return cls.from_fused(layer, *stack_gate_up_adapters(gate_adapter, up_adapter))
+
+    @classmethod
+    def from_packed(cls, *args, **kwargs):
+        raise TypeError("LoRANF4Linear needs an adapter: build a FusedNF4Linear.from_packed(...) and pass it to from_fused()")
+
+    @classmethod
+    def gate_up_from_packed(cls, *args, **kwargs):
+        raise TypeError("LoRANF4Linear needs adapters: build a FusedNF4Linear.gate_up_from_packed(...) and pass it to gate_up_from_fused()")
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)  # device moves only
+        for name in ("lora_A", "lora_B", "lora_scale"):
+            self._buffers[name] = self._buffers[name].to(self.qweight.device)
+        self._cast = {}
+        return self
+
+    # -- forward -----------------------------------------------------------------------------------------------------
+    def _adapter(self, dtype: torch.dtype):
+        # the adapter follows the activation dtype, as the bias does; the buffers stay as attached and every cast starts from them,
+        # so a layer that meets two activation dtypes rounds the adapter once for each, never twice in a row
+        if self.lora_A.dtype == dtype:
+            return self.lora_A, self.lora_B
+        cast = self._cast.get(dtype)
+        if cast is None or cast[0].device != self.lora_A.device:
+            cast = self._cast[dtype] = (self.lora_A.to(dtype), self.lora_B.to(dtype))
+        return cast
+
+    def _adapter_in_torch(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
+        A, B = self._adapter(x.dtype)
+        delta = (x.float() @ A.float().t() * self.lora_scale) @ B.float().t()
+        if self.epilogue == EPILOGUE_SILU_MUL_PAIRS:
+            y = (self.quant_data.forward(x).float() + delta).to(x.dtype)
+            y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
+        else:
+            y = (FusedNF4Linear.forward(self, x).float() + delta).to(x.dtype)
+        return y if residual is None else y + residual
+
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        qd = self.quant_data
+        K = x.shape[-1]
+        if not qd.compute_dtype_set and x.numel():
+            qd.set_compute_type(x)
+            if qd.bias is not None:
+                self._buffers["bias"] = qd.bias  # the buffer follows the cast to the compute dtype
+        rows = x.numel() // K if K else 0
+        if self._lora_ok and rows >= 1 and K == self.in_features and x.dtype == qd.o_type and K % qd.blocksize == 0:
+            one = rows == 1 and x.ndim in (2, 3) and self._fused_ok
+            many = (2 <= rows <= 64 and self._small_ok and x.dtype in (torch.float16, torch.bfloat16) and qd.blocksize == 64
+                    and K % 64 == 0)
+            if (one or many) and lora_fused_ahead(rows, int(qd.M), K, int(self.lora_A.shape[0])):
+                A, B = self._adapter(x.dtype)
+                x = x.contiguous()
+                try:
+                    t = ext.lora_down(x, A, self.lora_scale)
+                except RuntimeError as exc:
+                    if "not covered" not in str(exc):
+                        raise
+                    self._lora_ok = False
+                    return self._adapter_in_torch(x, residual)
+                # the parent's measured exception holds here as well (the store loop is the same one): more than 32 rows against
+                # rows of 8192 and more weights with the plain epilogue leave the residual add to torch, T(t + r) either way
+                in_kernel = residual is not None and not (many and self.epilogue == EPILOGUE_NONE and rows > 32 and K >= 8192)
+                try:
+                    op = ext.gemv_nf4_lora if one else ext.gemm_nf4_lora
+                    y = op(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual if in_kernel else None, self.epilogue, B, t)
+                    return y if in_kernel or residual is None else y + residual
+                except RuntimeError as exc:  # a refusal clears the flag of the op that refused, whatever its wording
+                    if "not available" not in str(exc) and "not covered" not in str(exc):
+                        raise
+                    if one:
+                        self._fused_ok = False  # outside the GEMV's fused coverage: the fallback from now on
+                    else:
+                        self._small_ok = False
+        return self._adapter_in_torch(x, residual)
+
+    def extra_repr(self) -> str:
+        return super().extra_repr() + f", lora_rank={self.rank}"

@@ -205,3 +205,108 @@ def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_pr
         else:
             count += fuse_gated_mlps(child, gate, up, down, act, nf4)
     return count
+
+
+# ---- LoRA adapters beside NF4 weights (QLoRA serving) ---------------------------------------------------------------------------------
+def _adapter_tensors(adapter_state) -> dict:
+    """peft's saved keys -> {module path: {"A": tensor, "B": tensor}}.  Keys look like
+    ``base_model.model.<path>.lora_A.weight`` or, with an adapter-name segment, ``base_model.model.<path>.lora_A.<name>.weight``."""
+    out = {}
+    for key, tensor in adapter_state.items():
+        parts = key.split(".")
+        which = next((i for i, p in enumerate(parts) if p in ("lora_A", "lora_B")), None)
+        if which is None or parts[-1] != "weight" or len(parts) - which not in (2, 3):
+            raise KeyError(f"not a LoRA adapter key: {key!r} (expected <path>.lora_A.weight / <path>.lora_B.weight)")
+        path = parts[:which]
+        if path[:2] == ["base_model", "model"]:
+            path = path[2:]
+        slot = out.setdefault(".".join(path), {})
+        if parts[which][-1] in slot:
+            raise KeyError(f"two tensors for {'.'.join(path)}.{parts[which]}: one adapter at a time")
+        slot[parts[which][-1]] = tensor
+    for path, slot in out.items():
+        if set(slot) != {"A", "B"}:
+            raise KeyError(f"adapter for {path!r} lacks lora_{'B' if 'A' in slot else 'A'}")
+    return out
+
+
+def _resolve(model: nn.Module, path: str):
+    """(parent module, child name, child) for a dotted path, or None.  A path into a :class:`FusedGatedMLP` names one of the two
+    projections it replaced: then the child is the FusedGatedMLP itself."""
+    parent, parts = model, path.split(".")
+    for i, name in enumerate(parts):
+        if isinstance(parent, FusedGatedMLP) and i == len(parts) - 1 and name in parent.projection_names:
+            return parent, name, parent
+        child = parent._modules.get(name) if isinstance(parent, nn.Module) else None
+        if child is None:
+            return None
+        if i == len(parts) - 1:
+            return parent, name, child
+        parent = child
+    return None
+
+
+def attach_lora(model: nn.Module, adapter_state, r: int, lora_alpha: float, use_rslora: bool = False, target_modules=None) -> int:
+    """Attach a saved LoRA adapter to the NF4 layers of ``model``: every NF4 :class:`TorchFP4Linear` (or
+    :class:`~torch_bnb_fp4.fused.FusedNF4Linear`) an adapter key names becomes a :class:`~torch_bnb_fp4.fused.LoRANF4Linear`, and
+    the gate|up layer of an NF4 :class:`FusedGatedMLP` (``fuse_gated_mlps(model, nf4=True)``) takes the gate and the up adapter
+    stacked (a projection without one gets a zero adapter).  ``adapter_state`` uses peft's saved key names, with or without the
+    ``base_model.model.`` prefix and an adapter-name segment; the factor is ``lora_alpha / r`` (``/ sqrt(r)`` with
+    ``use_rslora``).  ``target_modules`` (names, as in peft's config) restricts which keys are used; a key that is used but has no
+    NF4 home in ``model`` raises, and a call that raises leaves ``model`` as it was.  Adapters are not merged: 4-bit weights cannot absorb them without re-quantising.  Returns the
+    number of layers replaced.  peft itself is not needed."""
+    from .fused import FusedNF4Linear, LoRANF4Linear, lora_scaling
+
+    scaling = lora_scaling(r, lora_alpha, use_rslora)
+    adapters = _adapter_tensors(adapter_state)
+    if target_modules is not None:
+        names = [target_modules] if isinstance(target_modules, str) else list(target_modules)
+        adapters = {p: t for p, t in adapters.items() if any(p == n or p.endswith("." + n) for n in names)}
+    gated = {}  # id(FusedGatedMLP) -> (module, {"gate": adapter, "up": adapter})
+    plan = []  # (parent, attribute, new layer): every key is checked and every layer built before the model is touched
+    for path, slot in adapters.items():
+        found = _resolve(model, path) or (_resolve(model, path[len("model."):]) if path.startswith("model.") else None)
+        if found is None:
+            raise KeyError(f"adapter key for {path!r}: the model has no such module")
+        parent, name, child = found
+        A, B = slot["A"], slot["B"]
+        if A.shape[0] != r or B.shape[1] != r:
+            raise ValueError(f"adapter for {path!r} has rank {A.shape[0]} / {B.shape[1]}, the config says r = {r}")
+        if isinstance(child, FusedGatedMLP):
+            if not isinstance(child.gate_up, FusedNF4Linear):
+                raise ValueError(f"adapter key for {path!r}: the fused MLP there is not NF4")
+            which = "gate" if name == child.projection_names[0] else "up"
+            gated.setdefault(id(child), (child, {}))[1][which] = (A, B, scaling)
+        elif isinstance(child, TorchFP4Linear) and child.quant_data.nf4:
+            plan.append((parent, name, LoRANF4Linear.from_linear(child, A, B, scaling)))
+        elif type(child) is FusedNF4Linear:
+            plan.append((parent, name, LoRANF4Linear.from_fused(child, A, B, scaling)))
+        else:
+            raise ValueError(f"adapter key for {path!r}: {type(child).__name__} is not an NF4 layer (quantise the model with "
+                             f"quant_type='nf4' first; an adapter is attached once)")
+    for mlp, pair in gated.values():
+        gu = mlp.gate_up
+        if isinstance(gu, LoRANF4Linear):
+            raise ValueError("this fused MLP already carries an adapter")
+        M, K = gu.out_features, gu.in_features
+        ref = next(iter(pair.values()))[0]
+        zero = (ref.new_zeros(r, K), ref.new_zeros(M, r), 0.0)
+        plan.append((mlp, "gate_up", LoRANF4Linear.gate_up_from_fused(gu, pair.get("gate", zero), pair.get("up", zero))))
+    for parent, name, layer in plan:
+        parent._modules[name] = layer
+    return len(plan)
+
+
+def load_lora_adapter(model: nn.Module, directory: str) -> int:
+    """:func:`attach_lora` from a directory in peft's layout: ``adapter_model.safetensors`` and ``adapter_config.json`` (``r``,
+    ``lora_alpha``, ``use_rslora``, ``target_modules``)."""
+    import json
+    import os
+
+    from safetensors.torch import load_file
+
+    with open(os.path.join(directory, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    state = load_file(os.path.join(directory, "adapter_model.safetensors"))
+    return attach_lora(model, state, int(cfg["r"]), float(cfg["lora_alpha"]), bool(cfg.get("use_rslora", False)),
+                       cfg.get("target_modules"))
