@@ -334,6 +334,39 @@ FP4_HIP_API int fp4_hip_gemm_lora_nf4(const void *x, const uint8_t *packed, cons
                                       int blocksize, int dtype, int epilogue, void *stream);
 
 /*
+ * Nested (double-quantised) absmax -- bitsandbytes' compress_statistics (bnb_4bit_use_double_quant=True, the QLoRA recipe): the
+ * per-block scales of a 4-bit weight are themselves quantised.  Per weight with nb = ceil(M*K / blocksize) blocks and g = nested_blocksize:
+ *   absmax_u8 : uint8[nb]      nested_absmax : float[ceil(nb / g)]      code256 : float[256]      offset : one float
+ *   absmax[i] = fl32( fl32( code256[absmax_u8[i]] * nested_absmax[i / g] ) + offset )        a multiply, then an add: two roundings.
+ * Not in the reference.  Additions to ABI version 7.  All three are deterministic, neither allocate nor synchronise, and take
+ * `offset` by value (no host scalar is read on the device): capturable.
+ *
+ * fp4_hip_absmax_unnest: writes the nb expanded scales to out_f32, after which every entry point above applies unchanged.
+ *   g: a power of two in 64..4096 (else FP4_ERR_UNSUPPORTED); nb <= 2^31; the last group may be partial; FP4_OK without a launch
+ *   for nb == 0; a null pointer or nb < 0: FP4_ERR_INVALID_ARGUMENT.  Nothing is launched and out is untouched on an error.
+ *
+ * fp4_hip_absmax_nest: the writing side.  Per group: v = fl32(a - offset), m = max|v|, n = fl32(v * fl32(1 / m)),
+ *   out_u8 = the index of the entry of code256 nearest to n (an exact tie: the lower index), out_nested_absmax = m.  A group with
+ *   m == 0 gets every out_u8 = the index of the table's 0.0, so it expands to exactly `offset`.  Any offset is valid (bitsandbytes
+ *   uses the mean of absmax); the table needs no particular order.  Same argument rules as fp4_hip_absmax_unnest.
+ *
+ * fp4_hip_gemv_nested_nf4: fp4_hip_gemv_fused_nf4 reading the compressed statistics directly (33 instead of 36 bytes streamed per
+ *   64 weights at blocksize 64, and a quarter of the resident statistics).  The scale is formed by the formula above inside the
+ *   kernel; everything after it is fp4_hip_gemv_fused_nf4's, so the result EQUALS fp4_hip_gemv_fused_nf4 on the expanded absmax
+ *   bit for bit, for every shape, dtype and epilogue.  Covered: what fp4_hip_gemv_fused_nf4 covers, with nested_blocksize == 256
+ *   (what every bitsandbytes file holds).  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, out untouched - the caller
+ *   expands the statistics and runs the plain entry points.  Error codes otherwise as fp4_hip_gemv_fused_nf4; nested_blocksize <= 0
+ *   or a null nested_absmax / code256: FP4_ERR_INVALID_ARGUMENT.
+ */
+FP4_HIP_API int fp4_hip_absmax_unnest(const uint8_t *absmax_u8, const float *nested_absmax, const float *code256, float offset,
+                                      int nested_blocksize, int64_t nb, float *out_f32, void *stream);
+FP4_HIP_API int fp4_hip_absmax_nest(const float *absmax_f32, int64_t nb, float offset, const float *code256, int nested_blocksize,
+                                    uint8_t *out_u8, float *out_nested_absmax, void *stream);
+FP4_HIP_API int fp4_hip_gemv_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                        const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
+                                        void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
+
+/*
  * Tuning hook for benchmarks/sweeps: selects a kernel geometry by name
  * ("dequant", "gemv", "gemv_nf4" (0 = 16-entry f32 table, 1 = 256-entry pair table), "gemm_wide_nf4" (1 / 2 = 16 / 32 weight rows per workgroup), "gemm_small", "gemm_wide" = rows per workgroup of the 17..64-row kernels (1 / 2 / 3 / 4 = 16 / 32 / 64 / 128, 5 = 16 with self-contained waves; 0 = off),
  * "quantize": 1..999 = the persistent kernel with that many workgroups per CU, 1001 / 1002 / 1004 = the one-shot tiles kernel with 1 / 2 / 4 loads per lane).  variant < 0 (quantize: 0) restores the built-in heuristic.

@@ -33,6 +33,12 @@ fp16, one run on the same operands, all through the torch ops as the layers issu
 (c) the fused NF4 op alone (what the adapter costs on top).  The 28672-row shape runs the gate|up epilogue, where (b) has to take the
 plain rows, add and apply silu * up itself.  A cell is won where (a) is ahead of (b) by more than both replay-to-replay ranges together.
 --lora-ranks / --lora-rows replace the rank and row lists.
+
+--nested: double-quantised absmax (profiles/nf4_nested.json), bf16, the four decoder shapes, one run on the same operands, the
+protocol of --fused.  (1) fp4_hip_gemv_nested_nf4 on the compressed statistics against fp4_hip_gemv_fused_nf4 on their expansion
+(level / ahead / behind beyond both replay-to-replay ranges).  (2) The plain fp4_hip_gemv_nf4 of this tree's library and, with
+--baseline-lib, of the parent commit's, side by side; "within" as for --fused.  (3) absmax_unnest alone, and qlinear_nf4_nested
+against qlinear_nf4 at 8 and 64 rows.  (4) Device bytes of one layer's statistics, resident and expanded.
 """
 import argparse
 import ctypes
@@ -288,6 +294,91 @@ def fused_epilogues(args):
                       "fused_vs_unfused": cells}))
 
 
+def nested(args):
+    L = lib()
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    dev = torch.device("cuda", 0)
+    s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    dtype, dt = torch.bfloat16, DT[torch.bfloat16]
+    G = 256
+
+    def bind(l):
+        l.fp4_hip_gemv_nf4.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+        return l
+
+    L.fp4_hip_gemv_fused_nf4.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp]
+    L.fp4_hip_gemv_nested_nf4.argtypes = [vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, i64, i64, i32, i32, i32, vp]
+    libs = {"this_tree": bind(L)}
+    if args.baseline_lib:
+        libs["baseline"] = bind(ctypes.CDLL(os.path.abspath(args.baseline_lib)))
+
+    def timed(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        med, samples = time_replays(replay, args.reps, args.launches)
+        q = sorted(samples)
+        return {"us": round(med, 2), "min_us": round(q[0], 2), "max_us": round(q[-1], 2)}
+
+    def check(l, rc):
+        if rc:
+            raise RuntimeError(l.fp4_hip_last_error().decode())
+
+    rng_of = lambda t: t["max_us"] - t["min_us"]  # noqa: E731
+    from torch_bnb_fp4.nested import dynamic_map
+
+    code = dynamic_map().to(dev)
+    cells = []
+    for M, K in SHAPES:
+        n = M * K
+        torch.manual_seed(0)
+        w16 = (torch.randn(n, device=dev) * 0.02).to(torch.float16)
+        packed = torch.empty(n // 2, dtype=torch.uint8, device=dev)
+        absmax = torch.empty(n // BS, dtype=torch.float32, device=dev)
+        check(L, L.fp4_hip_quantize_blockwise_nf4(p_(w16), DT[torch.float16], p_(packed), p_(absmax), n, BS, s()))
+        del w16
+        offset = float(absmax.mean())
+        q, nabs = pkg.ext.absmax_nest(absmax, offset, code, G)
+        expanded = pkg.ext.absmax_unnest(q, nabs, code, offset, G)
+        x = torch.randn(K, device=dev).to(dtype)
+        y = torch.empty(M, dtype=dtype, device=dev)
+        y2 = torch.empty(M, dtype=dtype, device=dev)
+        nested_call = lambda: check(L, L.fp4_hip_gemv_nested_nf4(p_(x), p_(packed), p_(q), p_(nabs), p_(code), offset, G, None, None, p_(y), M, K,  # noqa: E731
+                                                                 BS, dt, 0, s()))
+        fused_call = lambda: check(L, L.fp4_hip_gemv_fused_nf4(p_(x), p_(packed), p_(expanded), None, None, p_(y2), M, K, BS, dt, 0, s()))  # noqa: E731
+        nested_call(), fused_call()
+        torch.cuda.synchronize()
+        cell = {"M": M, "K": K, "bit_identical": bool(torch.equal(y, y2))}
+        tn, tf = timed(nested_call), timed(fused_call)
+        spread = rng_of(tn) + rng_of(tf)
+        delta = tn["us"] - tf["us"]
+        cell.update({"gemv_nf4_nested": tn, "gemv_nf4_fused_on_expanded": tf, "delta_us": round(delta, 2), "ratio": round(tn["us"] / tf["us"], 3),
+                     "spread_us": round(spread, 2), "verdict": "level" if abs(delta) <= spread else ("nested ahead" if delta < 0 else "nested behind")})
+        plain = {}
+        for tag, l in libs.items():
+            plain[tag] = timed(lambda: check(l, l.fp4_hip_gemv_nf4(p_(x), p_(packed), p_(expanded), None, p_(y2), M, K, BS, dt, s())))
+        if "baseline" in plain:
+            margin = max(rng_of(plain["this_tree"]), rng_of(plain["baseline"]))
+            plain.update({"margin_us": round(margin, 2), "delta_us": round(plain["this_tree"]["us"] - plain["baseline"]["us"], 2)})
+            plain["within_margin"] = bool(abs(plain["delta_us"]) <= margin)
+        cell["plain_gemv_nf4"] = plain
+        cell["absmax_unnest"] = timed(lambda: pkg.ext.absmax_unnest(q, nabs, code, offset, G))
+        for rows in (8, 64):
+            xb = torch.randn(rows, K, device=dev).to(dtype)
+            a = timed(lambda: pkg.ext.qlinear_nf4_nested(xb, packed, q, nabs, code, offset, G, M, K, BS, None))
+            b = timed(lambda: pkg.ext.qlinear_nf4(xb, packed, expanded, M, K, BS))
+            cell[f"qlinear_rows{rows}"] = {"qlinear_nf4_nested": a, "qlinear_nf4": b, "delta_us": round(a["us"] - b["us"], 2)}
+        resident = q.numel() + 4 * nabs.numel() + 4 * code.numel()
+        cell["statistics_bytes"] = {"resident": resident, "expanded": 4 * expanded.numel(), "packed_weight": packed.numel(),
+                                    "bits_per_weight_resident": round(8 * resident / n, 4), "bits_per_weight_expanded": round(32 * expanded.numel() / n, 4)}
+        cells.append(cell)
+        del packed, absmax, q, nabs, expanded
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "revision": args.revision, "dtype": "bf16", "blocksize": BS, "nested_blocksize": G,
+                      "launches_per_graph": args.launches, "reps": args.reps,
+                      "baseline_lib": "the parent commit's library, same run" if args.baseline_lib else "not measured",
+                      "plain_gemv_all_within_margin": (all(c["plain_gemv_nf4"]["within_margin"] for c in cells) if args.baseline_lib else None),
+                      "all_bit_identical": all(c["bit_identical"] for c in cells), "cells": cells}))
+
+
 def lora(args):
     dev = torch.device("cuda", 0)
     silu = torch.nn.functional.silu
@@ -345,12 +436,15 @@ def main():
     ap.add_argument("--wide-batch", action="store_true", help="the 17..128-row NF4 regime (profiles/nf4_wide_batch.json)")
     ap.add_argument("--revision", default="unknown", help="--wide-batch: the git revision the figures belong to, recorded as given")
     ap.add_argument("--fused", action="store_true", help="the fused NF4 decode epilogues (profiles/nf4_fused_epilogues.json)")
-    ap.add_argument("--baseline-lib", default=None, help="--fused: another build of libtorch_bnb_fp4_hip.so to time the plain calls of, side by side")
+    ap.add_argument("--baseline-lib", default=None, help="--fused / --nested: another build of libtorch_bnb_fp4_hip.so to time the plain calls of, side by side")
     ap.add_argument("--lora", action="store_true", help="LoRA adapters beside NF4 weights, fused against torch ops (profiles/nf4_lora.json)")
     ints = lambda v: [int(i) for i in v.split(",")]  # noqa: E731
     ap.add_argument("--lora-ranks", type=ints, default=[16, 64], help="--lora: adapter ranks (multiples of 8), comma-separated")
     ap.add_argument("--lora-rows", type=ints, default=[1, 8, 32, 64], help="--lora: activation row counts (1..64), comma-separated")
+    ap.add_argument("--nested", action="store_true", help="double-quantised absmax: the nested GEMV, unnest and qlinear_nf4_nested (profiles/nf4_nested.json)")
     args = ap.parse_args()
+    if args.nested:
+        return nested(args)
     if args.lora:
         return lora(args)
     if args.fused:

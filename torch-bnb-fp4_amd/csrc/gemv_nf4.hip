@@ -27,10 +27,18 @@
 // owns the row with 8 * l32 < R request 16 bytes of B[row] and their t slice before the weight stream, as x is requested; their
 // partial deltas go through a second copy of the dpp chain (not through p[it]: the plain sum keeps its order and its bits) and
 // sum + delta is one f32 add.  With KSPLIT > 1 only the kw == 0 wave of a row carries the term, through a column of its own in s_part.
+//
+// Nested (double-quantised) absmax (fp4_hip_gemv_nested_nf4): the NESTED instantiations (always FUSED, never LORA) read the block
+// scale as bitsandbytes' compress_statistics stores it - a uint8 code per block, an f32 scale per 256 blocks, a 256-entry f32 table
+// and an offset - and form absmax = fl32(fl32(table[code] * group) + offset) themselves (unnest_scale, nested_absmax.h): 33 instead
+// of 36 bytes streamed per 64 weights and a quarter of the resident statistics.  The table sits in LDS beside the NF4 table; the
+// code byte and the group scale are requested where the f32 scale was.  Everything after the scale is the FUSED kernel's, so the
+// result equals fp4_hip_gemv_fused_nf4 on the expanded absmax bit for bit.
 #include <atomic>
 
 #include "gemv_common.h"
 #include "lora_nf4.h"
+#include "nested_absmax.h"
 
 namespace fp4 {
 
@@ -80,13 +88,17 @@ struct OutPtr<true> {
 // FUSED = false: `residual` and `mode` are ignored (fp4_hip_gemv_nf4).  FUSED = true: the row epilogue adds the residual, and with
 // kModeSiluMulPairs (16-bit DT only, M even) rows (2i, 2i + 1) are a gate / up pair and out[i] = silu(gate_i) * up_i (+ residual[i]).
 // LORA = true (with FUSED): delta[row] = sum_j lora_B[row][j] * lora_t[j] (R % 8 == 0, 8 <= R <= 256) is added to the f32 row sum first.
-template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED, bool LORA = false>
+// NESTED = true (with FUSED, without LORA): `absmax` points at uint8 codes, one per block; the scale of block i is
+// unnest_scale(nested_code[code[i]], nested_absmax[i >> 8], nested_offset).
+template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED, bool LORA = false, bool NESTED = false>
 __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ x, const uint8_t *__restrict__ W,
                                                        const float *__restrict__ absmax, const void *__restrict__ bias,
                                                        typename OutPtr<FUSED>::type out, int M, int K, int bs_shift,
                                                        const void *residual_arg, int mode,  // new arguments last: the plain kernels keep their argument layout
-                                                       const void *lora_B, const float *lora_t, int R) {
+                                                       const void *lora_B, const float *lora_t, int R,
+                                                       const float *nested_absmax, const float *nested_code, float nested_offset) {
     static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
+    static_assert(!NESTED || (FUSED && !LORA), "nested absmax comes with the fused epilogues and without the adapter term");
     const void *residual = FUSED ? residual_arg : nullptr;
     [[maybe_unused]] const bool gated = FUSED && DT != FP4_DTYPE_F32 && (mode & kModeSiluMulPairs);
     constexpr int RG = 4 / KSPLIT;
@@ -94,6 +106,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
     constexpr int kBand = G * 32 * KSPLIT;  // chunks of K covered per pass
     __shared__ float s_lut[PAIR ? 1 : 16];
     __shared__ f32x2 s_pair[PAIR ? 256 : 1];
+    __shared__ float s_ncode[NESTED ? 256 : 1];
     __shared__ float s_part[kRowsPerBlock][KSPLIT + (LORA && KSPLIT > 1 ? 1 : 0)];  // LORA: column KSPLIT holds the row's delta
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -108,6 +121,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
     } else {
         if (tid < 16) s_lut[tid] = nf4_lut_entry(tid);
     }
+    if constexpr (NESTED) s_ncode[tid] = nested_code[tid];  // 256 threads, 256 entries
 
     int rowi[ITERS], rclamp[ITERS];
 #pragma unroll
@@ -158,17 +172,34 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
         }
         u32x4 wq[ITERS][G];
         float am[ITERS][G];
+        [[maybe_unused]] uint32_t aq[NESTED ? ITERS : 1][NESTED ? G : 1];  // NESTED: the block's code; am holds its group's scale
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 const int64_t chunk = int64_t(rclamp[it]) * C + cidx[g];
                 wq[it][g] = __builtin_nontemporal_load(Wv + chunk);
-                const float a = absmax[(chunk << 5) >> bs_shift];
-                am[it][g] = live[g] ? a : 0.0f;
+                if constexpr (NESTED) {
+                    const int64_t blk = (chunk << 5) >> bs_shift;
+                    aq[it][g] = reinterpret_cast<const uint8_t *>(absmax)[blk];
+                    am[it][g] = nested_absmax[blk >> kNestedGemvShift];
+                } else {
+                    const float a = absmax[(chunk << 5) >> bs_shift];
+                    am[it][g] = live[g] ? a : 0.0f;
+                }
             }
         }
-        if (cb == 0) __syncthreads();  // table visible (uniform: every thread runs the same passes)
+        if (cb == 0) __syncthreads();  // tables visible (uniform: every thread runs the same passes)
+        if constexpr (NESTED) {
+#pragma unroll
+            for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const float a = unnest_scale(s_ncode[aq[it][g]], am[it][g], nested_offset);
+                    am[it][g] = live[g] ? a : 0.0f;
+                }
+            }
+        }
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
 #pragma unroll
@@ -276,21 +307,26 @@ struct Nf4Args {
     const void *lora_B = nullptr;  // LORA instantiations only
     const float *lora_t = nullptr;
     int R = 0;
+    const float *nested_absmax = nullptr;  // NESTED instantiations only (absmax then points at the uint8 codes)
+    const float *nested_code = nullptr;
+    float nested_offset = 0.0f;
 };
 
-template <int DT, int KSPLIT, int G, int ITERS, bool FUSED, bool LORA>
+template <int DT, int KSPLIT, int G, int ITERS, bool FUSED, bool LORA, bool NESTED>
 void launch_nf4(bool pair, const Nf4Args &a) {
     constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
     const dim3 grid((unsigned)((a.M + rows_per_block - 1) / rows_per_block)), block(256);
     if (pair)
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED, LORA>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
-                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R);
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED, LORA, NESTED>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
+                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R, a.nested_absmax, a.nested_code,
+                           a.nested_offset);
     else
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED, LORA>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
-                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R);
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED, LORA, NESTED>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
+                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R, a.nested_absmax, a.nested_code,
+                           a.nested_offset);
 }
 
-template <int DT, bool FUSED, bool LORA = false>
+template <int DT, bool FUSED, bool LORA = false, bool NESTED = false>
 void dispatch_nf4(bool pair, const Nf4Args &a) {
     const int M = a.M, K = a.K;
     const int C = K >> 5;
@@ -301,9 +337,9 @@ void dispatch_nf4(bool pair, const Nf4Args &a) {
     while (iters < 4 && M / (2 * (4 / ks) * iters * 2) >= 256) iters *= 2;
 #define NF4_ITERS(KS, GG)                                                                                          \
     switch (iters) {                                                                                               \
-        case 1: return launch_nf4<DT, KS, GG, 1, FUSED, LORA>(pair, a);                                            \
-        case 2: return launch_nf4<DT, KS, GG, 2, FUSED, LORA>(pair, a);                                            \
-        default: return launch_nf4<DT, KS, GG, 4, FUSED, LORA>(pair, a);                                           \
+        case 1: return launch_nf4<DT, KS, GG, 1, FUSED, LORA, NESTED>(pair, a);                                           \
+        case 2: return launch_nf4<DT, KS, GG, 2, FUSED, LORA, NESTED>(pair, a);                                           \
+        default: return launch_nf4<DT, KS, GG, 4, FUSED, LORA, NESTED>(pair, a);                                          \
     }
     if (C <= 32) { NF4_ITERS(1, 1) }
     if (C <= 64) { NF4_ITERS(2, 1) }
@@ -323,10 +359,12 @@ namespace {
 
 // fused = false: fp4_hip_gemv_nf4 (irregular shapes run the generic kernel).  fused = true: fp4_hip_gemv_fused_nf4 (the fast path or
 // FP4_ERR_UNSUPPORTED with nothing launched).  `name` is the entry point the messages speak for.  lora = true (with fused):
-// fp4_hip_gemv_lora_nf4, the fused form plus the adapter term.
+// fp4_hip_gemv_lora_nf4, the fused form plus the adapter term.  nested_absmax != nullptr (with fused, without lora):
+// fp4_hip_gemv_nested_nf4 - `absmax` then points at the uint8 codes of the compressed statistics.
 int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                    const void *residual, void *out, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream,
-                   bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0) {
+                   bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0,
+                   const float *nested_absmax = nullptr, const float *nested_code = nullptr, float nested_offset = 0.0f) {
     if (M < 0 || K < 0 || (K & 1) || blocksize < 2 || (blocksize & 1)) {
         set_error("%s: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", name, (long long)M, (long long)K,
                   blocksize);
@@ -363,6 +401,17 @@ int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *p
                   "the plain GEMV and apply the epilogue separately",
                   name, (long long)M, (long long)K, blocksize, dtype, (mode & kModeSiluMulPairs) ? 1 : 0);
         return FP4_ERR_UNSUPPORTED;
+    }
+    if (nested_absmax) {
+        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
+        Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s};
+        a.nested_absmax = nested_absmax, a.nested_code = nested_code, a.nested_offset = nested_offset;
+        switch (dtype) {
+            case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, false, true>(pair, a); break;
+            case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, false, true>(pair, a); break;
+            default: dispatch_nf4<FP4_DTYPE_F32, true, false, true>(pair, a); break;
+        }
+        return check_launch(name);
     }
     if (lora) {
         if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
@@ -422,4 +471,31 @@ extern "C" int fp4_hip_gemv_lora_nf4(const void *x, const uint8_t *packed, const
     }
     return fp4::gemv_nf4_entry("fp4_hip_gemv_lora_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
                                epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R);
+}
+
+extern "C" int fp4_hip_gemv_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                       const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
+                                       void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
+    const char *name = "fp4_hip_gemv_nested_nf4";
+    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
+        fp4::set_error("%s: unknown epilogue %d", name, epilogue);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    if (nested_blocksize <= 0) {
+        fp4::set_error("%s: nested_blocksize=%d (need a positive group size)", name, nested_blocksize);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    if (M > 0 && K > 0 && (!nested_absmax || !code256)) {  // absmax_u8 is checked with the other operands
+        fp4::set_error("%s: null pointer", name);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    if (nested_blocksize != (1 << fp4::kNestedGemvShift)) {
+        fp4::set_error("%s: nested_blocksize %d is not covered (the GEMV reads groups of 256 blocks); expand the statistics with "
+                       "fp4_hip_absmax_unnest and run fp4_hip_gemv_fused_nf4", name, nested_blocksize);
+        return FP4_ERR_UNSUPPORTED;
+    }
+    // K == 0 never reaches a kernel: the fused form refuses it (not the fast path) before the statistics are looked at
+    return fp4::gemv_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, M, K, blocksize, dtype,
+                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, false, nullptr, nullptr, 0,
+                               nested_absmax, code256, offset);
 }

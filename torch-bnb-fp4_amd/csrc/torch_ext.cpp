@@ -14,7 +14,7 @@
 //   * qlinear_codebook* dequantise all M*N elements (the reference passes the BYTE count,
 //     csrc/torch_fp4.cpp:90,101, leaving half of the weight uninitialised).
 // Extra exports (not in the reference): the NF4 ops (dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4, qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4,
-// quantize_nf4: bitsandbytes' second 4-bit code, same kernels' shapes and dispatch; lora_down, gemv_nf4_lora, gemm_nf4_lora: LoRA adapters beside an NF4 weight), gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
+// quantize_nf4: bitsandbytes' second 4-bit code, same kernels' shapes and dispatch; lora_down, gemv_nf4_lora, gemm_nf4_lora: LoRA adapters beside an NF4 weight; absmax_unnest, absmax_nest, gemv_nf4_nested, qlinear_nf4_nested: double-quantised absmax), gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -690,6 +690,101 @@ torch::Tensor gemm_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absm
     return nf4_fused_impl("gemm_nf4_lora", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, &lora_B, &t);
 }
 
+// ---- nested (double-quantised) absmax: bitsandbytes' compress_statistics ------------------------------------------------------------
+// absmax_u8 uint8 [nb], nested_absmax float32 [ceil(nb / nested_blocksize)], code float32 [256], offset a Python float (passed to the
+// kernel by value: no device read of a host scalar, no sync).
+void check_nested(const char *op, const torch::Tensor &absmax_u8, const torch::Tensor &nested_absmax, const torch::Tensor &code,
+                  int64_t nested_blocksize, int64_t nb) {
+    check_gpu_contiguous(absmax_u8, "absmax_u8");
+    check_gpu_contiguous(nested_absmax, "nested_absmax");
+    check_gpu_contiguous(code, "nested_code");
+    TORCH_CHECK(absmax_u8.scalar_type() == torch::kUInt8, op, ": absmax_u8 must be uint8");
+    TORCH_CHECK(nested_absmax.scalar_type() == torch::kFloat32 && code.scalar_type() == torch::kFloat32, op,
+                ": nested_absmax and nested_code must be float32");
+    TORCH_CHECK(code.numel() == 256, op, ": nested_code must hold 256 entries, got ", code.numel());
+    TORCH_CHECK(nested_blocksize > 0, op, ": nested_blocksize must be positive");
+    TORCH_CHECK(absmax_u8.numel() >= nb, op, ": absmax_u8 holds ", absmax_u8.numel(), " codes, ", nb, " needed");
+    TORCH_CHECK(nested_absmax.numel() >= (nb + nested_blocksize - 1) / nested_blocksize, op, ": nested_absmax holds ", nested_absmax.numel(),
+                " group scales, ", (nb + nested_blocksize - 1) / nested_blocksize, " needed");
+    TORCH_CHECK(nested_absmax.device() == absmax_u8.device() && code.device() == absmax_u8.device(), op, ": all tensors must be on one device");
+}
+
+torch::Tensor absmax_unnest(torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code, double offset, int64_t nested_blocksize) {
+    const int64_t nb = absmax_u8.numel();
+    check_nested("absmax_unnest", absmax_u8, nested_absmax, code, nested_blocksize, nb);
+    torch::Tensor out = torch::empty({nb}, absmax_u8.options().dtype(torch::kFloat32));
+    c10::DeviceGuard guard(absmax_u8.device());
+    check_status(fp4_hip_absmax_unnest(absmax_u8.data_ptr<uint8_t>(), nested_absmax.data_ptr<float>(), code.data_ptr<float>(), (float)offset,
+                                       (int)nested_blocksize, nb, out.data_ptr<float>(), current_stream(absmax_u8)));
+    return out;
+}
+
+// (absmax float32 [nb], offset, code float32 [256], nested_blocksize) -> (absmax_u8 uint8 [nb], nested_absmax float32 [ceil(nb / g)])
+std::tuple<torch::Tensor, torch::Tensor> absmax_nest(torch::Tensor absmax, double offset, torch::Tensor code, int64_t nested_blocksize) {
+    check_gpu_contiguous(absmax, "absmax");
+    check_gpu_contiguous(code, "nested_code");
+    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && code.scalar_type() == torch::kFloat32, "absmax_nest: absmax and nested_code must be float32");
+    TORCH_CHECK(code.numel() == 256 && code.device() == absmax.device(), "absmax_nest: nested_code must hold 256 entries on absmax's device");
+    TORCH_CHECK(nested_blocksize > 0, "absmax_nest: nested_blocksize must be positive");
+    const int64_t nb = absmax.numel();
+    torch::Tensor q = torch::empty({nb}, absmax.options().dtype(torch::kUInt8));
+    torch::Tensor nested = torch::empty({(nb + nested_blocksize - 1) / nested_blocksize}, absmax.options());
+    c10::DeviceGuard guard(absmax.device());
+    check_status(fp4_hip_absmax_nest(absmax.data_ptr<float>(), nb, (float)offset, code.data_ptr<float>(), (int)nested_blocksize,
+                                     q.data_ptr<uint8_t>(), nested.data_ptr<float>(), current_stream(absmax)));
+    return {q, nested};
+}
+
+// gemv_nf4_fused reading the compressed statistics (fp4_hip_gemv_nested_nf4): A [1, K] / [1, 1, K] -> [.., m] or [.., m / 2]
+torch::Tensor gemv_nf4_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
+                              double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
+                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    const char *op = "gemv_nf4_nested";
+    check_gpu_contiguous(A, "A");
+    check_gpu_contiguous(B, "B");
+    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
+    const int64_t m = Bshape[0], k = Bshape[1];
+    TORCH_CHECK(blocksize > 0, op, ": blocksize must be positive");
+    check_nested(op, absmax_u8, nested_absmax, code, nested_blocksize, (m * k + blocksize - 1) / blocksize);
+    TORCH_CHECK(epilogue == FP4_EPILOGUE_NONE || epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS, op, ": unknown epilogue ", epilogue);
+    const int64_t m_out = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? m / 2 : m;
+    TORCH_CHECK(A.dim() >= 1 && k > 0 && A.size(-1) == k && A.numel() == k, op, " is batch-1 only: activation has ", A.numel(),
+                " elements, in_features is ", k);
+    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
+    TORCH_CHECK(B.device() == A.device() && absmax_u8.device() == A.device(), "all tensors must be on one device");
+    const int dt = to_fp4_dtype(A.scalar_type(), op);
+    auto shape = A.sizes().vec();
+    shape.back() = m_out;
+    torch::Tensor out = torch::empty(shape, A.options());
+    const void *bias_ptr = nullptr, *res_ptr = nullptr;
+    torch::Tensor bias_c, res_c;
+    if (bias.has_value()) {
+        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
+                    "] tensor of the activation dtype");
+        bias_c = bias->contiguous();
+        bias_ptr = bias_c.data_ptr();
+    }
+    if (residual.has_value()) {
+        TORCH_CHECK(residual->is_cuda() && residual->numel() == m_out && residual->scalar_type() == A.scalar_type() &&
+                        residual->device() == A.device(),
+                    "residual must hold ", m_out, " elements of the activation dtype on the activation's device");
+        res_c = residual->contiguous();
+        res_ptr = res_c.data_ptr();
+    }
+    c10::DeviceGuard guard(A.device());
+    check_status(fp4_hip_gemv_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(), nested_absmax.data_ptr<float>(),
+                                         code.data_ptr<float>(), (float)offset, (int)nested_blocksize, bias_ptr, res_ptr, out.data_ptr(), m, k,
+                                         blocksize, dt, epilogue, current_stream(A)));
+    return out;
+}
+
+// unnest into a temporary from the caching allocator (stream-ordered: no sync, capturable), then qlinear_nf4 / qlinear_nf4_bias
+torch::Tensor qlinear_nf4_nested(torch::Tensor A_in, torch::Tensor A, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
+                                 double offset, int64_t nested_blocksize, int M, int N, int blocksize, c10::optional<torch::Tensor> bias) {
+    torch::Tensor absmax = absmax_unnest(absmax_u8, nested_absmax, code, offset, nested_blocksize);
+    return qlinear_impl(A_in, A, absmax, M, N, blocksize, FP4_TABLE_NF4, bias);
+}
+
 // f32 partial sums of a K-split shard: [1, m] float32 (see fp4_hip_gemv_partial)
 torch::Tensor gemv_fp4_partial(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape) {
     check_gpu_contiguous(A, "A");
@@ -851,6 +946,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm_nf4_lora", &gemm_nf4_lora,
           "gemm_nf4_fused for 1..64 rows plus the adapter term: (A, B, absmax, blocksize, Bshape, bias|None, residual|None, epilogue, "
           "lora_B [m, R], t float32 [rows, R])");
+    m.def("absmax_unnest", &absmax_unnest,
+          "expand double-quantised absmax: (absmax_u8, nested_absmax, nested_code [256], offset, nested_blocksize) -> float32 [nb]");
+    m.def("absmax_nest", &absmax_nest,
+          "double-quantise absmax: (absmax float32 [nb], offset, nested_code [256], nested_blocksize) -> (absmax_u8, nested_absmax)");
+    m.def("gemv_nf4_nested", &gemv_nf4_nested,
+          "gemv_nf4_fused reading double-quantised absmax: (A, B, absmax_u8, nested_absmax, nested_code, offset, nested_blocksize, blocksize, "
+          "Bshape, bias|None, residual|None, epilogue)");
+    m.def("qlinear_nf4_nested", &qlinear_nf4_nested,
+          "absmax_unnest + NF4 dequant + linear: (A_in, A, absmax_u8, nested_absmax, nested_code, offset, nested_blocksize, M, N, blocksize, bias|None)");
     m.def("quantize_nf4", &quantize_nf4, "blockwise NF4 quantiser: (W, blocksize) -> (packed, absmax)");
     m.def("code_table", &code_table, "16-entry code table as a CPU float tensor");
     m.def("set_kernel_variant", &set_kernel_variant, "benchmark hook: select a kernel geometry");

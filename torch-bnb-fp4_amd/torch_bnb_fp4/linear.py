@@ -30,6 +30,8 @@ class TorchFP4Linear(nn.Module):
                 f"Linear weights are not quantized, and I have no idea what to do with that rn. Weights are {w.data.dtype}")
         self.quant_data = QuantData(w.data, w.quant_state, w.quant_state.shape, bias=lin.bias, original_lin=lin,
                                     use_codebook_dequant=self.use_codebook_dequant)
+        if getattr(w.quant_state, "nested", False):  # QuantData expanded the statistics: the wrapped layer follows (one copy, one truth)
+            w.quant_state = self.quant_data.quant_state
         self.register_buffer("qweight", self.quant_data.A, persistent=True)
         self.register_buffer("absmax", self.quant_data.absmax, persistent=True)
         self.register_buffer("code", self.quant_data.code, persistent=True)

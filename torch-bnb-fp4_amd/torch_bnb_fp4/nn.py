@@ -51,22 +51,44 @@ def check_quant_type(quant_type) -> str:
 
 
 class QuantState:
-    """Attribute-compatible subset of ``bitsandbytes.functional.QuantState`` (FP4 or NF4, no nested absmax)."""
+    """Attribute-compatible subset of ``bitsandbytes.functional.QuantState`` (FP4 or NF4).
+
+    A nested (double-quantised, ``compress_statistics``) state carries what bitsandbytes' carries: ``absmax`` holds uint8 codes,
+    ``state2`` is the state of those codes (``absmax`` = one f32 scale per ``blocksize`` = 256 blocks, ``code`` = the 256-entry
+    table), ``offset`` the value added back after decoding (a Python float here, a 0-d tensor in bitsandbytes) and ``nested`` is
+    True.  :func:`expand_quant_state` turns it into a plain one."""
 
     def __init__(self, absmax: torch.Tensor, shape, code: torch.Tensor, blocksize: int = 64,
-                 dtype: torch.dtype = torch.float16, quant_type: str = "fp4"):
+                 dtype: torch.dtype = torch.float16, quant_type: str = "fp4", offset=None, state2: "Optional[QuantState]" = None):
         self.absmax = absmax
-        self.shape = torch.Size(shape)
+        self.shape = None if shape is None else torch.Size(shape)
         self.code = code
         self.blocksize = int(blocksize)
         self.dtype = dtype
         self.quant_type = quant_type
-        self.nested = False
+        self.offset = offset
+        self.state2 = state2
+        self.nested = state2 is not None
 
     def to(self, device) -> "QuantState":
         self.absmax = self.absmax.to(device)
         self.code = self.code.to(device)
+        if self.state2 is not None:
+            self.state2.to(device)
         return self
+
+
+def expand_quant_state(state):
+    """``state`` itself if it is not nested, else a plain :class:`QuantState` with the f32 absmax the nested one decodes to
+    (``ext.absmax_unnest``, on the state's device; a bitsandbytes state with a tensor offset is read once, here)."""
+    if not getattr(state, "nested", False):
+        return state
+    s2 = state.state2
+    offset = state.offset
+    offset = float(offset.item() if isinstance(offset, torch.Tensor) else offset)
+    absmax = ext.absmax_unnest(state.absmax.reshape(-1).contiguous(), s2.absmax.float().contiguous(), s2.code.float().contiguous(), offset,
+                               int(s2.blocksize))
+    return QuantState(absmax, state.shape, state.code, state.blocksize, state.dtype, getattr(state, "quant_type", "fp4"))
 
 
 class Params4bit(nn.Parameter):
@@ -86,12 +108,22 @@ class Params4bit(nn.Parameter):
         return Params4bit(self.data.clone(), self.requires_grad, self.quant_state, self.blocksize, self.quant_type)
 
     @classmethod
-    def quantized_from(cls, dense: torch.Tensor, device, blocksize: int = 64, quant_type: str = "fp4") -> "Params4bit":
-        """Quantise like ``Params4bit.cuda()``: the weight is cast to fp16 first, then blockwise FP4 or NF4."""
+    def quantized_from(cls, dense: torch.Tensor, device, blocksize: int = 64, quant_type: str = "fp4",
+                       compress_statistics: bool = False) -> "Params4bit":
+        """Quantise like ``Params4bit.cuda()``: the weight is cast to fp16 first, then blockwise FP4 or NF4.
+        ``compress_statistics=True`` (bitsandbytes' argument of that name) double-quantises the absmax afterwards: offset =
+        absmax.mean(), groups of 256, the dynamic 8-bit map - the state is then a nested one (lossy in the scales)."""
         nf4 = check_quant_type(quant_type) == "nf4"
         w = dense.detach().contiguous().to(device=device, dtype=torch.float16)
         packed, absmax = (quantize_nf4 if nf4 else quantize_fp4)(w, blocksize)
         code = (nf4_code() if nf4 else fp4_code()).to(device)
+        if compress_statistics:
+            from .nested import nest_absmax
+
+            q, nested_absmax, nested_code, offset = nest_absmax(absmax)
+            state2 = QuantState(nested_absmax, None, nested_code, 256, torch.float32)
+            state = QuantState(q, dense.shape, code, blocksize, dense.dtype, quant_type, offset=offset, state2=state2)
+            return cls(packed, False, state, blocksize, quant_type)
         state = QuantState(absmax, dense.shape, code, blocksize, dense.dtype, quant_type)
         return cls(packed, False, state, blocksize, quant_type)
 

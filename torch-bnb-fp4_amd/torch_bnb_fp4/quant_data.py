@@ -38,7 +38,7 @@ import torch
 from ._ext import ext
 from .dtypes import ScalarType
 from .functional import dequantize_fp4_codebook_invoke_qtype, dequantize_fp4_qtype
-from .nn import check_quant_type
+from .nn import check_quant_type, expand_quant_state
 
 
 class QuantData:
@@ -48,6 +48,7 @@ class QuantData:
                  small_batch_fused: bool = False, small_batch_fused_nf4: bool = False,
                  wide_batch_fused_nf4: bool = False):
         self.use_codebook_dequant = use_codebook_dequant
+        state = expand_quant_state(state)  # a nested (double-quantised) state is expanded once: the kernels below take f32 absmax
         self.quant_type = check_quant_type(getattr(state, "quant_type", "fp4"))
         self.nf4 = self.quant_type == "nf4"
         self.A = A
