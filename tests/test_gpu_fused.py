@@ -246,3 +246,31 @@ def test_small_batch_epilogues(dtype, B, M, K):
     for a, b in ((gu, ref), (gur, ref + rh)):
         d = ulp_distance(bits(a), bits(b))
         assert d.max() <= 1 and (d == 0).mean() >= 0.998, (int(d.max()), float((d == 0).mean()))
+
+
+@pytest.mark.parametrize("dtype", DT16)
+def test_torch_ops_equal_the_c_abi_bit_for_bit(dtype):
+    """ext.gemv_fp4_fused is fp4_hip_gemv_fused and ext.gemm_small_fp4_fused is fp4_hip_gemm_small_fused - or fp4_hip_gemm_small_ws
+    where the library asks for a workspace (test_gpu_gemv.WS_SHAPE) - on the same operands, both epilogues, bias and residual."""
+    import torch_bnb_fp4 as pkg
+    from test_gpu_gemv import WS_SHAPE, randn_rows
+
+    M = 16
+    b = randn_rows(1, M, dtype, 3).view(-1) * 0.1
+    for rows, K in ((1, 64), (4, 512), (WS_SHAPE[0], WS_SHAPE[2])):
+        P, A = dev_case(M, K)
+        x = randn_rows(rows, K, dtype, rows)
+        for epi in (hipabi.EPILOGUE_NONE, hipabi.EPILOGUE_SILU_MUL_PAIRS):
+            m_out = M // 2 if epi == hipabi.EPILOGUE_SILU_MUL_PAIRS else M
+            r = randn_rows(rows, m_out, dtype, 9)
+            if rows == 1:
+                got = pkg.ext.gemv_fp4_fused(x, P.view(-1, 1).t(), A, 64, [M, K], b, r, epi)
+                want = hipabi.gemv_fused(x.view(-1), P, A, M, K, 64, b, r.view(-1), epi).view(1, -1)
+            else:
+                got = pkg.ext.gemm_small_fp4_fused(x, P.view(-1, 1).t(), A, 64, [M, K], b, r, epi)
+                if (rows, M, K) == WS_SHAPE:
+                    want, asked = hipabi.gemm_small_ws(x, P, A, M, K, 64, b, r, epi)
+                    assert asked > 0
+                else:
+                    want = hipabi.gemm_small_fused(x, P, A, M, K, 64, b, r, epi)
+            assert torch.equal(got, want) and got.shape == (rows, m_out)

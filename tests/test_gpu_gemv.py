@@ -506,3 +506,42 @@ def test_small_batch_f32_rows_are_the_f32_gemv_row_by_row(M, K, B):
     assert hipabi.gemm_small(nine, c.P, c.A, M, K, 64, expect_ok=False) == hipabi.ERR_UNSUPPORTED and "dequant + GEMM" in hipabi.last_error()
     if M % 2 == 0:
         assert hipabi.gemm_small_fused(x_t, c.P, c.A, M, K, 64, None, None, hipabi.EPILOGUE_SILU_MUL_PAIRS, expect_ok=False) == hipabi.ERR_UNSUPPORTED
+
+
+# ---- the torch ops over these entry points -------------------------------------------------------------------------------------------
+# The smallest (rows, M, K) at which fp4_hip_gemm_small_ws_bytes asks for a workspace (blocksize 64, a 16-bit dtype), so that
+# ext.gemm_small_fp4 / ext.gemm_small_fp4_fused take their workspace branch.  Found by calling that function through ctypes, which
+# needs no GPU, over rows 1..128, K = 64, 128, ..., 8192 and M = 1, 2, 8, 15, 16, 17, 32 in that order: the first hit is
+# (33, 16, 8192) -> 33792 bytes, and (32, 16, 8192), (33, 15, 8192), (33, 16, 8128) all return 0.
+WS_SHAPE = (33, 16, 8192)
+
+
+def randn_rows(rows, K, dtype, seed):
+    g = torch.Generator(device=dev()).manual_seed(seed)
+    return torch.randn(rows, K, device=dev(), generator=g).to(dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_torch_ops_equal_the_c_abi_bit_for_bit(dtype):
+    """ext.gemm_small_fp4 is fp4_hip_gemm_small - or fp4_hip_gemm_small_ws where the library asks for a workspace - and
+    ext.gemv_fp4_partial is fp4_hip_gemv_partial, on the same operands."""
+    import torch_bnb_fp4 as pkg
+
+    M = 16
+    for rows, K in ((4, 512), (WS_SHAPE[0], WS_SHAPE[2])):
+        c = case(M, K, 64, shape_seed(M, K))
+        x, b = randn_rows(rows, K, dtype, rows), randn_rows(1, M, dtype, 3).view(-1) * 0.1
+        for bias in (None, b):
+            got = pkg.ext.gemm_small_fp4(x, c.P.view(-1, 1).t(), c.A, 64, [M, K], bias)
+            if (rows, M, K) == WS_SHAPE:
+                want, asked = hipabi.gemm_small_ws(x, c.P, c.A, M, K, 64, bias)
+                assert asked > 0
+            else:
+                want = hipabi.gemm_small(x, c.P, c.A, M, K, 64, bias)
+            assert torch.equal(got, want) and got.shape == (rows, M)
+    K = 64
+    c = case(M, K, 64, shape_seed(M, K))
+    x = randn_rows(1, K, dtype, 1)
+    got = pkg.ext.gemv_fp4_partial(x, c.P.view(-1, 1).t(), c.A, 64, [M, K])
+    assert got.dtype == torch.float32 and got.shape == (1, M)
+    assert torch.equal(got.view(-1), hipabi.gemv_partial(x.view(-1), c.P, c.A, M, K, 64))

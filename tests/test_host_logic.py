@@ -217,6 +217,32 @@ def test_fused_layers_dispatch_and_fall_back(fake, monkeypatch):
         fused.FusedFP4Linear(dn.quant_data, epilogue=5)
 
 
+def test_the_fused_layers_share_one_forward_ladder():
+    from torch_bnb_fp4 import fused
+
+    assert fused.FusedNF4Linear.forward is fused.FusedFP4Linear.forward
+    assert fused.LoRANF4Linear.forward is not fused.FusedFP4Linear.forward  # its two-launch sequence is its own
+
+
+def test_residual_in_kernel_rule_at_its_corners(monkeypatch):
+    """The measured exception of the NF4 layers: the plain epilogue with more than 32 rows against rows of 8192 and more weights
+    leaves the residual add to torch; every other cell, and the FP4 layer everywhere, adds it in the kernel."""
+    from torch_bnb_fp4 import fused
+
+    monkeypatch.setattr(fused, "fp4_code", lambda: torch.from_numpy(o.TREE_TABLE.copy()))
+    monkeypatch.setattr(fused, "nf4_code", lambda: torch.from_numpy(o.TREE_TABLE.copy()))
+    packed, absmax = torch.zeros(32 * 64 // 2, 1, dtype=torch.uint8), torch.ones(32)
+    for epilogue in (fused.EPILOGUE_NONE, fused.EPILOGUE_SILU_MUL_PAIRS):
+        fp4 = fused.FusedFP4Linear.from_packed(packed, absmax, (32, 64), 64, epilogue=epilogue)
+        nf4 = fused.FusedNF4Linear.from_packed(packed, absmax, (32, 64), 64, epilogue=epilogue)
+        for rows in (32, 33):
+            for K in (8191, 8192):
+                left_to_torch = epilogue == fused.EPILOGUE_NONE and rows == 33 and K == 8192
+                assert fp4._residual_in_kernel(rows, K) is True
+                assert nf4._residual_in_kernel(rows, K) is (not left_to_torch), (epilogue, rows, K)
+                assert fused.LoRANF4Linear._residual_in_kernel(nf4, rows, K) is (not left_to_torch)
+
+
 def test_surgery_helpers_cpu():
     assert pkg.check_if_name_contained_in_list("model.lm_head", ["lm_head"])
     assert not pkg.check_if_name_contained_in_list("proj", ["lm_head", "pooler"])

@@ -42,3 +42,9 @@ with torch.inference_mode():
     bench("torch.add (one trivial torch op)", lambda: torch.add(x, x))
     xb = torch.randn(4, K, device=dev, dtype=torch.bfloat16)
     bench("TorchFP4Linear batch 4 (dequant + GEMM)", lambda: fp4(xb), n=1000)
+    # the fused weight ops of the extension, whose operand checks share one preamble (csrc/torch_ext.cpp: weight_op)
+    nf4_packed, nf4_absmax = pkg.ext.quantize_nf4(lin.weight.detach().contiguous(), 64)
+    nf4_B = nf4_packed.t()
+    bench("ext.gemv_nf4_fused (raw extension op)", lambda: pkg.ext.gemv_nf4_fused(x, nf4_B, nf4_absmax, 64, [M, K], None, None, 0))
+    bench("ext.gemm_nf4_fused 4 rows (raw extension op)", lambda: pkg.ext.gemm_nf4_fused(xb, nf4_B, nf4_absmax, 64, [M, K], None, None, 0))
+    bench("ext.gemm_small_fp4 4 rows (raw extension op)", lambda: pkg.ext.gemm_small_fp4(xb, qd._B_t, qd.absmax, 64, qd._shape_list, None))

@@ -13,8 +13,16 @@
 //   * launch / dtype failures raise instead of printf (csrc/dequant_fp4_optimized.cu:48-53,201-203);
 //   * qlinear_codebook* dequantise all M*N elements (the reference passes the BYTE count,
 //     csrc/torch_fp4.cpp:90,101, leaving half of the weight uninitialised).
-// Extra exports (not in the reference): the NF4 ops (dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4, qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4,
-// quantize_nf4: bitsandbytes' second 4-bit code, same kernels' shapes and dispatch; lora_down, gemv_nf4_lora, gemm_nf4_lora: LoRA adapters beside an NF4 weight; absmax_unnest, absmax_nest, gemv_nf4_nested, qlinear_nf4_nested: double-quantised absmax), gemv_fp4_bias, gemv_fp4_fused, comm_* / allreduce_oneshot, gemm_small_fp4, gemv_fp4_partial, quantize_fp4, set_kernel_variant, set_qlinear_gemm, code_table.
+// Extra exports (not in the reference):
+//   * FP4:    gemv_fp4_bias, gemv_fp4_fused, gemm_small_fp4, gemm_small_fp4_fused, gemv_fp4_partial, quantize_fp4;
+//   * NF4 (bitsandbytes' second 4-bit code, same shapes and dispatch): dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4,
+//     qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4, gemv_nf4_fused, gemm_nf4_fused, quantize_nf4;
+//   * LoRA adapters beside an NF4 weight: lora_down, gemv_nf4_lora, gemm_nf4_lora;
+//   * double-quantised absmax: absmax_unnest, absmax_nest, gemv_nf4_nested, qlinear_nf4_nested;
+//   * tensor parallelism: comm_alloc / comm_open / comm_close / comm_free / comm_status / comm_clear_status, allreduce_oneshot;
+//   * hooks: code_table, set_kernel_variant, set_qlinear_gemm.
+// The fused 4-bit weight ops (every *_fused, gemm_small_*, gemm_wide_nf4, *_lora, gemv_nf4_nested, gemv_fp4_partial) validate their
+// operands in one place, weight_op() below.
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -29,6 +37,7 @@
 #include <string>
 #include <tuple>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "torch_bnb_fp4_hip.h"
@@ -62,10 +71,27 @@ int to_fp4_dtype(torch::ScalarType t, const char *what) {
     }
 }
 
-void check_gpu_contiguous(const torch::Tensor &t, const char *name) {
-    // reference: CHECK_CUDA / CHECK_CONTIGUOUS (csrc/torch_fp4.cpp:19-20)
-    TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
-    TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+void check_gpu_contiguous(const torch::Tensor &t, const char *name, const char *op = nullptr) {
+    // reference: CHECK_CUDA / CHECK_CONTIGUOUS (csrc/torch_fp4.cpp:19-20); the ops beyond the reference's name themselves
+    const char *prefix = op ? op : "", *sep = op ? ": " : "";
+    TORCH_CHECK(t.is_cuda(), prefix, sep, name, " must be a CUDA tensor");
+    TORCH_CHECK(t.is_contiguous(), prefix, sep, name, " must be contiguous");
+}
+
+void check_on_device(const char *op, const char *name, const torch::Tensor &t, const torch::Tensor &A) {
+    TORCH_CHECK(t.device() == A.device(), op, ": ", name, " is on ", t.device(), ", the activation on ", A.device(),
+                "; all tensors must be on one device");
+}
+
+// an optional epilogue operand (bias, residual): `n` elements of `st` on `device`; `keep` holds the contiguous tensor the pointer is of
+const void *epilogue_operand(const char *op, const char *name, const c10::optional<torch::Tensor> &t, int64_t n, torch::ScalarType st,
+                             const torch::Device &device, torch::Tensor &keep) {
+    if (!t.has_value()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->numel() == n && t->scalar_type() == st && t->device() == device, op, ": ", name, " must hold ", n,
+                " elements of dtype ", st, " on the activation's device (", device, "); got ", t->numel(), " of ", t->scalar_type(), " on ",
+                t->device());
+    keep = t->contiguous();
+    return keep.data_ptr();
 }
 
 void check_status(int rc) {
@@ -98,30 +124,30 @@ void dequant_into(const torch::Tensor &A, const torch::Tensor &absmax, torch::Te
                                               n, dt, table, flags, current_stream(A)));
 }
 
-torch::Tensor dequantize_fp4(torch::Tensor A, torch::Tensor absmax, int blocksize, int M, int N, ScalarTypeEnum o_type) {
+torch::Tensor dequantize_impl(const torch::Tensor &A, const torch::Tensor &absmax, int blocksize, int M, int N, int64_t n,
+                              ScalarTypeEnum o_type, int table) {
     check_gpu_contiguous(A, "A");
     check_gpu_contiguous(absmax, "absmax");
     torch::Tensor out = torch::empty({M, N}, torch::TensorOptions().dtype(to_torch(o_type)).device(A.device()));
-    dequant_into(A, absmax, out, blocksize, int64_t(M) * N, FP4_TABLE_TREE);
+    dequant_into(A, absmax, out, blocksize, n, table);
     return out;
 }
 
+torch::Tensor dequantize_fp4(torch::Tensor A, torch::Tensor absmax, int blocksize, int M, int N, ScalarTypeEnum o_type) {
+    return dequantize_impl(A, absmax, blocksize, M, N, int64_t(M) * N, o_type, FP4_TABLE_TREE);
+}
+
+// the `codebook` tensor of the *_codebook ops is checked at most and never read, like the reference's (its kernels use CODE_PARAM)
 torch::Tensor dequantize_fp4_codebook(torch::Tensor A, torch::Tensor absmax, torch::Tensor codebook, int M, int N,
                                       int blocksize, int64_t n, ScalarTypeEnum dtype) {
     check_gpu_contiguous(A, "A");
     check_gpu_contiguous(absmax, "absmax");
-    check_gpu_contiguous(codebook, "codebook");  // checked but unused, like the reference (its kernels use CODE_PARAM)
-    torch::Tensor out = torch::empty({M, N}, torch::TensorOptions().dtype(to_torch(dtype)).device(A.device()));
-    dequant_into(A, absmax, out, blocksize, n, FP4_TABLE_CODEBOOK);
-    return out;
+    check_gpu_contiguous(codebook, "codebook");
+    return dequantize_impl(A, absmax, blocksize, M, N, n, dtype, FP4_TABLE_CODEBOOK);
 }
 
 torch::Tensor dequantize_nf4(torch::Tensor A, torch::Tensor absmax, int blocksize, int M, int N, ScalarTypeEnum o_type) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(absmax, "absmax");
-    torch::Tensor out = torch::empty({M, N}, torch::TensorOptions().dtype(to_torch(o_type)).device(A.device()));
-    dequant_into(A, absmax, out, blocksize, int64_t(M) * N, FP4_TABLE_NF4);
-    return out;
+    return dequantize_impl(A, absmax, blocksize, M, N, int64_t(M) * N, o_type, FP4_TABLE_NF4);
 }
 
 // ---- the dense GEMM of the batch > 1 path: hipBLASLt, called directly ------------------------------------------------------------
@@ -321,12 +347,10 @@ torch::Tensor qlinear_bias(torch::Tensor A_in, torch::Tensor A, torch::Tensor ab
 }
 torch::Tensor qlinear_codebook(torch::Tensor A_in, torch::Tensor A, torch::Tensor absmax, torch::Tensor codebook, int M, int N,
                                int blocksize) {
-    (void)codebook;
     return qlinear_impl(A_in, A, absmax, M, N, blocksize, FP4_TABLE_CODEBOOK, c10::nullopt);
 }
 torch::Tensor qlinear_codebook_bias(torch::Tensor A_in, torch::Tensor A, torch::Tensor absmax, torch::Tensor codebook, int M,
                                     int N, int blocksize, torch::Tensor bias) {
-    (void)codebook;
     return qlinear_impl(A_in, A, absmax, M, N, blocksize, FP4_TABLE_CODEBOOK, bias);
 }
 
@@ -362,13 +386,8 @@ torch::Tensor gemv_impl(const torch::Tensor &A, const torch::Tensor &B, const to
     TORCH_CHECK(B.device() == A.device() && absmax.device() == A.device(), "all tensors must be on one device");
     // reference output shape: [A.size(0), m] or [A.size(0), A.size(1), m] (csrc/gemv_fp4_optimized.cu:296-299)
     torch::Tensor out = A.dim() == 3 ? torch::empty({A.size(0), A.size(1), m}, A.options()) : torch::empty({A.size(0), m}, A.options());
-    const void *bias_ptr = nullptr;
     torch::Tensor bias_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == st, "bias must be a [", m, "] tensor of ", st);
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
+    const void *bias_ptr = epilogue_operand(op, "bias", bias, m, st, A.device(), bias_c);
     c10::DeviceGuard guard(A.device());
     const auto gemv = datatype ? fp4_hip_gemv : fp4_hip_gemv_nf4;
     check_status(gemv(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, out.data_ptr(), m, k, blocksize, (int)dtype,
@@ -393,262 +412,166 @@ torch::Tensor gemv_nf4_bias(torch::Tensor A, torch::Tensor B, torch::Tensor absm
     return gemv_impl(A, B, absmax, nullptr, blocksize, dtype, Bshape, bias);
 }
 
-// GEMV with a fused epilogue (fp4_hip_gemv_fused): bias, residual add, and - for a weight whose rows interleave a gate and an
-// up projection - silu(gate) * up.  A is [1, K] / [1, 1, K]; the result is [.., m] or, for the gated epilogue, [.., m / 2].
+// ---- the fused 4-bit weight ops: one validated preamble ----------------------------------------------------------------------------
+// Each op below takes an activation A [.., k], the packed weight B (uint8, two codes a byte), its float32 absmax (one scale per
+// `blocksize` weights) and Bshape = [m, k], optionally a bias [m] and a residual of the output's shape, and returns a fresh tensor:
+// A's shape with the last dimension replaced by m - or by m / 2 under the gated epilogue, silu(gate) * up over a weight whose rows
+// interleave a gate and an up projection.  weight_op() is the only place they validate and allocate; an op is then that call, the
+// device guard and the C ABI call it stands for.  One torch allocation (the output), no sync: every op can be captured in a graph.
+struct WeightOp {
+    const char *name;
+    int64_t max_rows;      // the op covers 1..max_rows activation rows; 1: a batch-1 GEMV
+    bool f32_out = false;  // the output is float32 [1, m] (gemv_fp4_partial), not of the activation's dtype and shape
+};
+
+struct WeightCall {
+    int64_t m, k, rows, m_out;
+    int dt;                            // FP4_DTYPE_* of the activation
+    torch::Tensor out, bias_c, res_c;  // bias_c / res_c own what bias_ptr / res_ptr point to
+    const void *bias_ptr, *res_ptr;
+};
+
+// absmax == nullptr: the op reads its scales from elsewhere (gemv_nf4_nested: check_nested)
+WeightCall weight_op(const WeightOp &op, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor *absmax, int blocksize,
+                     const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
+                     const c10::optional<torch::Tensor> &residual, int epilogue) {
+    check_gpu_contiguous(A, "A", op.name);
+    check_gpu_contiguous(B, "B", op.name);
+    if (absmax) check_gpu_contiguous(*absmax, "absmax", op.name);
+    TORCH_CHECK(Bshape.size() == 2, op.name, ": Bshape must be the [out_features, in_features] of the quantised weight");
+    WeightCall w;
+    const int64_t m = w.m = Bshape[0], k = w.k = Bshape[1];
+    TORCH_CHECK(epilogue == FP4_EPILOGUE_NONE || epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS, op.name, ": unknown epilogue ", epilogue);
+    w.m_out = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? m / 2 : m;
+    if (op.max_rows == 1) {
+        TORCH_CHECK(A.dim() >= 1 && k > 0 && A.size(-1) == k && A.numel() == k, op.name, " is batch-1 only: activation has ", A.numel(),
+                    " elements, in_features is ", k);
+        w.rows = 1;
+    } else {
+        TORCH_CHECK(A.dim() >= 1 && k > 0 && A.size(-1) == k, op.name, ": last dim of the activation must be in_features = ", k);
+        w.rows = A.numel() / k;
+        TORCH_CHECK(w.rows >= 1 && w.rows <= op.max_rows, op.name, " covers 1..", op.max_rows, " activation rows, got ", w.rows);
+    }
+    TORCH_CHECK(B.scalar_type() == torch::kUInt8 && B.numel() * 2 >= m * k, op.name, ": B must be uint8, ", (m * k + 1) / 2,
+                " bytes for a ", m, "x", k, " weight; B holds ", B.numel(), " of ", B.scalar_type(), ": too small");
+    if (absmax)
+        TORCH_CHECK(absmax->scalar_type() == torch::kFloat32 && absmax->numel() * int64_t(blocksize) >= m * k, op.name,
+                    ": Only fp32 absmax is supported, one scale per ", blocksize, " weights of a ", m, "x", k, " weight; absmax holds ",
+                    absmax->numel(), " of ", absmax->scalar_type(), ": absmax too small");
+    check_on_device(op.name, "B", B, A);
+    if (absmax) check_on_device(op.name, "absmax", *absmax, A);
+    w.dt = to_fp4_dtype(A.scalar_type(), op.name);
+    if (op.f32_out) {
+        w.out = torch::empty({1, m}, A.options().dtype(torch::kFloat32));
+    } else {
+        auto shape = A.sizes().vec();
+        shape.back() = w.m_out;
+        w.out = torch::empty(shape, A.options());
+    }
+    w.bias_ptr = epilogue_operand(op.name, "bias", bias, m, A.scalar_type(), A.device(), w.bias_c);
+    w.res_ptr = epilogue_operand(op.name, "residual", residual, w.rows * w.m_out, A.scalar_type(), A.device(), w.res_c);
+    return w;
+}
+
+// GEMV with a fused epilogue (fp4_hip_gemv_fused): bias, residual add, silu(gate) * up.  A is [1, K] / [1, 1, K].
 torch::Tensor gemv_fp4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    check_gpu_contiguous(absmax, "absmax");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be the [out_features, in_features] of the quantised weight");
-    const int64_t m = Bshape[0], k = Bshape[1];
-    TORCH_CHECK(epilogue == FP4_EPILOGUE_NONE || epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS, "gemv_fp4_fused: unknown epilogue ", epilogue);
-    const int64_t m_out = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? m / 2 : m;
-    const int dt = to_fp4_dtype(A.scalar_type(), "gemv_fp4_fused");
-    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32, "Only fp32 absmax is supported");
-    TORCH_CHECK(B.dtype() == torch::kUInt8, "B must be uint8");
-    TORCH_CHECK(A.dim() >= 1 && A.numel() == k && A.size(-1) == k, "gemv_fp4_fused is batch-1 only: activation has ", A.numel(),
-                " elements, in_features is ", k);
-    TORCH_CHECK(B.numel() * 2 >= m * k, "B holds ", B.numel(), " bytes, ", m * k / 2, " needed");
-    TORCH_CHECK(absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small for a ", m, "x", k, " weight");
-    TORCH_CHECK(B.device() == A.device() && absmax.device() == A.device(), "all tensors must be on one device");
-    auto shape = A.sizes().vec();
-    shape.back() = m_out;
-    torch::Tensor out = torch::empty(shape, A.options());
-    const void *bias_ptr = nullptr, *res_ptr = nullptr;
-    torch::Tensor bias_c, res_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
-                    "] tensor of the activation dtype");
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
-    if (residual.has_value()) {
-        TORCH_CHECK(residual->is_cuda() && residual->numel() == m_out && residual->scalar_type() == A.scalar_type() &&
-                        residual->device() == A.device(),
-                    "residual must hold ", m_out, " elements of the activation dtype on the activation's device");
-        res_c = residual->contiguous();
-        res_ptr = res_c.data_ptr();
-    }
+    WeightCall w = weight_op({"gemv_fp4_fused", 1}, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue);
     c10::DeviceGuard guard(A.device());
-    check_status(fp4_hip_gemv_fused(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(), m, k,
-                                    blocksize, dt, epilogue, current_stream(A)));
-    return out;
+    check_status(fp4_hip_gemv_fused(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, w.out.data_ptr(),
+                                    w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    return std::move(w.out);
 }
 
-// fused small-batch product: A [..., K] with 1..128 rows in total -> [..., m]; raises if the shape is not covered
+// Short weight x long rows: the split-K path of the FP4 small-batch product wants a scratch buffer (a second allocation, from torch's
+// caching allocator: no sync, graph-capturable).  True if the library asked for one and the call was made through it.
+bool gemm_small_fp4_with_workspace(const WeightCall &w, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
+                                   int blocksize, int epilogue) {
+    const int64_t ws_bytes = fp4_hip_gemm_small_ws_bytes(w.rows, w.m, w.k, blocksize, w.dt);
+    if (ws_bytes <= 0) return false;
+    torch::Tensor ws = torch::empty({ws_bytes}, A.options().dtype(torch::kUInt8));
+    check_status(fp4_hip_gemm_small_ws(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, w.out.data_ptr(),
+                                       w.rows, w.m, w.k, blocksize, w.dt, epilogue, ws.data_ptr(), ws_bytes, current_stream(A)));
+    return true;
+}
+
+// fused small-batch product (fp4_hip_gemm_small): A [..., K] with 1..128 rows in total; raises if the shape is not covered
 torch::Tensor gemm_small_fp4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
                              c10::optional<torch::Tensor> bias) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    check_gpu_contiguous(absmax, "absmax");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
-    const int64_t m = Bshape[0], k = Bshape[1];
-    TORCH_CHECK(A.dim() >= 1 && A.size(-1) == k, "gemm_small_fp4: last dim of the activation must be in_features = ", k);
-    const int64_t rows = A.numel() / k;
-    TORCH_CHECK(rows >= 1 && rows <= 128, "gemm_small_fp4 covers 1..128 activation rows, got ", rows);
-    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
-    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
-    const int dt = to_fp4_dtype(A.scalar_type(), "gemm_small_fp4");
-    auto shape = A.sizes().vec();
-    shape.back() = m;
-    torch::Tensor out = torch::empty(shape, A.options());
-    const void *bias_ptr = nullptr;
-    torch::Tensor bias_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
-                    "] tensor of the activation dtype");
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
+    WeightCall w = weight_op({"gemm_small_fp4", 128}, A, B, &absmax, blocksize, Bshape, bias, c10::nullopt, FP4_EPILOGUE_NONE);
     c10::DeviceGuard guard(A.device());
-    // short weight x long rows: the split-K path wants a scratch buffer (torch's caching allocator: no sync, graph-capturable)
-    const int64_t ws_bytes = fp4_hip_gemm_small_ws_bytes(rows, m, k, blocksize, dt);
-    if (ws_bytes > 0) {
-        torch::Tensor ws = torch::empty({ws_bytes}, A.options().dtype(torch::kUInt8));
-        check_status(fp4_hip_gemm_small_ws(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, nullptr, out.data_ptr(),
-                                           rows, m, k, blocksize, dt, FP4_EPILOGUE_NONE, ws.data_ptr(), ws_bytes, current_stream(A)));
-        return out;
-    }
-    check_status(fp4_hip_gemm_small(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, out.data_ptr(), rows, m,
-                                    k, blocksize, dt, current_stream(A)));
-    return out;
+    if (!gemm_small_fp4_with_workspace(w, A, B, absmax, blocksize, FP4_EPILOGUE_NONE))
+        check_status(fp4_hip_gemm_small(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.out.data_ptr(), w.rows,
+                                        w.m, w.k, blocksize, w.dt, current_stream(A)));
+    return std::move(w.out);
 }
 
-// fused NF4 small-batch product on the matrix cores (fp4_hip_gemm_small_nf4): A [..., K] with 1..16 rows in total -> [..., m];
-// raises if the shape is not covered (blocksize 64, K % 512 == 0, fp16 / bf16).  One allocation (the output), no sync: capturable.
-torch::Tensor gemm_small_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                             c10::optional<torch::Tensor> bias) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    check_gpu_contiguous(absmax, "absmax");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
-    const int64_t m = Bshape[0], k = Bshape[1];
-    TORCH_CHECK(A.dim() >= 1 && A.size(-1) == k, "gemm_small_nf4: last dim of the activation must be in_features = ", k);
-    const int64_t rows = A.numel() / k;
-    TORCH_CHECK(rows >= 1 && rows <= 16, "gemm_small_nf4 covers 1..16 activation rows, got ", rows);
-    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
-    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
-    const int dt = to_fp4_dtype(A.scalar_type(), "gemm_small_nf4");
-    auto shape = A.sizes().vec();
-    shape.back() = m;
-    torch::Tensor out = torch::empty(shape, A.options());
-    const void *bias_ptr = nullptr;
-    torch::Tensor bias_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
-                    "] tensor of the activation dtype");
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
-    c10::DeviceGuard guard(A.device());
-    check_status(fp4_hip_gemm_small_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, out.data_ptr(), rows, m,
-                                        k, blocksize, dt, current_stream(A)));
-    return out;
-}
-
-// fused NF4 wide-batch product on the matrix cores (fp4_hip_gemm_wide_nf4): A [..., K] with 1..128 rows in total -> [..., m];
-// raises if the shape is not covered (blocksize 64, K % 64 == 0, fp16 / bf16).  One allocation (the output), no sync: capturable.
-torch::Tensor gemm_wide_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                             c10::optional<torch::Tensor> bias) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    check_gpu_contiguous(absmax, "absmax");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
-    const int64_t m = Bshape[0], k = Bshape[1];
-    TORCH_CHECK(A.dim() >= 1 && A.size(-1) == k, "gemm_wide_nf4: last dim of the activation must be in_features = ", k);
-    const int64_t rows = A.numel() / k;
-    TORCH_CHECK(rows >= 1 && rows <= 128, "gemm_wide_nf4 covers 1..128 activation rows, got ", rows);
-    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
-    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
-    const int dt = to_fp4_dtype(A.scalar_type(), "gemm_wide_nf4");
-    auto shape = A.sizes().vec();
-    shape.back() = m;
-    torch::Tensor out = torch::empty(shape, A.options());
-    const void *bias_ptr = nullptr;
-    torch::Tensor bias_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
-                    "] tensor of the activation dtype");
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
-    c10::DeviceGuard guard(A.device());
-    check_status(fp4_hip_gemm_wide_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, out.data_ptr(), rows, m,
-                                        k, blocksize, dt, current_stream(A)));
-    return out;
-}
-
-// the small-batch product with the fused epilogues (fp4_hip_gemm_small_fused): A [..., K] with 1..128 rows -> [..., m] or [..., m / 2]
+// the small-batch product with the fused epilogues (fp4_hip_gemm_small_fused)
 torch::Tensor gemm_small_fp4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
                                    c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    check_gpu_contiguous(absmax, "absmax");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
-    const int64_t m = Bshape[0], k = Bshape[1];
-    TORCH_CHECK(epilogue == FP4_EPILOGUE_NONE || epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS, "gemm_small_fp4_fused: unknown epilogue ", epilogue);
-    const int64_t m_out = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? m / 2 : m;
-    TORCH_CHECK(A.dim() >= 1 && A.size(-1) == k, "gemm_small_fp4_fused: last dim of the activation must be in_features = ", k);
-    const int64_t rows = A.numel() / k;
-    TORCH_CHECK(rows >= 1 && rows <= 128, "gemm_small_fp4_fused covers 1..128 activation rows, got ", rows);
-    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
-    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
-    const int dt = to_fp4_dtype(A.scalar_type(), "gemm_small_fp4_fused");
-    auto shape = A.sizes().vec();
-    shape.back() = m_out;
-    torch::Tensor out = torch::empty(shape, A.options());
-    const void *bias_ptr = nullptr, *res_ptr = nullptr;
-    torch::Tensor bias_c, res_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
-                    "] tensor of the activation dtype");
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
-    if (residual.has_value()) {
-        TORCH_CHECK(residual->is_cuda() && residual->numel() == rows * m_out && residual->scalar_type() == A.scalar_type() &&
-                        residual->device() == A.device(),
-                    "residual must hold ", rows * m_out, " elements of the activation dtype on the activation's device");
-        res_c = residual->contiguous();
-        res_ptr = res_c.data_ptr();
-    }
+    WeightCall w = weight_op({"gemm_small_fp4_fused", 128}, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue);
     c10::DeviceGuard guard(A.device());
-    const int64_t ws_bytes = fp4_hip_gemm_small_ws_bytes(rows, m, k, blocksize, dt);
-    if (ws_bytes > 0) {
-        torch::Tensor ws = torch::empty({ws_bytes}, A.options().dtype(torch::kUInt8));
-        check_status(fp4_hip_gemm_small_ws(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(),
-                                           rows, m, k, blocksize, dt, epilogue, ws.data_ptr(), ws_bytes, current_stream(A)));
-        return out;
-    }
-    check_status(fp4_hip_gemm_small_fused(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(),
-                                          rows, m, k, blocksize, dt, epilogue, current_stream(A)));
-    return out;
+    if (!gemm_small_fp4_with_workspace(w, A, B, absmax, blocksize, epilogue))
+        check_status(fp4_hip_gemm_small_fused(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr,
+                                              w.out.data_ptr(), w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    return std::move(w.out);
 }
 
-// the NF4 twins of gemv_fp4_fused / gemm_small_fp4_fused (fp4_hip_gemv_fused_nf4 / fp4_hip_gemm_fused_nf4): A [.., K] with `rows`
-// rows in total -> [.., m] or, for the gated epilogue, [.., m / 2].  One allocation (the output), no sync: capturable.
+// fused NF4 products on the matrix cores; raise if the shape is not covered (blocksize 64, fp16 / bf16).  gemm_small_nf4
+// (fp4_hip_gemm_small_nf4): 1..16 rows, K % 512 == 0.  gemm_wide_nf4 (fp4_hip_gemm_wide_nf4): 1..128 rows, K % 64 == 0.
+torch::Tensor gemm_nf4_impl(const WeightOp &op, decltype(&fp4_hip_gemm_small_nf4) entry, const torch::Tensor &A, const torch::Tensor &B,
+                            const torch::Tensor &absmax, int blocksize, const std::vector<uint32_t> &Bshape,
+                            const c10::optional<torch::Tensor> &bias) {
+    WeightCall w = weight_op(op, A, B, &absmax, blocksize, Bshape, bias, c10::nullopt, FP4_EPILOGUE_NONE);
+    c10::DeviceGuard guard(A.device());
+    check_status(entry(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.out.data_ptr(), w.rows, w.m, w.k,
+                       blocksize, w.dt, current_stream(A)));
+    return std::move(w.out);
+}
+torch::Tensor gemm_small_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                             c10::optional<torch::Tensor> bias) {
+    return gemm_nf4_impl({"gemm_small_nf4", 16}, fp4_hip_gemm_small_nf4, A, B, absmax, blocksize, Bshape, bias);
+}
+torch::Tensor gemm_wide_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                            c10::optional<torch::Tensor> bias) {
+    return gemm_nf4_impl({"gemm_wide_nf4", 128}, fp4_hip_gemm_wide_nf4, A, B, absmax, blocksize, Bshape, bias);
+}
+
+// the operands of the LoRA forms: lora_B [m, R] of the activation dtype over the weight's rows, t [rows, R] float32 (lora_down); -> R
+int64_t check_lora(const char *op, const torch::Tensor &A, const WeightCall &w, const torch::Tensor &lora_B, const torch::Tensor &t) {
+    check_gpu_contiguous(lora_B, "lora_B", op);
+    check_gpu_contiguous(t, "t", op);
+    TORCH_CHECK(lora_B.dim() == 2 && lora_B.size(0) == w.m && lora_B.scalar_type() == A.scalar_type() && lora_B.device() == A.device(), op,
+                ": lora_B must be a [", w.m, ", R] tensor of the activation dtype on the activation's device");
+    const int64_t R = lora_B.size(1);
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.numel() == w.rows * R && t.device() == A.device(), op, ": t must hold ", w.rows * R,
+                " float32 elements (lora_down's output) on the activation's device");
+    return R;
+}
+
+// the NF4 twins of gemv_fp4_fused / gemm_small_fp4_fused (fp4_hip_gemv_fused_nf4 / fp4_hip_gemm_fused_nf4) and, given lora_B and
+// lora_t, their LoRA forms (fp4_hip_gemv_lora_nf4 / fp4_hip_gemm_lora_nf4)
 torch::Tensor nf4_fused_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
                              int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
                              const c10::optional<torch::Tensor> &residual, int epilogue, const torch::Tensor *lora_B = nullptr,
                              const torch::Tensor *lora_t = nullptr) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    check_gpu_contiguous(absmax, "absmax");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
-    const int64_t m = Bshape[0], k = Bshape[1];
-    TORCH_CHECK(epilogue == FP4_EPILOGUE_NONE || epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS, op, ": unknown epilogue ", epilogue);
-    const int64_t m_out = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? m / 2 : m;
-    TORCH_CHECK(A.dim() >= 1 && k > 0 && A.size(-1) == k, op, ": last dim of the activation must be in_features = ", k);
-    const int64_t rows = A.numel() / k;
-    TORCH_CHECK(!gemv || rows == 1, op, " is batch-1 only: activation has ", A.numel(), " elements, in_features is ", k);
-    TORCH_CHECK(rows >= 1 && rows <= 128, op, " covers 1..128 activation rows, got ", rows);
-    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
-    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
-    TORCH_CHECK(B.device() == A.device() && absmax.device() == A.device(), "all tensors must be on one device");
-    const int dt = to_fp4_dtype(A.scalar_type(), op);
-    auto shape = A.sizes().vec();
-    shape.back() = m_out;
-    torch::Tensor out = torch::empty(shape, A.options());
-    const void *bias_ptr = nullptr, *res_ptr = nullptr;
-    torch::Tensor bias_c, res_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
-                    "] tensor of the activation dtype");
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
-    if (residual.has_value()) {
-        TORCH_CHECK(residual->is_cuda() && residual->numel() == rows * m_out && residual->scalar_type() == A.scalar_type() &&
-                        residual->device() == A.device(),
-                    "residual must hold ", rows * m_out, " elements of the activation dtype on the activation's device");
-        res_c = residual->contiguous();
-        res_ptr = res_c.data_ptr();
-    }
+    WeightCall w = weight_op({op, gemv ? 1 : 128}, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue);
+    const int64_t R = lora_B ? check_lora(op, A, w, *lora_B, *lora_t) : 0;
     c10::DeviceGuard guard(A.device());
-    if (lora_B) {  // the LoRA forms: lora_B [m, R] of the activation dtype over the weight's rows, lora_t [rows, R] float32 (lora_down)
-        check_gpu_contiguous(*lora_B, "lora_B");
-        check_gpu_contiguous(*lora_t, "t");
-        TORCH_CHECK(lora_B->dim() == 2 && lora_B->size(0) == m && lora_B->scalar_type() == A.scalar_type() && lora_B->device() == A.device(),
-                    op, ": lora_B must be a [", m, ", R] tensor of the activation dtype on the activation's device");
-        const int64_t R = lora_B->size(1);
-        TORCH_CHECK(lora_t->scalar_type() == torch::kFloat32 && lora_t->numel() == rows * R && lora_t->device() == A.device(), op,
-                    ": t must hold ", rows * R, " float32 elements (lora_down's output) on the activation's device");
-        if (gemv)
-            check_status(fp4_hip_gemv_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, lora_B->data_ptr(),
-                              lora_t->data_ptr<float>(), R, out.data_ptr(), m, k, blocksize, dt, epilogue, current_stream(A)));
-        else
-            check_status(fp4_hip_gemm_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, lora_B->data_ptr(),
-                              lora_t->data_ptr<float>(), R, out.data_ptr(), rows, m, k, blocksize, dt, epilogue, current_stream(A)));
-        return out;
-    }
-    if (gemv)
-        check_status(fp4_hip_gemv_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(),
-                                            m, k, blocksize, dt, epilogue, current_stream(A)));
+    if (lora_B && gemv)
+        check_status(fp4_hip_gemv_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, lora_B->data_ptr(),
+                                           lora_t->data_ptr<float>(), R, w.out.data_ptr(), w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    else if (lora_B)
+        check_status(fp4_hip_gemm_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, lora_B->data_ptr(),
+                                           lora_t->data_ptr<float>(), R, w.out.data_ptr(), w.rows, w.m, w.k, blocksize, w.dt, epilogue,
+                                           current_stream(A)));
+    else if (gemv)
+        check_status(fp4_hip_gemv_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, w.out.data_ptr(),
+                                            w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
     else
-        check_status(fp4_hip_gemm_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), bias_ptr, res_ptr, out.data_ptr(),
-                                            rows, m, k, blocksize, dt, epilogue, current_stream(A)));
-    return out;
+        check_status(fp4_hip_gemm_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, w.out.data_ptr(),
+                                            w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    return std::move(w.out);
 }
 torch::Tensor gemv_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
@@ -740,42 +663,15 @@ torch::Tensor gemv_nf4_nested(torch::Tensor A, torch::Tensor B, torch::Tensor ab
                               double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
                               c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
     const char *op = "gemv_nf4_nested";
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features]");
-    const int64_t m = Bshape[0], k = Bshape[1];
     TORCH_CHECK(blocksize > 0, op, ": blocksize must be positive");
-    check_nested(op, absmax_u8, nested_absmax, code, nested_blocksize, (m * k + blocksize - 1) / blocksize);
-    TORCH_CHECK(epilogue == FP4_EPILOGUE_NONE || epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS, op, ": unknown epilogue ", epilogue);
-    const int64_t m_out = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? m / 2 : m;
-    TORCH_CHECK(A.dim() >= 1 && k > 0 && A.size(-1) == k && A.numel() == k, op, " is batch-1 only: activation has ", A.numel(),
-                " elements, in_features is ", k);
-    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " weight");
-    TORCH_CHECK(B.device() == A.device() && absmax_u8.device() == A.device(), "all tensors must be on one device");
-    const int dt = to_fp4_dtype(A.scalar_type(), op);
-    auto shape = A.sizes().vec();
-    shape.back() = m_out;
-    torch::Tensor out = torch::empty(shape, A.options());
-    const void *bias_ptr = nullptr, *res_ptr = nullptr;
-    torch::Tensor bias_c, res_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == A.scalar_type(), "bias must be a [", m,
-                    "] tensor of the activation dtype");
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
-    if (residual.has_value()) {
-        TORCH_CHECK(residual->is_cuda() && residual->numel() == m_out && residual->scalar_type() == A.scalar_type() &&
-                        residual->device() == A.device(),
-                    "residual must hold ", m_out, " elements of the activation dtype on the activation's device");
-        res_c = residual->contiguous();
-        res_ptr = res_c.data_ptr();
-    }
+    WeightCall w = weight_op({op, 1}, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue);
+    check_nested(op, absmax_u8, nested_absmax, code, nested_blocksize, (w.m * w.k + blocksize - 1) / blocksize);
+    check_on_device(op, "absmax_u8", absmax_u8, A);
     c10::DeviceGuard guard(A.device());
     check_status(fp4_hip_gemv_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(), nested_absmax.data_ptr<float>(),
-                                         code.data_ptr<float>(), (float)offset, (int)nested_blocksize, bias_ptr, res_ptr, out.data_ptr(), m, k,
-                                         blocksize, dt, epilogue, current_stream(A)));
-    return out;
+                                         code.data_ptr<float>(), (float)offset, (int)nested_blocksize, w.bias_ptr, w.res_ptr, w.out.data_ptr(),
+                                         w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    return std::move(w.out);
 }
 
 // unnest into a temporary from the caching allocator (stream-ordered: no sync, capturable), then qlinear_nf4 / qlinear_nf4_bias
@@ -785,22 +681,13 @@ torch::Tensor qlinear_nf4_nested(torch::Tensor A_in, torch::Tensor A, torch::Ten
     return qlinear_impl(A_in, A, absmax, M, N, blocksize, FP4_TABLE_NF4, bias);
 }
 
-// f32 partial sums of a K-split shard: [1, m] float32 (see fp4_hip_gemv_partial)
+// f32 partial sums of a K-split shard: [1, m] float32 (see fp4_hip_gemv_partial); Bshape is [out_features, in_features of this shard]
 torch::Tensor gemv_fp4_partial(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape) {
-    check_gpu_contiguous(A, "A");
-    check_gpu_contiguous(B, "B");
-    check_gpu_contiguous(absmax, "absmax");
-    TORCH_CHECK(Bshape.size() == 2, "Bshape must be [out_features, in_features_of_this_shard]");
-    const int64_t m = Bshape[0], k = Bshape[1];
-    TORCH_CHECK(A.numel() == k, "gemv_fp4_partial is batch-1 only: activation has ", A.numel(), " elements, shard K is ", k);
-    TORCH_CHECK(B.dtype() == torch::kUInt8 && B.numel() * 2 >= m * k, "B too small for a ", m, "x", k, " shard");
-    TORCH_CHECK(absmax.scalar_type() == torch::kFloat32 && absmax.numel() * int64_t(blocksize) >= m * k, "absmax too small");
-    const int dt = to_fp4_dtype(A.scalar_type(), "gemv_fp4_partial");
-    torch::Tensor out = torch::empty({1, m}, A.options().dtype(torch::kFloat32));
+    WeightCall w = weight_op({"gemv_fp4_partial", 1, true}, A, B, &absmax, blocksize, Bshape, c10::nullopt, c10::nullopt, FP4_EPILOGUE_NONE);
     c10::DeviceGuard guard(A.device());
-    check_status(fp4_hip_gemv_partial(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), out.data_ptr<float>(), m, k,
-                                      blocksize, dt, current_stream(A)));
-    return out;
+    check_status(fp4_hip_gemv_partial(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.out.data_ptr<float>(), w.m, w.k,
+                                      blocksize, w.dt, current_stream(A)));
+    return std::move(w.out);
 }
 
 // bitsandbytes-format FP4 / NF4 quantisation of a float tensor: returns (packed uint8[ceil(n/2), 1], absmax float32[ceil(n/bs)])
@@ -860,19 +747,9 @@ torch::Tensor allreduce_oneshot(torch::Tensor partial, std::vector<int64_t> peer
     const int64_t m = partial.numel();
     const torch::ScalarType st = to_torch(dtype);
     torch::Tensor out = torch::empty(partial.sizes(), partial.options().dtype(st));
-    const void *bias_ptr = nullptr, *res_ptr = nullptr;
     torch::Tensor bias_c, res_c;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == m && bias->scalar_type() == st, "bias must hold ", m, " elements of ", st);
-        bias_c = bias->contiguous();
-        bias_ptr = bias_c.data_ptr();
-    }
-    if (residual.has_value()) {
-        TORCH_CHECK(residual->is_cuda() && residual->numel() == m && residual->scalar_type() == st, "residual must hold ", m,
-                    " elements of ", st);
-        res_c = residual->contiguous();
-        res_ptr = res_c.data_ptr();
-    }
+    const void *bias_ptr = epilogue_operand("allreduce_oneshot", "bias", bias, m, st, partial.device(), bias_c);
+    const void *res_ptr = epilogue_operand("allreduce_oneshot", "residual", residual, m, st, partial.device(), res_c);
     std::vector<void *> bufs(world);
     for (int p = 0; p < world; ++p) bufs[p] = reinterpret_cast<void *>(peers[p]);
     c10::DeviceGuard guard(partial.device());

@@ -165,29 +165,47 @@ class FusedFP4Linear(nn.Module):
             y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
         return y if residual is None else y + residual
 
-    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    # forward()'s ladder is this class's alone; a subclass over another code names its two ops and says what its batched op covers
+    _gemv_op = "gemv_fp4_fused"
+    _batched_op = "gemm_small_fp4_fused"
+
+    def _batched_covers(self, rows: int, K: int, dtype: torch.dtype) -> bool:
         qd = self.quant_data
-        K = x.shape[-1]
+        return (2 <= rows <= 128 and dtype in (torch.float16, torch.bfloat16)
+                and ((qd.blocksize == 64 and K % 64 == 0) or (rows <= 8 and K % qd.blocksize == 0 and K % 32 == 0 and K <= 4096)))
+
+    def _residual_in_kernel(self, rows: int, K: int) -> bool:
+        """Whether the batched op adds the residual itself; where it does not, torch adds it to the op's output - T(t + r) either way."""
+        return True
+
+    def _fix_compute_dtype(self, x: torch.Tensor) -> None:
+        qd = self.quant_data
         if not qd.compute_dtype_set and x.numel():
             qd.set_compute_type(x)
             if qd.bias is not None:
                 self._buffers["bias"] = qd.bias  # the buffer follows the cast to the compute dtype
+
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        qd = self.quant_data
+        K = x.shape[-1]
+        self._fix_compute_dtype(x)
         if (self._fused_ok and x.numel() == K and K == self.in_features and x.ndim in (2, 3) and K % qd.blocksize == 0
                 and x.dtype == qd.o_type):
             if not x.is_contiguous():
                 x = x.contiguous()
             try:
-                return ext.gemv_fp4_fused(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual, self.epilogue)
+                return getattr(ext, self._gemv_op)(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual, self.epilogue)
             except RuntimeError as exc:
                 if "not available" not in str(exc):
                     raise
                 self._fused_ok = False  # shape outside the fused kernel's coverage: unfused sequence from now on
         rows = x.numel() // K if K else 0
-        if (self._small_ok and 2 <= rows <= 128 and K == self.in_features and x.dtype == qd.o_type and x.dtype in (torch.float16, torch.bfloat16)
-                and ((qd.blocksize == 64 and K % 64 == 0) or (rows <= 8 and K % qd.blocksize == 0 and K % 32 == 0 and K <= 4096))):
+        if self._small_ok and K == self.in_features and x.dtype == qd.o_type and self._batched_covers(rows, K, x.dtype):
+            in_kernel = residual is not None and self._residual_in_kernel(rows, K)
             try:  # batched decode: the same epilogues on the small-batch kernels
-                return ext.gemm_small_fp4_fused(x.contiguous(), qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual,
-                                                self.epilogue)
+                y = getattr(ext, self._batched_op)(x.contiguous(), qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias,
+                                                   residual if in_kernel else None, self.epilogue)
+                return y if in_kernel or residual is None else y + residual
             except RuntimeError as exc:
                 if "not covered" not in str(exc):
                     raise
@@ -216,37 +234,16 @@ class FusedNF4Linear(FusedFP4Linear):
     def _code(cls) -> torch.Tensor:
         return nf4_code()
 
-    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        qd = self.quant_data
-        K = x.shape[-1]
-        if not qd.compute_dtype_set and x.numel():
-            qd.set_compute_type(x)
-            if qd.bias is not None:
-                self._buffers["bias"] = qd.bias  # the buffer follows the cast to the compute dtype
-        if (self._fused_ok and x.numel() == K and K == self.in_features and x.ndim in (2, 3) and K % qd.blocksize == 0
-                and x.dtype == qd.o_type):
-            if not x.is_contiguous():
-                x = x.contiguous()
-            try:
-                return ext.gemv_nf4_fused(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual, self.epilogue)
-            except RuntimeError as exc:
-                if "not available" not in str(exc):
-                    raise
-                self._fused_ok = False  # shape outside the fused kernel's coverage: unfused sequence from now on
-        rows = x.numel() // K if K else 0
-        if (self._small_ok and 2 <= rows <= 64 and K == self.in_features and x.dtype == qd.o_type and x.dtype in (torch.float16, torch.bfloat16)
-                and qd.blocksize == 64 and K % 64 == 0):
-            # the one cell in which the fused residual add measured no gain: the add stays torch's (T(t + r) either way)
-            in_kernel = residual is not None and not (self.epilogue == EPILOGUE_NONE and rows > 32 and K >= 8192)
-            try:  # batched decode: the same epilogues on the matrix-core kernels
-                y = ext.gemm_nf4_fused(x.contiguous(), qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias,
-                                       residual if in_kernel else None, self.epilogue)
-                return y if in_kernel or residual is None else y + residual
-            except RuntimeError as exc:
-                if "not covered" not in str(exc):
-                    raise
-                self._small_ok = False
-        return self._unfused(x, residual)
+    _gemv_op = "gemv_nf4_fused"
+    _batched_op = "gemm_nf4_fused"
+
+    def _batched_covers(self, rows: int, K: int, dtype: torch.dtype) -> bool:
+        return 2 <= rows <= 64 and dtype in (torch.float16, torch.bfloat16) and self.quant_data.blocksize == 64 and K % 64 == 0
+
+    def _residual_in_kernel(self, rows: int, K: int) -> bool:
+        # the one cell in which the fused residual add measured no gain (profiles/nf4_fused_epilogues.json): more than 32 rows against
+        # rows of 8192 and more weights with the plain epilogue - there the add stays torch's
+        return not (self.epilogue == EPILOGUE_NONE and rows > 32 and K >= 8192)
 
 
 LORA_RANK_MULTIPLE = 8  # the kernels read B and t in 16-byte units
@@ -400,10 +397,7 @@ class LoRANF4Linear(FusedNF4Linear):
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         qd = self.quant_data
         K = x.shape[-1]
-        if not qd.compute_dtype_set and x.numel():
-            qd.set_compute_type(x)
-            if qd.bias is not None:
-                self._buffers["bias"] = qd.bias  # the buffer follows the cast to the compute dtype
+        self._fix_compute_dtype(x)
         rows = x.numel() // K if K else 0
         if self._lora_ok and rows >= 1 and K == self.in_features and x.dtype == qd.o_type and K % qd.blocksize == 0:
             one = rows == 1 and x.ndim in (2, 3) and self._fused_ok
@@ -419,9 +413,8 @@ class LoRANF4Linear(FusedNF4Linear):
                         raise
                     self._lora_ok = False
                     return self._adapter_in_torch(x, residual)
-                # the parent's measured exception holds here as well (the store loop is the same one): more than 32 rows against
-                # rows of 8192 and more weights with the plain epilogue leave the residual add to torch, T(t + r) either way
-                in_kernel = residual is not None and not (many and self.epilogue == EPILOGUE_NONE and rows > 32 and K >= 8192)
+                # the parent's measured exception holds here as well (the store loop is the same one)
+                in_kernel = residual is not None and self._residual_in_kernel(rows, K)
                 try:
                     op = ext.gemv_nf4_lora if one else ext.gemm_nf4_lora
                     y = op(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual if in_kernel else None, self.epilogue, B, t)
