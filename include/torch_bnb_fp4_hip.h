@@ -130,6 +130,9 @@ FP4_HIP_API int fp4_hip_gemv_fused(const void *x, const uint8_t *packed, const f
  * where that kernel does not apply the rows are split evenly over ceil(B/16) launches, each streaming the weight once.
  * 65..128 rows: two even chunks of at most 64.  Measured against dequant + hipBLASLt GEMM on MI355X
  * (profiles/r02_wide_batch_17_to_128_rows.txt): 1.7-3.1x faster at 17..64 rows, 1.27-1.6x at 65..128.
+ * FP4_OK without a launch for B == 0 or M == 0; B > 128, a negative size or a null pointer: FP4_ERR_INVALID_ARGUMENT.  A refused
+ * call (either error code) launches nothing and leaves out untouched - also at 17..128 rows, where every chunk has the same shape
+ * and the first one is refused.
  */
 FP4_HIP_API int fp4_hip_gemm_small(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                                    int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream);
@@ -140,7 +143,10 @@ FP4_HIP_API int fp4_hip_gemm_small(const void *x, const uint8_t *packed, const f
  *                             out : T[B, M], residual : T[B, M].
  *   EPILOGUE_SILU_MUL_PAIRS:  rows interleave gate and up (row 2i / 2i+1): g = T(sum_2i + bias_2i), u = T(sum_2i+1 + bias_2i+1),
  *                             t = T(T(silu(g)) * u); if residual: t = T(t + residual[b][i]);  out, residual : T[B, M/2], M even.
- * Same shape coverage and FP4_ERR_UNSUPPORTED behaviour as fp4_hip_gemm_small.  Not in the reference.
+ * `residual` may alias `out` under either epilogue (h = h + Linear(a) in place): on every path - the 16-row kernels, the one-pass
+ * kernels, the 16-row and 64-row chunking - each output element is read and then written by the one thread that owns it.
+ * Same shape coverage and FP4_ERR_UNSUPPORTED behaviour as fp4_hip_gemm_small; an unknown epilogue, or the gated one with an odd M
+ * ("even row count"): FP4_ERR_INVALID_ARGUMENT.  Not in the reference.
  */
 FP4_HIP_API int fp4_hip_gemm_small_fused(const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                              const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype,
@@ -152,7 +158,8 @@ FP4_HIP_API int fp4_hip_gemm_small_fused(const void *x, const uint8_t *packed, c
  * slices go through `workspace` and a second small launch adds them in a fixed order and applies the epilogue (deterministic, no
  * atomics).  fp4_hip_gemm_small_ws_bytes returns the bytes that path wants for a shape, or 0 where it would not be used (then, or
  * with workspace == NULL or too small, the call is exactly fp4_hip_gemm_small_fused).  16-byte aligned workspace; it may be reused by
- * the next call on the same stream.  Not in the reference.
+ * the next call on the same stream; no byte beyond the returned size is written.  `residual` may alias `out` here too: the
+ * reducing launch reads and writes each output element from one thread (the workspace must not overlap either).  Not in the reference.
  */
 FP4_HIP_API int64_t fp4_hip_gemm_small_ws_bytes(int64_t B, int64_t M, int64_t K, int blocksize, int dtype);
 FP4_HIP_API int fp4_hip_gemm_small_ws(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,

@@ -78,8 +78,9 @@ def dequantize(packed: torch.Tensor, absmax: torch.Tensor, blocksize: int, n: in
 
 
 def gemv(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: int, K: int, blocksize: int,
-         bias: torch.Tensor | None = None) -> torch.Tensor:
-    out = torch.empty(M, dtype=x.dtype, device=x.device)
+         bias: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    if out is None:
+        out = torch.empty(M, dtype=x.dtype, device=x.device)
     rc = lib().fp4_hip_gemv(_ptr(x), _ptr(packed), _ptr(absmax), _ptr(bias), _ptr(out), M, K, blocksize, DT[x.dtype], _stream())
     assert rc == OK, (rc, last_error())
     return out
@@ -102,9 +103,10 @@ def gemv_fused(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: i
 
 
 def gemm_small(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: int, K: int, blocksize: int,
-               bias: torch.Tensor | None = None, expect_ok: bool = True):
+               bias: torch.Tensor | None = None, expect_ok: bool = True, out: torch.Tensor | None = None):
     B = x.numel() // K
-    out = torch.empty(B, M, dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty(B, M, dtype=x.dtype, device=x.device)
     rc = lib().fp4_hip_gemm_small(_ptr(x), _ptr(packed), _ptr(absmax), _ptr(bias), _ptr(out), B, M, K, blocksize, DT[x.dtype], _stream())
     if expect_ok is None:  # the caller looks at both
         return rc, out
@@ -116,8 +118,9 @@ def gemm_small(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: i
 
 def gemm_small_ws(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: int, K: int, blocksize: int,
                   bias: torch.Tensor | None = None, residual: torch.Tensor | None = None, epilogue: int = EPILOGUE_NONE,
-                  workspace: torch.Tensor | None = None):
-    """fp4_hip_gemm_small_ws with a workspace of the size the library asks for (or the one given); returns (out, bytes asked)."""
+                  workspace: torch.Tensor | None = None, out: torch.Tensor | None = None):
+    """fp4_hip_gemm_small_ws with a workspace of the size the library asks for (or the one given, which may be a view into a larger
+    buffer); returns (out, bytes asked)."""
     B = x.numel() // K
     l = lib()
     l.fp4_hip_gemm_small_ws_bytes.restype = ctypes.c_int64
@@ -125,20 +128,22 @@ def gemm_small_ws(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M
     want = l.fp4_hip_gemm_small_ws_bytes(B, M, K, blocksize, DT[x.dtype])
     if workspace is None and want > 0:
         workspace = torch.empty(want, dtype=torch.uint8, device=x.device)
-    out = torch.empty(B, M // 2 if epilogue == EPILOGUE_SILU_MUL_PAIRS else M, dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty(B, M // 2 if epilogue == EPILOGUE_SILU_MUL_PAIRS else M, dtype=x.dtype, device=x.device)
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     l.fp4_hip_gemm_small_ws.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, i64, vp]
     rc = l.fp4_hip_gemm_small_ws(_ptr(x), _ptr(packed), _ptr(absmax), _ptr(bias), _ptr(residual), _ptr(out), B, M, K, blocksize, DT[x.dtype],
-                                 epilogue, _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream())
+                                 epilogue, _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(), _stream())
     assert rc == OK, (rc, last_error())
     return out, want
 
 
 def gemm_small_fused(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: int, K: int, blocksize: int,
                      bias: torch.Tensor | None = None, residual: torch.Tensor | None = None, epilogue: int = EPILOGUE_NONE,
-                     expect_ok: bool = True):
+                     expect_ok: bool = True, out: torch.Tensor | None = None):
     B = x.numel() // K
-    out = torch.empty(B, M // 2 if epilogue == EPILOGUE_SILU_MUL_PAIRS else M, dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty(B, M // 2 if epilogue == EPILOGUE_SILU_MUL_PAIRS else M, dtype=x.dtype, device=x.device)
     rc = lib().fp4_hip_gemm_small_fused(_ptr(x), _ptr(packed), _ptr(absmax), _ptr(bias), _ptr(residual), _ptr(out), B, M, K, blocksize,
                                         DT[x.dtype], epilogue, _stream())
     if expect_ok:
@@ -147,17 +152,21 @@ def gemm_small_fused(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor
     return rc
 
 
-def gemv_partial(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: int, K: int, blocksize: int) -> torch.Tensor:
-    out = torch.empty(M, dtype=torch.float32, device=x.device)
+def gemv_partial(x: torch.Tensor, packed: torch.Tensor, absmax: torch.Tensor, M: int, K: int, blocksize: int,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    if out is None:
+        out = torch.empty(M, dtype=torch.float32, device=x.device)
     rc = lib().fp4_hip_gemv_partial(_ptr(x), _ptr(packed), _ptr(absmax), _ptr(out), M, K, blocksize, DT[x.dtype], _stream())
     assert rc == OK, (rc, last_error())
     return out
 
 
-def quantize(w: torch.Tensor, blocksize: int = 64):
+def quantize(w: torch.Tensor, blocksize: int = 64, packed: torch.Tensor | None = None, absmax: torch.Tensor | None = None):
     n = w.numel()
-    packed = torch.empty((n + 1) // 2, dtype=torch.uint8, device=w.device)
-    absmax = torch.empty((n + blocksize - 1) // blocksize, dtype=torch.float32, device=w.device)
+    if packed is None:
+        packed = torch.empty((n + 1) // 2, dtype=torch.uint8, device=w.device)
+    if absmax is None:
+        absmax = torch.empty((n + blocksize - 1) // blocksize, dtype=torch.float32, device=w.device)
     rc = lib().fp4_hip_quantize_blockwise(_ptr(w), DT[w.dtype], _ptr(packed), _ptr(absmax), n, blocksize, _stream())
     assert rc == OK, (rc, last_error())
     return packed, absmax

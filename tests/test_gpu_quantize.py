@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import fp4_constructed as C
 import hipabi
 from gpu_util import dev, to_dev
 from oracle import c_oracle, fp4_oracle as o
@@ -42,6 +43,56 @@ def test_quantize_matches_oracle(dtype, bs):
     if n % 2:  # the unused low nibble of the last byte is zero in both
         assert got[-1] & 0x0F == 0
     assert np.array_equal(got, want_p)
+
+
+def _tail_lengths(bs):
+    """Around the 2048 / 4096 / 8192-element tiles of the tiles and persistent kernels, plus the shortest inputs."""
+    return sorted({1, 3, 7, 9, bs - 1, bs + 1, 2047, 2049, 4095, 4097, 8191, 8193, 3 * 4096 + bs + 3})
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("bs", [32, 64, 128, 256, 512, 1024, 2048, 4096])
+def test_quantize_odd_and_ragged_lengths_between_guards(dtype, bs):
+    """fp4_hip_quantize_blockwise writes exactly ceil(n / 2) bytes and ceil(n / bs) scales: `packed` sits between 0xA5 guards and
+    `absmax` between f32 sentinel guards (both views 4-byte aligned), w is a view at a 16-byte offset inside a larger buffer.  Every
+    kernel variant, ragged lengths around each tile size, the last block plain, all zero, holding an inf, or holding a NaN; the
+    spare low nibble of an odd n is 0."""
+    rng = np.random.default_rng(bs)
+    off = 16 // torch.empty(0, dtype=dtype).element_size()
+    for n in _tail_lengths(bs):
+        last = (n - 1) // bs * bs
+        for tail in ("plain", "zero", "inf", "nan"):
+            w32 = rng.standard_normal(n).astype(np.float32)
+            if tail == "zero":
+                w32[last:] = 0.0
+            elif tail == "inf":
+                w32[last + (n - last) // 2] = -np.inf
+            elif tail == "nan":
+                w32[n - 1] = np.nan
+            holder = torch.zeros(n + 2 * off, dtype=dtype, device=dev())
+            w = holder[off:off + n]
+            w.copy_(torch.from_numpy(w32).to(dtype))
+            assert w.data_ptr() % 16 == 0 and w.data_ptr() != holder.data_ptr()
+            want_p, want_a = o.quantize_fp4(w.float().cpu().numpy(), bs)
+            assert want_p.size == (n + 1) // 2 and want_a.size == -(-n // bs)
+            pbuf, packed = C.guarded(want_p.size, torch.uint8, 64, dev())
+            abuf, absmax = C.guarded(want_a.size, torch.float32, 16, dev())
+            assert packed.data_ptr() % 4 == 0 and absmax.data_ptr() % 4 == 0
+            for variant in (0, 4, 1001, 1002, 1004):
+                C.refill(pbuf)
+                C.refill(abuf)
+                hipabi.set_variant("quantize", variant)
+                try:
+                    hipabi.quantize(w, bs, packed=packed, absmax=absmax)
+                finally:
+                    hipabi.set_variant("quantize", 0)
+                what = (n, tail, variant)
+                assert C.guards_intact(pbuf, want_p.size, 64) and C.guards_intact(abuf, want_a.size, 16), what
+                got = packed.cpu().numpy()
+                assert np.array_equal(got, want_p), (what, np.flatnonzero(got != want_p)[:8])
+                np.testing.assert_array_equal(absmax.cpu().numpy(), want_a)  # NaN == NaN here
+                if n % 2:
+                    assert got[-1] & 0x0F == 0, what
 
 
 def _check(w_t, bs):

@@ -734,14 +734,15 @@ int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *ab
 namespace {
 int gemm_small_entry(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual, void *out,
                      int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream) {
-    if (B < 1 || B > 128 || M < 0 || K <= 0) {
-        set_error("fp4_hip_gemm_small: B=%lld M=%lld K=%lld (need 1 <= B <= 128)", (long long)B, (long long)M, (long long)K);
+    if (B < 0 || B > 128 || M < 0 || K <= 0) {
+        set_error("fp4_hip_gemm_small: B=%lld M=%lld K=%lld (need 0 <= B <= 128, M >= 0, K > 0)", (long long)B, (long long)M, (long long)K);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     if ((mode & kModeSiluMulPairs) && (M & 1)) {
         set_error("fp4_hip_gemm_small_fused: the gate|up epilogue needs an even row count, got M=%lld", (long long)M);
         return FP4_ERR_INVALID_ARGUMENT;
     }
+    if (B == 0) return FP4_OK;  // an empty batch is no error (as M == 0 below, and as the NF4 entry points): nothing to launch
     const int64_t M_out = (mode & kModeSiluMulPairs) ? M / 2 : M;
     if (dtype == FP4_DTYPE_F32) {
         // f32 activations (the reference's sanity harness; models run 16-bit): no matrix-core kernel and none needed - up to 8 rows run
