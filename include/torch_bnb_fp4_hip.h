@@ -235,6 +235,10 @@ FP4_HIP_API int fp4_hip_quantize_blockwise(const void *w, int w_dtype, uint8_t *
  *
  * fp4_hip_gemv_nf4: the batch-1 GEMV of fp4_hip_gemv over an NF4 weight; same arguments, shape coverage, bias rule
  * (T(f32(T(sum)) + f32(bias)) for 16-bit T) and error codes.  The f32 code values are used as they are (f32 accumulation).
+ *   Non-finite activations (this entry point and fp4_hip_gemv_fused_nf4 / _lora_nf4 / _nested_nf4): a NaN or an infinite x[k] makes
+ *   the outputs it enters non-finite - at batch 1 that is every out[r]; whether such an output is NaN or a signed infinity is
+ *   unspecified (the fast path loads branch-free: lanes past the end of a row re-read its last 32 activations under a zero scale,
+ *   so an infinity there also arrives as 0 * Inf).
  *
  * fp4_hip_quantize_blockwise_nf4: arguments as fp4_hip_quantize_blockwise.  absmax = max|w|, x = w * (1/absmax) in f32,
  *   nibble = #{ i : x > T[i] } over the 15 f32 midpoints T[i] = f32((code[i] + code[i+1]) / 2) (strict >; NaN -> 0, so an
@@ -315,6 +319,8 @@ FP4_HIP_API int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, con
  * x : T[Bt, K], A : T[R, K] row-major, scale : float[R] (one factor per adapter row, so stacked adapters may differ), t : float[Bt, R].
  * Covered: 1 <= Bt <= 64, R % 8 == 0 with 8 <= R <= 256 (pad A with zero rows), K % 8 == 0 (K <= 2^24), fp16 / bf16 / f32,
  * x and A 16-byte aligned.  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, t untouched.  FP4_OK without a launch for Bt == 0.
+ * A NaN or an infinite x[b][k] makes every t[b][j] of its own row b non-finite and touches no other row; NaN versus a signed infinity
+ * is unspecified (units past the end of K re-read the row's last 8 activations against a zeroed A: 0 * Inf).
  *
  * fp4_hip_gemv_lora_nf4 / fp4_hip_gemm_lora_nf4: fp4_hip_gemv_fused_nf4 / fp4_hip_gemm_fused_nf4 with the adapter term
  *   delta[b][r] = sum_j f32(lora_B[r][j]) * t[b][j]
