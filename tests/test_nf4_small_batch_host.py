@@ -218,3 +218,11 @@ def test_the_new_source_is_built_and_its_kernels_are_tied_to_it():
     assert files and any(f.endswith("gemm_small_nf4.hip") for f in files)
     assert not any(f.endswith("gemm_small_fp4.hip") for f in files)
     assert any(f.endswith("gemm_small_fp4.hip") for f in source_digest.sources_of("gemm16_mfma_kernel<2, 4, 1, true, 4>"))
+    # the shared headers: rebuilt on an edit, and among the sources of the matrix-core kernels that include them - and of no other
+    assert {"mfma_common.h", "nf4_mfma.h", "launchers.h"} <= set(build.HIP_HEADERS)
+    names = lambda kernel: {os.path.basename(f) for f in source_digest.sources_of(kernel)}
+    assert {"mfma_common.h", "nf4_mfma.h"} <= names("gemm_nf4_mfma_kernel<2, 4, 4>")
+    for fp4_kernel in ("gemm16_mfma_kernel<2, 4, 1, true, 4>", "gemm16_small_kernel<2, 4>"):
+        assert "mfma_common.h" in names(fp4_kernel) and "nf4_mfma.h" not in names(fp4_kernel)
+    for other in ("gemv16_regx_kernel<2, 4>", "gemv_nf4_kernel<2, 4>", "dequant_tiles_kernel<2>", "quantize_nf4_kernel<2>", "lora_down_kernel<2>"):
+        assert not {"mfma_common.h", "nf4_mfma.h"} & names(other), other

@@ -196,3 +196,11 @@ def test_the_new_source_is_built_and_its_kernels_are_tied_to_it():
     small = source_digest.sources_of("gemm_nf4_mfma_kernel<2, 4, 4>")
     assert any(f.endswith("gemm_small_nf4.hip") for f in small) and not any(f.endswith("gemm_wide_nf4.hip") for f in small)
     assert any(f.endswith("gemm_wide_fp4.hip") for f in source_digest.sources_of("gemm16_wide_ring_kernel<2, 4, 4>"))
+    # the shared headers: rebuilt on an edit, and among the sources of the matrix-core kernels that include them - and of no other
+    assert {"mfma_common.h", "nf4_mfma.h", "launchers.h"} <= set(build.HIP_HEADERS)
+    names = lambda kernel: {os.path.basename(f) for f in source_digest.sources_of(kernel)}
+    assert {"mfma_common.h", "nf4_mfma.h"} <= names("gemm_wide_nf4_kernel<2, 4, 1, 4>")
+    for fp4_kernel in ("gemm16_wide_ring_kernel<2, 4, 4>", "gemm16_xstat_kernel<2, 4>", "splitk_reduce_kernel<2>"):
+        assert "mfma_common.h" in names(fp4_kernel) and "nf4_mfma.h" not in names(fp4_kernel)
+    for other in ("gemv16_regx_kernel<2, 4>", "dequant_tiles_kernel<2>"):
+        assert not {"mfma_common.h", "nf4_mfma.h"} & names(other), other

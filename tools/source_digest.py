@@ -12,9 +12,11 @@ CSRC = os.path.join("torch-bnb-fp4_amd", "csrc")
 COMMON = [os.path.join(CSRC, "fp4_common.h"), os.path.join("torch-bnb-fp4_amd", "build.py")]  # code tables / conversions; compiler flags
 # kernel-name prefix (as it appears in profiles/rNN_traffic.json) -> the files its code object is compiled from
 LORA = os.path.join(CSRC, "lora_nf4.h")  # the adapter term of the NF4 decode kernels' LORA instantiations
+MFMA = os.path.join(CSRC, "mfma_common.h")  # the matrix-core kernels' shared device helpers
+NF4_MFMA = os.path.join(CSRC, "nf4_mfma.h")  # the NF4 hi / lo decode of the two NF4 matrix-core kernels
 KERNEL_SOURCES = {
-    "gemm_wide_nf4": [os.path.join(CSRC, "gemm_wide_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
-    "gemm_nf4": [os.path.join(CSRC, "gemm_small_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
+    "gemm_wide_nf4": [os.path.join(CSRC, "gemm_wide_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, NF4_MFMA, LORA] + COMMON,
+    "gemm_nf4": [os.path.join(CSRC, "gemm_small_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, NF4_MFMA, LORA] + COMMON,
     "gemv_nf4": [os.path.join(CSRC, "gemv_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
     "lora_down": [os.path.join(CSRC, "lora_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
     "quantize_nf4": [os.path.join(CSRC, "quantize_nf4.hip")] + COMMON,
@@ -22,10 +24,10 @@ KERNEL_SOURCES = {
     "gemv": [os.path.join(CSRC, "gemv_fp4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
     "quantize_": [os.path.join(CSRC, "quantize_fp4.hip")] + COMMON,
     # (longest prefix first: dict order is lookup order)
-    "gemm16_wide": [os.path.join(CSRC, "gemm_wide_fp4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
-    "gemm16_xstat": [os.path.join(CSRC, "gemm_splitk_fp4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
-    "splitk_reduce": [os.path.join(CSRC, "gemm_splitk_fp4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
-    "gemm16_": [os.path.join(CSRC, "gemm_small_fp4.hip"), os.path.join(CSRC, "gemv_common.h")] + COMMON,
+    "gemm16_wide": [os.path.join(CSRC, "gemm_wide_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA] + COMMON,
+    "gemm16_xstat": [os.path.join(CSRC, "gemm_splitk_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA] + COMMON,
+    "splitk_reduce": [os.path.join(CSRC, "gemm_splitk_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA] + COMMON,
+    "gemm16_": [os.path.join(CSRC, "gemm_small_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA] + COMMON,
 }
 
 

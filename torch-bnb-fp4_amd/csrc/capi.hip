@@ -5,20 +5,13 @@
 #include <cstring>
 
 #include "fp4_common.h"
+#include "launchers.h"
 
 namespace fp4 {
 
 namespace {
 thread_local char g_last_error[512] = "";
 }
-
-void set_dequant_variant(int v);
-void set_gemv_variant(int v);
-void set_small_variant(int v);
-void set_wide_variant(int v);
-void set_quantize_variant(int v);
-void set_gemv_nf4_variant(int v);
-void set_wide_nf4_variant(int v);
 
 void set_error(const char *fmt, ...) {
     va_list ap;

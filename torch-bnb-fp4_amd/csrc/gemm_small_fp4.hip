@@ -7,7 +7,8 @@
 //                           (v_mfma_f32_16x16x32): one-shot for any K % 512 == 0, persistent for K = 4096.
 #include <atomic>
 
-#include "gemv_common.h"
+#include "launchers.h"
+#include "mfma_common.h"
 
 namespace fp4 {
 
@@ -165,17 +166,6 @@ __global__ __launch_bounds__(256) void gemm16_small_kernel(const uint16_t *__res
 //   * the B operand is x[n = l&15][64b + 16kb + 8t + j], loaded straight from L2 into VGPRs (32 B per block);
 //   * the 8 partial 16x16 tiles meet in LDS; one rounding, bias added in f32 first (F.linear semantics).
 // Needs blocksize 64 and K a multiple of 512; everything else is served by the kernels above or by dequant + GEMM.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    if constexpr (DT == FP4_DTYPE_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
 // 8 consecutive 16-bit activations (x0..x7) -> the dword order decode8's pairs multiply with: (x0,x2) (x4,x6) (x1,x3) (x5,x7)
 __device__ __forceinline__ u32x4 pair_up8(u32x4 w) {
     u32x4 o;
@@ -726,11 +716,6 @@ void set_small_variant(int v) {
 }  // namespace fp4
 
 namespace fp4 {
-int64_t gemm_splitk_workspace_bytes(int64_t B, int64_t M, int64_t K, int blocksize, int dtype);  // gemm_splitk_fp4.hip
-int gemm_splitk_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                       int B, int M, int K, int mode, void *workspace, int64_t workspace_bytes, hipStream_t stream);
-int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                     int B, int M, int K, int mode, bool any_rows, hipStream_t stream);  // gemm_wide_fp4.hip
 namespace {
 int gemm_small_entry(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual, void *out,
                      int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream) {

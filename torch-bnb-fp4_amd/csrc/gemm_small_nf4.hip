@@ -1,62 +1,29 @@
 // Small-batch NF4 product for gfx950 (MI355X): 1..16 activation rows against one NF4 weight on the matrix cores,
 //     out[b][r] = T( sum_k x[b][k] * code[nib(r,k)] * absmax[(r*K+k)/64] + bias[r] )
-// The tile scheme is gemm16_mfma_kernel's (gemm_small_fp4.hip; its staging logic is copied here rather than shared, so that the
-// FP4 translation unit stays byte-identical): 8-wave workgroup per 16-row tile of W, the waves split K, row-contiguous 16-byte
-// weight loads staged through a wave-private LDS image, scales re-read from it as broadcasts, loads one pass ahead,
-// v_mfma_f32_16x16x32_{bf16,f16} with one instruction never straddling two scales, partial tiles meeting in LDS.
+// The tile scheme is gemm16_mfma_kernel's (gemm_small_fp4.hip; the staging is written out in both kernels - sharing it between the
+// FP4 and the NF4 kernel is a change of its own, not made here): 8-wave workgroup per 16-row tile of W, the waves split K,
+// row-contiguous 16-byte weight loads staged through a wave-private LDS image, scales re-read from it as broadcasts, loads one pass
+// ahead, v_mfma_f32_16x16x32_{bf16,f16} with one instruction never straddling two scales, partial tiles meeting in LDS.
 //
-// What differs is the decode.  The FP4 kernel builds 12*|code| in 8 bits with v_perm; the 16 NF4 codes are arbitrary f32 values,
-// exact in neither bf16 nor fp16, and T(code) alone misses the project's error bar (|err| <= 1e-5 * sum|x*w| beside the final
-// rounding) by up to 31.6x in bf16 and 4.7x in fp16.  So every weight goes to the matrix cores TWICE:
-//     hi = T(code),  lo = T(code - hi)        |hi + lo - code| <= 5.45e-6 |code| (bf16), 1.05e-7 |code| (fp16)
-// as two instructions against the same activation fragment.  Both halves come from one 256-entry LDS table indexed by the packed
-// BYTE: entry = { hi(high nibble) | hi(low nibble) << 16 , lo(high nibble) | lo(low nibble) << 16 }, so one ds_read_b64 per byte
-// yields one A-fragment dword for each of the two instructions, in natural k order (element 2i is the HIGH nibble of byte i), and
-// the B side uses x as loaded.  The table is computed by the workgroup from the f32 codes with the kernel's own RNE conversions.
-//
-// fp16: most lo values are below fp16's smallest normal (6.1e-5).  Whether v_mfma_f32_16x16x32_f16 flushes subnormal inputs is not
-// documented, so this kernel does not depend on it: the fp16 table holds lo * 2^24 (every non-zero entry normal, none above 4096),
-// the lo instructions run into a tile of their own, and hi_tile + 2^-24 * lo_tile (exact scaling, one FMA per element) is formed
-// before the block's absmax is applied.  bf16 has f32's exponent range: both instructions share one accumulator.
+// What differs is the decode: every weight goes to the matrix cores twice, as hi = T(code) and lo = T(code - hi) from one 256-entry
+// LDS table indexed by the packed byte.  nf4_mfma.h has the decode, the reason for it and fp16's 2^24 rule; here the weight is the
+// A operand and the B side uses x as loaded.
 //
 // Fused decode epilogues (fp4_hip_gemm_fused_nf4, 1..16 rows with K % 512 == 0): the FUSED instantiations take a residual and the
 // `mode` of gemm_small_fp4.hip.  The final pass over the LDS partials has one thread per (activation row, weight row); for the
 // gate|up epilogue the thread of an even weight row also sums its odd neighbour's partials (tid + 1) and stores the pair, the odd
-// thread stores nothing.  A compile-time choice: the plain entry point keeps its instantiations instruction for instruction.
+// thread stores nothing (store_nf4_pair, nf4_mfma.h).  A compile-time choice: the plain entry point keeps its instantiations
+// instruction for instruction.
 //
 // LoRA adapter term (fp4_hip_gemm_lora_nf4, 2..16 rows with K % 512 == 0): the LORA instantiations (always FUSED) add
 // delta[n][row] = sum_j f32(lora_B[row][j]) * lora_t[n][j] (lora_nf4.h) to the thread's finished f32 sum ahead of the epilogue, and
 // to the up row's likewise; lora_t = s * A x is lora_down_kernel's f32 output.
-#include "gemv_common.h"
-#include "lora_nf4.h"
+#include "launchers.h"
+#include "nf4_mfma.h"
 
 namespace fp4 {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    if constexpr (DT == FP4_DTYPE_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-// lo is stored times 2^kLoShift: 24 for fp16 (see above), 0 for bf16
-template <int DT>
-constexpr int kLoShift = DT == FP4_DTYPE_F16 ? 24 : 0;
-
-// (hi, lo) of one code in T: hi = RNE_T(code), lo = RNE_T((code - hi) * 2^kLoShift); code - hi is exact in f32
-template <int DT>
-__device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &lo) {
-    const float c = nf4_lut_entry(nibble);
-    hi = from_f32<DT>(c);
-    const float rest = c - to_f32<DT>(uint16_t(hi));
-    lo = from_f32<DT>(rest * float(1 << kLoShift<DT>));
-}
 
 // Workgroup = 8 waves = one 16-row tile of W; wave w owns quant blocks (p*8 + w)*NBW.. of pass p.  Lane (r = l & 15, kb = l >> 4)
 // supplies, per 64-weight block, the 8 packed bytes [8kb, 8kb + 8) of row r: k-sets {16kb + 8t + j}, t = 0, 1, each fed as hi and as
@@ -123,12 +90,7 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     issue_staged(0);
 
     // the byte table, once per workgroup, while the first pass's loads fly
-    if (tid < 256) {
-        uint32_t h0, l0, h1, l1;
-        split_code<DT>(tid >> 4, h0, l0);  // element 2i: the HIGH nibble
-        split_code<DT>(tid & 15, h1, l1);
-        s_code[tid] = u32x2{h0 | (h1 << 16), l0 | (l1 << 16)};
-    }
+    fill_code_table<DT>(s_code, tid);
     __syncthreads();
     const uint8_t *code = reinterpret_cast<const uint8_t *>(s_code);
 
@@ -194,25 +156,14 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
                 else
                     bfrag = xr[j][t];
                 const uint32_t q = t == 0 ? wq[j].x : wq[j].y;
-                // byte d of q -> table entry at 8 * byte: dword d of the hi fragment and of the lo fragment
-                const u32x2 e0 = *reinterpret_cast<const u32x2 *>(code + ((q << 3) & 0x7F8u));
-                const u32x2 e1 = *reinterpret_cast<const u32x2 *>(code + ((q >> 5) & 0x7F8u));
-                const u32x2 e2 = *reinterpret_cast<const u32x2 *>(code + ((q >> 13) & 0x7F8u));
-                const u32x2 e3 = *reinterpret_cast<const u32x2 *>(code + ((q >> 21) & 0x7F8u));
-                const u32x4 a_hi = {e0.x, e1.x, e2.x, e3.x}, a_lo = {e0.y, e1.y, e2.y, e3.y};
-                tile = mfma16<DT>(a_hi, bfrag, tile);
+                const HiLoFrag w = decode8_hi_lo(code, q);
+                tile = mfma16<DT>(w.hi, bfrag, tile);
                 if constexpr (kLoShift<DT> == 0)
-                    tile = mfma16<DT>(a_lo, bfrag, tile);
+                    tile = mfma16<DT>(w.lo, bfrag, tile);
                 else
-                    tile_lo = mfma16<DT>(a_lo, bfrag, tile_lo);
+                    tile_lo = mfma16<DT>(w.lo, bfrag, tile_lo);
             }
-            if constexpr (kLoShift<DT> != 0) {
-                constexpr float kUnscale = 1.0f / float(1 << kLoShift<DT>);
-                tile.x = __builtin_fmaf(tile_lo.x, kUnscale, tile.x);
-                tile.y = __builtin_fmaf(tile_lo.y, kUnscale, tile.y);
-                tile.z = __builtin_fmaf(tile_lo.z, kUnscale, tile.z);
-                tile.w = __builtin_fmaf(tile_lo.w, kUnscale, tile.w);
-            }
+            tile = fold_lo<DT>(tile, tile_lo);
             acc.x = __builtin_fmaf(tile.x, am[0][j], acc.x);
             acc.y = __builtin_fmaf(tile.y, am[1][j], acc.y);
             acc.z = __builtin_fmaf(tile.z, am[2][j], acc.z);
@@ -234,13 +185,7 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
                     float u = 0.0f;
 #pragma unroll
                     for (int w = 0; w < 8; ++w) u += s_part[w][tid + 1];
-                    if (row < M && n < B) {
-                        if constexpr (LORA) {
-                            t += lora_delta<DT>(lora_B + int64_t(row) * R, lora_t + n * R, R);
-                            u += lora_delta<DT>(lora_B + int64_t(row + 1) * R, lora_t + n * R, R);
-                        }
-                        store_small_silu_mul<DT>(out, bias, residual, n, row >> 1, M >> 1, t, u);
-                    }
+                    if (row < M && n < B) store_nf4_pair<DT, LORA>(out, bias, residual, lora_B, lora_t, R, n, row, M, t, u);
                 }
             } else if (row < M && n < B) {
                 if constexpr (LORA) t += lora_delta<DT>(lora_B + int64_t(row) * R, lora_t + n * R, R);
@@ -252,21 +197,8 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     }
 }
 
-struct SmallNf4Args {
-    const void *x;
-    const uint8_t *W;
-    const float *absmax;
-    const void *bias, *residual;
-    void *out;
-    int B, M, K, mode;
-    hipStream_t stream;
-    const void *lora_B = nullptr;  // LORA instantiations only
-    const float *lora_t = nullptr;
-    int R = 0;
-};
-
 template <int DT, int NBW, int XS, bool FUSED, bool LORA>
-void launch_nf4_mfma(const SmallNf4Args &a) {
+void launch_nf4_mfma(const Nf4GemmArgs &a) {
     hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED, LORA>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
                        reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
                        reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
@@ -274,7 +206,7 @@ void launch_nf4_mfma(const SmallNf4Args &a) {
 }
 
 template <int DT, bool FUSED, bool LORA = false>
-void dispatch_nf4_mfma(const SmallNf4Args &a) {
+void dispatch_nf4_mfma(const Nf4GemmArgs &a) {
     const int B = a.B, M = a.M, K = a.K;
     const int units = K / 512;  // quant blocks per wave over the whole K
     const int blocks = (M + 15) / 16;
@@ -295,22 +227,16 @@ void dispatch_nf4_mfma(const SmallNf4Args &a) {
 // K % 512 == 0, fp16 / bf16, M even for the gate|up epilogue.  Launches only.
 void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
                                  void *out, int B, int M, int K, int mode, hipStream_t stream) {
-    const SmallNf4Args a{x, W, absmax, bias, residual, out, B, M, K, mode, stream};
-    if (dtype == FP4_DTYPE_F16)
-        dispatch_nf4_mfma<FP4_DTYPE_F16, true>(a);
-    else
-        dispatch_nf4_mfma<FP4_DTYPE_BF16, true>(a);
+    const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream};
+    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true>(a); });
 }
 
 // the same with the adapter term, for fp4_hip_gemm_lora_nf4 (gemm_wide_nf4.hip), which has validated the adapter as well
 void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
                                 const void *lora_B, const float *lora_t, int R, void *out, int B, int M, int K, int mode,
                                 hipStream_t stream) {
-    const SmallNf4Args a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, lora_B, lora_t, R};
-    if (dtype == FP4_DTYPE_F16)
-        dispatch_nf4_mfma<FP4_DTYPE_F16, true, true>(a);
-    else
-        dispatch_nf4_mfma<FP4_DTYPE_BF16, true, true>(a);
+    const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, lora_B, lora_t, R};
+    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true, true>(a); });
 }
 
 }  // namespace fp4
@@ -318,30 +244,9 @@ void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, cons
 extern "C" int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                                       int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
     using namespace fp4;
-    if (B < 0 || M < 0 || K <= 0 || blocksize <= 0) {
-        set_error("fp4_hip_gemm_small_nf4: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", (long long)B,
-                  (long long)M, (long long)K, blocksize);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
-    // the kernel addresses with 64-bit element offsets: M * K may pass 2^32; the bounds keep the int row / block arithmetic in range
-    if (B > 16 || blocksize != 64 || (K % 512) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) || (align & 15u) != 0 ||
-        M > (int64_t(1) << 30) || K > (int64_t(1) << 24)) {
-        set_error("fp4_hip_gemm_small_nf4: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..16 rows, blocksize 64, "
-                  "K %% 512 == 0, fp16 / bf16, 16-byte aligned x and packed); use dequant + GEMM",
-                  (long long)B, (long long)M, (long long)K, blocksize, dtype);
-        return FP4_ERR_UNSUPPORTED;
-    }
+    if (const int rc = nf4_check_args("fp4_hip_gemm_small_nf4", 16, 512, x, packed, absmax, out, B, M, K, blocksize, dtype, 0)) return rc;
     if (M == 0 || B == 0) return FP4_OK;
-    if (!x || !packed || !absmax || !out) {
-        set_error("fp4_hip_gemm_small_nf4: null pointer");
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const SmallNf4Args a{x, packed, absmax, bias, nullptr, out, (int)B, (int)M, (int)K, 0, s};
-    if (dtype == FP4_DTYPE_F16)
-        dispatch_nf4_mfma<FP4_DTYPE_F16, false>(a);
-    else
-        dispatch_nf4_mfma<FP4_DTYPE_BF16, false>(a);
+    const Nf4GemmArgs a{x, packed, absmax, bias, nullptr, out, (int)B, (int)M, (int)K, 0, static_cast<hipStream_t>(stream)};
+    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, false>(a); });
     return check_launch("fp4_hip_gemm_small_nf4");
 }

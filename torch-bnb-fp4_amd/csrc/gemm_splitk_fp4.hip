@@ -7,44 +7,12 @@
 // the first).  x traffic drops to (workgroups x rows x 1 KB), a few MB; the price is one float per (K slice, activation row, weight
 // row) through a workspace and a second, tiny launch that adds the slices in a fixed order and applies the epilogue - deterministic,
 // no atomics, no cross-workgroup synchronisation (stream order does it).
-#include "gemv_common.h"
+#include "launchers.h"
+#include "mfma_common.h"
 
 namespace fp4 {
 
 namespace {
-
-typedef __bf16 bf16x8s_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8s_t __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma_xw_s(u32x4 xfrag, u32x4 wfrag, f32x4 c) {
-    if constexpr (DT == FP4_DTYPE_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8s_t, xfrag), __builtin_bit_cast(f16x8s_t, wfrag), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s_t, xfrag), __builtin_bit_cast(bf16x8s_t, wfrag), c, 0, 0, 0);
-}
-
-template <int DT>
-__device__ __forceinline__ u32x4 decode8_nat(uint32_t q) {  // (e0,e1) (e2,e3) (e4,e5) (e6,e7), as in gemm_wide_fp4.hip
-    uint32_t P[4];
-    decode8<DT>(q, P);
-    u32x4 n;
-    n.x = perm(P[2], P[0], 0x05040100u);
-    n.y = perm(P[2], P[0], 0x07060302u);
-    n.z = perm(P[3], P[1], 0x05040100u);
-    n.w = perm(P[3], P[1], 0x07060302u);
-    return n;
-}
-
-__device__ __forceinline__ void dma16(const uint8_t *src, uint8_t *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // grid (K slices, row chunks); a K slice is 8 quant blocks (512 columns; the last may be shorter); `rows_per_wg` % 128 == 0.
 // partial[(slice * B + n) * M + row] = sum over the slice's columns, already times 1/12.
@@ -71,8 +39,8 @@ __global__ __launch_bounds__(512) void gemm16_xstat_kernel(const uint16_t *__res
         for (int d = 0; d < 2 * NT; ++d) {
             const int n = 8 * d + (lane >> 3), sl = lane & 7;
             const int nn = n < B ? n : B - 1;
-            dma16(xb + (uint32_t)nn * (uint32_t)K * 2u + (uint32_t)((sl ^ ((n >> 1) & 7)) * 16) + (uint32_t)(jb0 + wave) * 128u,
-                  s_raw + wave * (NT * 2048) + d * 1024);
+            lds_dma16(xb + (uint32_t)nn * (uint32_t)K * 2u + (uint32_t)((sl ^ ((n >> 1) & 7)) * 16) + (uint32_t)(jb0 + wave) * 128u,
+                      s_raw + wave * (NT * 2048) + d * 1024);
         }
     }
     // weight tile t of this wave = tile (wave + 8 t) of the workgroup: 4 DMAs of 4 rows x 256 B (piece ^ row), 2 of 8 rows x 8 scales
@@ -84,7 +52,7 @@ __global__ __launch_bounds__(512) void gemm16_xstat_kernel(const uint16_t *__res
         for (int q = 0; q < 4; ++q) {
             const int rl = 4 * q + wrl, r = r0 + rl;
             const int p = wp ^ rl;
-            dma16(W + (int64_t)(r < M ? r : M - 1) * (int64_t)(K >> 1) + jb0 * 32 + ((p >> 1) < nb ? p * 16 : (p & 1) * 16), slot + q * 1024);
+            lds_dma16(W + (int64_t)(r < M ? r : M - 1) * (int64_t)(K >> 1) + jb0 * 32 + ((p >> 1) < nb ? p * 16 : (p & 1) * 16), slot + q * 1024);
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -96,15 +64,15 @@ __global__ __launch_bounds__(512) void gemm16_xstat_kernel(const uint16_t *__res
     };
     const int my_tiles = tiles > wave ? (tiles - wave + 7) >> 3 : 0;
     for (int t = 0; t < D - 1 && t < my_tiles; ++t) issue(t);
-    wait_vm<0>();
+    wait_vmcnt<0>();
     __syncthreads();  // the x slice is in LDS for everyone; from here on every wave runs on its own
 
     const int xrd0 = i * 128 + (((2 * kb) ^ (i >> 1)) * 16), xrd1 = i * 128 + (((2 * kb + 1) ^ (i >> 1)) * 16);
     for (int t = 0; t < my_tiles; ++t) {
         if (D > 2 && t + D - 2 < my_tiles)
-            wait_vm<(D - 2) * 6>();
+            wait_vmcnt<(D - 2) * 6>();
         else
-            wait_vm<0>();
+            wait_vmcnt<0>();
         asm volatile("" ::: "memory");
         if (t + D - 1 < my_tiles) issue(t + D - 1);  // into the slot tile t - 1 used
         const uint8_t *slot = mine + (t % D) * kTile;
@@ -118,11 +86,11 @@ __global__ __launch_bounds__(512) void gemm16_xstat_kernel(const uint16_t *__res
             f32x4 tile[NT];
 #pragma unroll
             for (int t2 = 0; t2 < 2; ++t2) {
-                const u32x4 wf = decode8_nat<DT>(t2 == 0 ? wq.x : wq.y);
+                const u32x4 wf = decode8_natural<DT>(t2 == 0 ? wq.x : wq.y);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const u32x4 xf = *reinterpret_cast<const u32x4 *>(xs + nt * 2048 + (t2 == 0 ? xrd0 : xrd1));
-                    tile[nt] = mfma_xw_s<DT>(xf, wf, t2 == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[nt]);
+                    tile[nt] = mfma16<DT>(xf, wf, t2 == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[nt]);
                 }
             }
 #pragma unroll

@@ -23,40 +23,12 @@
 //   * K-slice partials meet in LDS (the ring's storage, after the loop) and are summed in a fixed order: deterministic.
 #include <atomic>
 
-#include "gemv_common.h"
+#include "launchers.h"
+#include "mfma_common.h"
 
 namespace fp4 {
 
 namespace {
-
-typedef __bf16 bf16x8w_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8w_t __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma_xw(u32x4 xfrag, u32x4 wfrag, f32x4 c) {
-    if constexpr (DT == FP4_DTYPE_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8w_t, xfrag), __builtin_bit_cast(f16x8w_t, wfrag), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8w_t, xfrag), __builtin_bit_cast(bf16x8w_t, wfrag), c, 0, 0, 0);
-}
-
-// 8 weights of one packed dword as 12*code in natural order: (e0,e1) (e2,e3) (e4,e5) (e6,e7)
-template <int DT>
-__device__ __forceinline__ u32x4 decode8_natural(uint32_t q) {
-    uint32_t P[4];
-    decode8<DT>(q, P);
-    u32x4 n;
-    n.x = perm(P[2], P[0], 0x05040100u);
-    n.y = perm(P[2], P[0], 0x07060302u);
-    n.z = perm(P[3], P[1], 0x05040100u);
-    n.w = perm(P[3], P[1], 0x07060302u);
-    return n;
-}
-
-__device__ __forceinline__ void lds_dma16(const uint8_t *src, uint8_t *lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
 
 // K-slice partials -> LDS (the ring's storage; the caller has synchronised) -> fixed-order sum -> store.
 // D layout: lane (j = lane & 15 -> weight row of the tile, lane >> 4) register g -> activation row nt*16 + (lane >> 4)*4 + g
@@ -108,11 +80,6 @@ __device__ __forceinline__ void wide_epilogue(uint8_t *s_raw, const f32x4 (&acc)
 //   * a counted s_waitcnt vmcnt leaves D - 2 steps in flight across the barrier, which is the bare s_barrier (a __syncthreads()
 //     fence would drain every wave's counter);
 //   * weight image: [row][128 B] with 16-byte piece ^ (row >> 1 & 7), applied to the DMA's source and to the ds_read_b64.
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int DT, int NT, int RT>
 __global__ __launch_bounds__(512) void gemm16_wide_ring_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
@@ -247,7 +214,7 @@ __global__ __launch_bounds__(512) void gemm16_wide_ring_kernel(const uint16_t *_
                 const u32x4 xf = *reinterpret_cast<const u32x4 *>(xs + nt * 2048 + (t == 0 ? xrd0 : xrd1));
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt)
-                    tile[rt][nt] = mfma_xw<DT>(xf, wf[rt], t == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[rt][nt]);
+                    tile[rt][nt] = mfma16<DT>(xf, wf[rt], t == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[rt][nt]);
             }
         }
 #pragma unroll
@@ -369,7 +336,7 @@ __global__ __launch_bounds__(640) void gemm16_wide_ring8_kernel(const uint16_t *
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 const u32x4 xf = *reinterpret_cast<const u32x4 *>(xs + nt * 2048 + (t == 0 ? xrd0 : xrd1));
-                tile[nt] = mfma_xw<DT>(xf, wf, t == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[nt]);
+                tile[nt] = mfma16<DT>(xf, wf, t == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[nt]);
             }
         }
 #pragma unroll
@@ -467,7 +434,7 @@ __global__ __launch_bounds__(512) void gemm16_wide_auto_kernel(const uint16_t *_
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const u32x4 xf = *reinterpret_cast<const u32x4 *>(xs + nt * 2048 + (t2 == 0 ? xrd0 : xrd1));
-                    tile[nt] = mfma_xw<DT>(xf, wf, t2 == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[nt]);
+                    tile[nt] = mfma16<DT>(xf, wf, t2 == 0 ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : tile[nt]);
                 }
             }
 #pragma unroll

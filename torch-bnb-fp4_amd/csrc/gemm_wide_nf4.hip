@@ -7,13 +7,12 @@
 // lane's four accumulators of a tile belong to ONE weight row (D column = lane & 15) and four activation rows, and the block's
 // absmax is one scalar per lane and 64-weight block.  No instruction straddles two scales.
 //
-// The decode is gemm_small_nf4.hip's (copied, that file stays as it is): every weight goes to the matrix cores twice,
+// The decode is gemm_small_nf4.hip's, shared through nf4_mfma.h (which says why): every weight goes to the matrix cores twice,
 //     hi = T(code),  lo = T(code - hi),
 // both halves from one 256-entry LDS table indexed by the packed BYTE (one ds_read_b64 per byte = one fragment dword of each half,
-// natural k order: element 2i is the HIGH nibble of byte i).  A decoded fragment pair is used for all NT column tiles of x:
+// natural k order).  A decoded fragment pair is used for all NT column tiles of x:
 // 8 table reads per lane, weight row and block feed 4 * NT matrix instructions (the 2..16-row kernel: 8 reads for 4).
-// fp16 keeps that kernel's rule that no subnormal matrix input is relied on: the table holds lo * 2^24, the lo products run into a
-// tile of their own, and hi_tile + 2^-24 * lo_tile is formed exactly (one FMA per element) before the block's scale is applied.
+// fp16 keeps the rule that no subnormal matrix input is relied on: the lo products run into a tile of their own.
 //
 // Work split: a workgroup of 8 waves owns RT 16-row tiles of W (RT in {1, 2}, chosen by M) and all NT <= 4 column tiles; the waves
 // split K in units of NBW blocks (unit u = pass * 8 + wave; NBW = 4 where K % 256 == 0, else 1; a ragged last pass leaves the
@@ -25,44 +24,20 @@
 // Fused decode epilogues (fp4_hip_gemm_fused_nf4): the FUSED instantiations take a residual and the `mode` of gemm_wide_fp4.hip.  The
 // final pass has one thread per (tile, activation row, weight row); for the gate|up epilogue the thread of an even weight row also
 // sums its odd neighbour's partials (wr + 1 = src + 4, as wide_epilogue of gemm_wide_fp4.hip does) and stores the pair, odd rows
-// store nothing; row tiles are 16 rows and row0 is even, so a pair never straddles a tile.  A compile-time choice: the plain entry
-// point keeps its instantiations instruction for instruction.
+// store nothing (store_nf4_pair, nf4_mfma.h); row tiles are 16 rows and row0 is even, so a pair never straddles a tile.  A compile-time
+// choice: the plain entry point keeps its instantiations instruction for instruction.
 //
 // LoRA adapter term (fp4_hip_gemm_lora_nf4, 1..64 rows): the LORA instantiations (always FUSED) add
 // delta[n][row] = sum_j f32(lora_B[row][j]) * lora_t[n][j] (lora_nf4.h) to the thread's finished f32 sum ahead of the epilogue, and
 // to the up row's likewise; lora_t = s * A x is lora_down_kernel's f32 output.
-#include "gemv_common.h"
-#include "lora_nf4.h"
-
 #include <atomic>
+
+#include "launchers.h"
+#include "nf4_mfma.h"
 
 namespace fp4 {
 
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    if constexpr (DT == FP4_DTYPE_F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-// lo is stored times 2^kLoShift: 24 for fp16 (see above), 0 for bf16
-template <int DT>
-constexpr int kLoShift = DT == FP4_DTYPE_F16 ? 24 : 0;
-
-// (hi, lo) of one code in T: hi = RNE_T(code), lo = RNE_T((code - hi) * 2^kLoShift); code - hi is exact in f32
-template <int DT>
-__device__ __forceinline__ void split_code(int nibble, uint32_t &hi, uint32_t &lo) {
-    const float c = nf4_lut_entry(nibble);
-    hi = from_f32<DT>(c);
-    const float rest = c - to_f32<DT>(uint16_t(hi));
-    lo = from_f32<DT>(rest * float(1 << kLoShift<DT>));
-}
 
 // Lane (r = l & 15, kb = l >> 4).  Instruction t = 0, 1 of a block takes k = 32t .. 32t + 31 in natural order: the B operand is the
 // packed dword [16t + 4kb, 16t + 4kb + 4) of weight row r (k = 32t + 8kb + j), the A operand x[16nt + r][64b + 32t + 8kb + j], so
@@ -133,12 +108,7 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
     issue_staged(0);
 
     // the byte table, once per workgroup, while the first pass's loads fly
-    if (tid < 256) {
-        uint32_t h0, l0, h1, l1;
-        split_code<DT>(tid >> 4, h0, l0);  // element 2i: the HIGH nibble
-        split_code<DT>(tid & 15, h1, l1);
-        s_code[tid] = u32x2{h0 | (h1 << 16), l0 | (l1 << 16)};
-    }
+    fill_code_table<DT>(s_code, tid);
     __syncthreads();
     const uint8_t *code = reinterpret_cast<const uint8_t *>(s_code);
     uint8_t *img = s_raw + wave * kRows * kStageStride;
@@ -187,32 +157,19 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
                 for (int nt = 0; nt < NT; ++nt) tile[nt] = tile_lo[nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
-                    const uint32_t q = wq[t];
-                    // byte d of q -> table entry at 8 * byte: dword d of the hi fragment and of the lo fragment
-                    const u32x2 e0 = *reinterpret_cast<const u32x2 *>(code + ((q << 3) & 0x7F8u));
-                    const u32x2 e1 = *reinterpret_cast<const u32x2 *>(code + ((q >> 5) & 0x7F8u));
-                    const u32x2 e2 = *reinterpret_cast<const u32x2 *>(code + ((q >> 13) & 0x7F8u));
-                    const u32x2 e3 = *reinterpret_cast<const u32x2 *>(code + ((q >> 21) & 0x7F8u));
-                    const u32x4 b_hi = {e0.x, e1.x, e2.x, e3.x}, b_lo = {e0.y, e1.y, e2.y, e3.y};
+                    const HiLoFrag w = decode8_hi_lo(code, wq[t]);
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
-                        tile[nt] = mfma16<DT>(xcur[nt][t], b_hi, tile[nt]);
+                        tile[nt] = mfma16<DT>(xcur[nt][t], w.hi, tile[nt]);
                         if constexpr (kLoShift<DT> == 0)
-                            tile[nt] = mfma16<DT>(xcur[nt][t], b_lo, tile[nt]);
+                            tile[nt] = mfma16<DT>(xcur[nt][t], w.lo, tile[nt]);
                         else
-                            tile_lo[nt] = mfma16<DT>(xcur[nt][t], b_lo, tile_lo[nt]);
+                            tile_lo[nt] = mfma16<DT>(xcur[nt][t], w.lo, tile_lo[nt]);
                     }
                 }
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-                    f32x4 v = tile[nt];
-                    if constexpr (kLoShift<DT> != 0) {
-                        constexpr float kUnscale = 1.0f / float(1 << kLoShift<DT>);
-                        v.x = __builtin_fmaf(tile_lo[nt].x, kUnscale, v.x);
-                        v.y = __builtin_fmaf(tile_lo[nt].y, kUnscale, v.y);
-                        v.z = __builtin_fmaf(tile_lo[nt].z, kUnscale, v.z);
-                        v.w = __builtin_fmaf(tile_lo[nt].w, kUnscale, v.w);
-                    }
+                    const f32x4 v = fold_lo<DT>(tile[nt], tile_lo[nt]);
                     acc[rt][nt].x = __builtin_fmaf(v.x, am, acc[rt][nt].x);
                     acc[rt][nt].y = __builtin_fmaf(v.y, am, acc[rt][nt].y);
                     acc[rt][nt].z = __builtin_fmaf(v.z, am, acc[rt][nt].z);
@@ -257,13 +214,7 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
                     float u = 0.0f;
 #pragma unroll
                     for (int w = 0; w < 4; ++w) u += s_part[w][src + 4];
-                    if (row < M && n < B) {
-                        if constexpr (LORA) {
-                            t += lora_delta<DT>(lora_B + row * R, lora_t + n * R, R);
-                            u += lora_delta<DT>(lora_B + (row + 1) * R, lora_t + n * R, R);
-                        }
-                        store_small_silu_mul<DT>(out, bias, residual, n, (int)(row >> 1), M >> 1, t, u);
-                    }
+                    if (row < M && n < B) store_nf4_pair<DT, LORA>(out, bias, residual, lora_B, lora_t, R, n, row, M, t, u);
                 }
             } else if (row < M && n < B) {
                 if constexpr (LORA) t += lora_delta<DT>(lora_B + row * R, lora_t + n * R, R);
@@ -277,21 +228,8 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
 
 std::atomic<int> g_wide_nf4_variant{-1};  // sweep hook: 1 / 2 = 16 / 32 weight rows per workgroup, anything else = the heuristic
 
-struct WideNf4Args {
-    const void *x;
-    const uint8_t *W;
-    const float *absmax;
-    const void *bias, *residual;
-    void *out;
-    int B, M, K, mode;
-    hipStream_t stream;
-    const void *lora_B = nullptr;  // LORA instantiations only
-    const float *lora_t = nullptr;
-    int R = 0;
-};
-
 template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA>
-void launch_wide_nf4(const WideNf4Args &a) {
+void launch_wide_nf4(const Nf4GemmArgs &a) {
     hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED, LORA>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512),
                        0, a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
                        reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
@@ -299,7 +237,7 @@ void launch_wide_nf4(const WideNf4Args &a) {
 }
 
 template <int DT, int NT, bool FUSED, bool LORA>
-void dispatch_wide_nf4_nt(const WideNf4Args &a) {
+void dispatch_wide_nf4_nt(const Nf4GemmArgs &a) {
     const int M = a.M, K = a.K;
     // 32 weight rows per workgroup halve the x traffic from L2, the kernel's largest stream: taken once that still fills three
     // quarters of the chip (the FP4 wide kernels' rule; measured here on either side of it, profiles/nf4_wide_batch.json)
@@ -316,7 +254,7 @@ void dispatch_wide_nf4_nt(const WideNf4Args &a) {
 
 // one launch: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
 template <int DT, bool FUSED, bool LORA = false>
-void dispatch_wide_nf4(const WideNf4Args &a) {
+void dispatch_wide_nf4(const Nf4GemmArgs &a) {
     switch ((a.B + 15) / 16) {
         case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED, LORA>(a);
         case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED, LORA>(a);
@@ -327,17 +265,8 @@ void dispatch_wide_nf4(const WideNf4Args &a) {
 
 }  // namespace
 
-void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                 void *out, int B, int M, int K, int mode, hipStream_t stream);  // gemm_small_nf4.hip
-void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                const void *lora_B, const float *lora_t, int R, void *out, int B, int M, int K, int mode,
-                                hipStream_t stream);  // gemm_small_nf4.hip
-
 void set_wide_nf4_variant(int v) { g_wide_nf4_variant.store(v, std::memory_order_relaxed); }
 
-}  // namespace fp4
-
-namespace fp4 {
 namespace {
 
 // fused = false: fp4_hip_gemm_wide_nf4.  fused = true: fp4_hip_gemm_fused_nf4 (same coverage and forwarding, plus residual / mode).
@@ -345,29 +274,9 @@ namespace {
 int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                         const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode,
                         void *stream, bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0) {
-    if (B < 0 || M < 0 || K <= 0 || blocksize <= 0 || (lora && R < 0)) {
-        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", name, (long long)B, (long long)M,
-                  (long long)K, blocksize);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    if ((mode & kModeSiluMulPairs) && (M & 1)) {
-        set_error("%s: the gate|up epilogue needs an even row count, got M=%lld", name, (long long)M);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
-    // the kernel addresses with 64-bit element offsets: M * K may pass 2^32; the bounds keep the int row / block arithmetic in range
-    if (B > (lora ? 64 : 128) || blocksize != 64 || (K % 64) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) || (align & 15u) != 0 ||
-        M > (int64_t(1) << 30) || K > (int64_t(1) << 24)) {
-        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..%d rows, blocksize 64, "
-                  "K %% 64 == 0, fp16 / bf16, 16-byte aligned x and packed); use dequant + GEMM",
-                  name, (long long)B, (long long)M, (long long)K, blocksize, dtype, lora ? 64 : 128);
-        return FP4_ERR_UNSUPPORTED;
-    }
+    if (const int rc = nf4_check_args(name, lora ? 64 : 128, 64, x, packed, absmax, out, B, M, K, blocksize, dtype, mode, lora, lora_B, lora_t, R))
+        return rc;
     if (M == 0 || B == 0) return FP4_OK;
-    if (!x || !packed || !absmax || !out || (lora && (!lora_B || !lora_t))) {
-        set_error("%s: null pointer", name);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (lora) {
         if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
@@ -375,11 +284,8 @@ int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8
             gemm_small_nf4_lora_launch(dtype, x, packed, absmax, bias, residual, lora_B, lora_t, (int)R, out, (int)B, (int)M, (int)K, mode, s);
             return check_launch(name);
         }
-        const WideNf4Args a{x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s, lora_B, lora_t, (int)R};
-        if (dtype == FP4_DTYPE_F16)
-            dispatch_wide_nf4<FP4_DTYPE_F16, true, true>(a);
-        else
-            dispatch_wide_nf4<FP4_DTYPE_BF16, true, true>(a);
+        const Nf4GemmArgs a{x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s, lora_B, lora_t, (int)R};
+        with_dtype(dtype, [&](auto dt) { dispatch_wide_nf4<decltype(dt)::value, true, true>(a); });
         return check_launch(name);
     }
     // 1..16 rows on a K the 2..16-row kernel covers: that kernel, bit for bit
@@ -394,7 +300,7 @@ int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8
     const int64_t first = B > 64 ? (B + 1) / 2 : B;
     for (int64_t b0 = 0; b0 < B; b0 += first) {
         const int rows = (int)(B - b0 < first ? B - b0 : first);
-        const WideNf4Args a{static_cast<const uint8_t *>(x) + b0 * K * esize,
+        const Nf4GemmArgs a{static_cast<const uint8_t *>(x) + b0 * K * esize,
                             packed,
                             absmax,
                             bias,
@@ -405,10 +311,10 @@ int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8
                             (int)K,
                             mode,
                             s};
-        if (dtype == FP4_DTYPE_F16)
-            fused ? dispatch_wide_nf4<FP4_DTYPE_F16, true>(a) : dispatch_wide_nf4<FP4_DTYPE_F16, false>(a);
-        else
-            fused ? dispatch_wide_nf4<FP4_DTYPE_BF16, true>(a) : dispatch_wide_nf4<FP4_DTYPE_BF16, false>(a);
+        with_dtype(dtype, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value;
+            fused ? dispatch_wide_nf4<DT, true>(a) : dispatch_wide_nf4<DT, false>(a);
+        });
     }
     return check_launch(name);
 }

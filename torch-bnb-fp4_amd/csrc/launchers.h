@@ -1,0 +1,34 @@
+// Host functions that one translation unit defines and another calls.  The calling file includes this header, and so does the
+// defining file among the matrix-core sources (gemm_*_fp4.hip, gemm_*_nf4.hip), so one declaration is read beside the definition
+// and beside every call instead of a hand-written copy at the point of use.  The four sweep hooks of the GEMV, dequant and quantiser sources are declared here
+// for capi.hip only; a file that defines one should include this header the next time it is edited.
+#pragma once
+
+#include "fp4_common.h"
+
+namespace fp4 {
+
+// gemm_small_nf4.hip, for the fused entry points of gemm_wide_nf4.hip (which validate): 1..16 rows, K % 512 == 0.  Launch only.
+void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
+                                 void *out, int B, int M, int K, int mode, hipStream_t stream);
+void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
+                                const void *lora_B, const float *lora_t, int R, void *out, int B, int M, int K, int mode,
+                                hipStream_t stream);
+
+// gemm_wide_fp4.hip, gemm_splitk_fp4.hip, for gemm_small_fp4.hip: FP4_OK after the launch, -1 where the shape is not theirs
+int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
+                     int B, int M, int K, int mode, bool any_rows, hipStream_t stream);
+int gemm_splitk_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
+                       int B, int M, int K, int mode, void *workspace, int64_t workspace_bytes, hipStream_t stream);
+int64_t gemm_splitk_workspace_bytes(int64_t B, int64_t M, int64_t K, int blocksize, int dtype);
+
+// sweep hooks behind fp4_hip_set_variant (capi.hip), each defined beside the kernels it steers
+void set_dequant_variant(int v);       // dequant_fp4.hip
+void set_gemv_variant(int v);          // gemv_fp4.hip
+void set_small_variant(int v);         // gemm_small_fp4.hip
+void set_wide_variant(int v);          // gemm_wide_fp4.hip
+void set_quantize_variant(int v);      // quantize_fp4.hip
+void set_gemv_nf4_variant(int v);      // gemv_nf4.hip
+void set_wide_nf4_variant(int v);      // gemm_wide_nf4.hip
+
+}  // namespace fp4
