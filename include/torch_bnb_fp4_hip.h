@@ -347,6 +347,46 @@ FP4_HIP_API int fp4_hip_gemm_lora_nf4(const void *x, const uint8_t *packed, cons
                                       int blocksize, int dtype, int epilogue, void *stream);
 
 /*
+ * Several adapters in one batch, selected per activation row on the device (sequence 0 one tenant's fine-tune, sequence 1 another's,
+ * sequence 2 the bare base model): still one pass over the packed weight per step, whatever the mix.  Not in the reference.
+ * Additions to ABI version 7.  All device memory:
+ *   A_stack : T[n_adapters][R][K]        the single-adapter A arrays one after another
+ *   B_stack : T[n_adapters][M][R]        over the weight's own row order (interleaved for a gate|up weight)
+ *   scale_stack : float[n_adapters][R]   ids : int32[rows], the adapter of each activation row
+ * An id outside 0 .. n_adapters - 1 (negative values included) means "no adapter for this row"; no address is formed from such an
+ * id.  ids is read on the device only - no host read, no synchronisation - so a captured step follows an in-place rewrite of ids.
+ * The slice offsets id * R * K and id * M * R are 64-bit.  Adapters of different ranks are zero-padded to one R (exact).
+ *
+ * fp4_hip_lora_down_multi: t[b][j] = scale_stack[a][j] * sum_k A_stack[a][j][k] x[b][k] with a = ids[b]; a row without an adapter
+ * gets t[b][:] = +0.0f (written, not skipped).  Row b is bit-identical to row b of fp4_hip_lora_down(x, A_stack[a], scale_stack[a], ..)
+ * on the same x.  Coverage and error codes are fp4_hip_lora_down's (A_stack 16-byte aligned; K % 8 == 0 aligns every slice; at most
+ * 2^20 adapters); in addition n_adapters < 1 or a null ids is FP4_ERR_INVALID_ARGUMENT.  The A fragment is reloaded only when a row's
+ * adapter differs from the previous row's, so a batch sorted by adapter reads A as often as the single-adapter kernel does.
+ *
+ * fp4_hip_gemm_lora_multi_nf4: the coverage of fp4_hip_gemm_lora_nf4 (1..64 rows, blocksize 64, K % 64 == 0, fp16 / bf16, both
+ * epilogues, `residual` may alias `out`).  A row with adapter a is bit-identical to the same row of fp4_hip_gemm_lora_nf4 called with
+ * B_stack[a] and the same t; a row without one is bit-identical to the same row of fp4_hip_gemm_fused_nf4 - the add is skipped, not
+ * done with zero, so a -0 sum keeps its sign.  The gated epilogue applies the same rule to the gate row and the up row.
+ * t : float[B, R] (fp4_hip_lora_down_multi's output).
+ *
+ * fp4_hip_gemv_lora_multi_nf4: the same for one row (ids : int32[1], t : float[R]): bit-identical to fp4_hip_gemv_lora_nf4 with the
+ * slice ids[0] names, or to fp4_hip_gemv_fused_nf4 where it names none - so that a captured one-row step follows ids as well.
+ *
+ * Both: n_adapters < 1 or a null ids is FP4_ERR_INVALID_ARGUMENT; B_stack and t 16-byte aligned, R % 8 == 0 in 8..256, else
+ * FP4_ERR_UNSUPPORTED with nothing launched and out untouched, as for the single-adapter forms.
+ */
+FP4_HIP_API int fp4_hip_lora_down_multi(const void *x, const void *A_stack, const float *scale_stack, const int32_t *ids, float *t,
+                                        int64_t Bt, int64_t n_adapters, int64_t R, int64_t K, int dtype, void *stream);
+FP4_HIP_API int fp4_hip_gemm_lora_multi_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias,
+                                            const void *residual, const void *B_stack, const int32_t *ids, int64_t n_adapters,
+                                            const float *t, int64_t R, void *out, int64_t B, int64_t M, int64_t K, int blocksize,
+                                            int dtype, int epilogue, void *stream);
+FP4_HIP_API int fp4_hip_gemv_lora_multi_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias,
+                                            const void *residual, const void *B_stack, const int32_t *ids, int64_t n_adapters,
+                                            const float *t, int64_t R, void *out, int64_t M, int64_t K, int blocksize, int dtype,
+                                            int epilogue, void *stream);
+
+/*
  * Nested (double-quantised) absmax -- bitsandbytes' compress_statistics (bnb_4bit_use_double_quant=True, the QLoRA recipe): the
  * per-block scales of a 4-bit weight are themselves quantised.  Per weight with nb = ceil(M*K / blocksize) blocks and g = nested_blocksize:
  *   absmax_u8 : uint8[nb]      nested_absmax : float[ceil(nb / g)]      code256 : float[256]      offset : one float

@@ -11,6 +11,9 @@ and is replaced by an identity on q (the GEMV traffic is what is being measured)
     python tools/decode_bench.py [--model mistral7b|llama3-8b] [--layers 32] [--tokens 64] [--fuse] [--epilogues]
     python tools/decode_bench.py --nf4 --epilogues --lora 16 [--lora-unfused]    # QLoRA serving: random rank-16 adapters on q, k, v,
                                                                               # o, gate, up and down of every layer
+    python tools/decode_bench.py --nf4 --epilogues --lora 16 --adapters 4 --batch 8 [--adapters-grouped]
+                                                                              # a mixed batch: 4 adapters, round-robin over the
+                                                                              # sequences, chosen per row on the device
     torchrun --nproc-per-node N tools/decode_bench.py --model llama3-8b      # tensor parallel: q/k/v/gate/up M-split,
                                                                               # o/down K-split + all-reduce
 
@@ -44,7 +47,7 @@ def fp4_bytes(m, k):
 
 def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epilogues=False, batch=1,
                    reference_dispatch=False, allreduce="dist", lm_head=True, seed=7, lean_glue=False, tensor_parallel=None, nf4=False,
-                   lora=0, lora_unfused=False):
+                   lora=0, lora_unfused=False, n_adapters=0, adapters_grouped=False):
     """Builds the FP4 layers of a `cfg`-shaped decoder and returns (token_fn, h0, meta).
 
     world == 1: QuantData dispatchers (the product's single-GPU path).  world > 1: Column/RowParallelFP4Linear
@@ -54,7 +57,11 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
     modules even for a one-rank group (bench.py's FP4_BENCH_FORCE_GROUP rehearsal of the N > 1 path through real RCCL on one GPU).
     lora (with nf4 and epilogues, single GPU): random adapters of that rank on q, k, v, o, gate, up and down of every layer, run by
     LoRANF4Linear (down projection + the adapter term inside the fused kernels); lora_unfused: the same adapters as torch ops around
-    FusedNF4Linear (three small products, a scale and an add per adapted Linear - what the op surface offered before)."""
+    FusedNF4Linear (three small products, a scale and an add per adapted Linear - what the op surface offered before).
+    n_adapters (with lora): that many adapters per adapted Linear, adapter b % n_adapters for sequence b, run by MultiLoRANF4Linear
+    (one pass over each weight, the adapter chosen per row on the device from the AdapterSelection returned as meta["selection"]);
+    adapters_grouped: the same adapters the way a single-adapter layer serves a mixed batch - rows grouped by adapter on the host and,
+    per group, index_select -> LoRANF4Linear -> index_copy."""
     import torch_bnb_fp4 as pkg
     from torch_bnb_fp4 import parallel as par
 
@@ -92,6 +99,15 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
 
     if lora and not (nf4 and epilogues and not tp):
         raise ValueError("lora needs nf4 and epilogues on a single GPU")
+    if n_adapters and (not lora or lora_unfused):
+        raise ValueError("n_adapters needs lora and the fused adapter kernels")
+    selection = None
+    if n_adapters:
+        from torch_bnb_fp4 import fused as _fused
+
+        row_ids = [b % n_adapters for b in range(batch)]
+        selection = _fused.AdapterSelection(dev, capacity=max(64, batch)).set(row_ids)
+        groups = [torch.tensor([b for b in range(batch) if row_ids[b] == a], dtype=torch.int64, device=dev) for a in range(n_adapters)]
 
     def adapters(ms, k, interleave=False):
         """Random adapters of rank `lora` for projections of ms[i] x k stacked into one weight's rows: (A [n r, k], B [sum m, n r]
@@ -115,6 +131,22 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
         dtype (peft's sequence) added to the rows of the fused base op, then the epilogue's own ops."""
         from torch_bnb_fp4 import fused
 
+        if n_adapters and not adapters_grouped:
+            return fused.MultiLoRANF4Linear.from_fused(layer, [adapters(ms, k, interleave) for _ in range(n_adapters)], selection)
+        if n_adapters:
+            singles = [fused.LoRANF4Linear.from_fused(layer, *adapters(ms, k, interleave)) for _ in range(n_adapters)]
+
+            def run_grouped(x, residual=None):
+                out = None
+                for single, idx in zip(singles, groups):
+                    if idx.numel() == 0:
+                        continue
+                    y = single(x.index_select(0, idx), None if residual is None else residual.index_select(0, idx))
+                    if out is None:
+                        out = y.new_empty(x.shape[0], y.shape[-1])
+                    out.index_copy_(0, idx, y)
+                return out
+            return run_grouped
         A, B, sc = adapters(ms, k, interleave)
         if not lora_unfused:
             return fused.LoRANF4Linear.from_fused(layer, A, B, sc)
@@ -214,7 +246,7 @@ def build_token_fn(cfg, dev, dtype, world=1, rank=0, group=None, fuse=False, epi
     meta = dict(layers=L, fp4_bytes_per_token_per_gpu=per_token_fp4, lm_head_bytes=(V * H * 2 if lm_head else 0),
                 fp4_linear_calls_per_token=(4 if (fuse or epilogues) else 7) * L,
                 allreduces_per_token=(2 * L if tp else 0),  # issued by the K-split layers (also by a forced one-rank group: reduce_single_rank)
-                collective_ranks=world if tp else 0)
+                collective_ranks=world if tp else 0, selection=selection)
     return token, h0, meta
 
 
@@ -279,6 +311,11 @@ def main():
                     help="with --nf4 --epilogues: random rank-R LoRA adapters on q, k, v, o, gate, up and down of every layer (LoRANF4Linear)")
     ap.add_argument("--lora-unfused", action="store_true",
                     help="with --lora: the same adapters as torch ops around FusedNF4Linear instead of the fused LoRA kernels")
+    ap.add_argument("--adapters", type=int, default=0, metavar="N",
+                    help="with --lora: N adapters per adapted Linear, adapter b %% N for sequence b, chosen per row on the device "
+                         "(MultiLoRANF4Linear); one captured step is also replayed under a second id vector and checked against eager")
+    ap.add_argument("--adapters-grouped", action="store_true",
+                    help="with --adapters: rows grouped by adapter on the host and, per group, index_select -> LoRANF4Linear -> index_copy")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--lean-glue", action="store_true",
                     help="attention stand-in as ONE elementwise launch and no rescale: what is left besides the FP4 Linears is minimal")
@@ -304,7 +341,8 @@ def main():
     dtype = getattr(torch, args.dtype)
     token, h0, meta = build_token_fn(cfg, dev, dtype, world, rank, fuse=args.fuse, epilogues=args.epilogues, batch=args.batch,
                                      reference_dispatch=args.reference_dispatch, allreduce=args.allreduce, lean_glue=args.lean_glue, nf4=args.nf4,
-                                     lora=args.lora, lora_unfused=args.lora_unfused)
+                                     lora=args.lora, lora_unfused=args.lora_unfused, n_adapters=args.adapters,
+                                     adapters_grouped=args.adapters_grouped)
 
     def barrier():
         torch.cuda.synchronize()
@@ -315,6 +353,33 @@ def main():
                     barrier=barrier)
     if t["graph_error"] and rank == 0:
         print("graph capture failed:", t["graph_error"], file=sys.stderr)
+    follows = None
+    if args.adapters and not args.adapters_grouped and not args.no_graph:
+        # one captured step, replayed under two id vectors: the second differs from the first and equals eager under the same ids
+        sel = meta["selection"]
+        first = [b % args.adapters for b in range(args.batch)]
+        second = [(b + 1) % args.adapters if b % 3 else -1 for b in range(args.batch)]
+        with torch.inference_mode():
+            g, static_h, side = torch.cuda.CUDAGraph(), h0.clone(), torch.cuda.Stream()
+            with torch.cuda.stream(side):
+                token(static_h)
+                torch.cuda.synchronize()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    static_out = token(static_h)
+            torch.cuda.synchronize()
+            g.replay()
+            torch.cuda.synchronize()
+            out_first = static_out.clone()
+            sel.set(second)
+            g.replay()
+            torch.cuda.synchronize()
+            out_second = static_out.clone()
+            eager_second = token(static_h)
+            sel.set(first)
+            as_bits = lambda t: t.contiguous().view(torch.int16)  # noqa: E731  (NaN-proof: the bits are compared)
+            follows = {"second_ids_change_the_output": not torch.equal(as_bits(out_first), as_bits(out_second)),
+                       "replay_equals_eager_under_second_ids": bool(torch.equal(as_bits(out_second), as_bits(eager_second))),
+                       "outputs_finite": bool(torch.isfinite(out_second.float()).all())}
     if world > 1 and args.allreduce == "oneshot":
         # sync point outside capture: a reduction that timed out waiting for a peer wrote NaN - the figure must not be reported
         from torch_bnb_fp4 import parallel as par
@@ -335,7 +400,11 @@ def main():
             "hbm_floor_ms_per_token_at_8TBps": round((per_token_fp4 + meta["lm_head_bytes"]) / 8e12 * 1e3, 3),
             "quant_type": "nf4" if args.nf4 else "fp4",
             "lora_rank": args.lora, "lora_path": (None if not args.lora else "torch ops around FusedNF4Linear" if args.lora_unfused
-                                                  else "LoRANF4Linear (down projection + fused adapter term)"),
+                                                  else "LoRANF4Linear (down projection + fused adapter term)" if not args.adapters
+                                                  else "rows grouped by adapter: index_select -> LoRANF4Linear -> index_copy" if args.adapters_grouped
+                                                  else "MultiLoRANF4Linear (adapter chosen per row on the device)"),
+            "adapters": args.adapters, "adapter_ids": ([b % args.adapters for b in range(args.batch)] if args.adapters else None),
+            "captured_step_follows_ids": follows,
             "data": "synthetic random FP4 bytes + scales; attention replaced by identity; lm_head dense " + args.dtype,
         }), file=result_out, flush=True)
     if world > 1:

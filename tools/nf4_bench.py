@@ -34,6 +34,15 @@ fp16, one run on the same operands, all through the torch ops as the layers issu
 plain rows, add and apply silu * up itself.  A cell is won where (a) is ahead of (b) by more than both replay-to-replay ranges together.
 --lora-ranks / --lora-rows replace the rank and row lists.
 
+--multi-lora: several adapters in one batch (profiles/nf4_multi_lora.json), bf16, the four decoder shapes, 8 / 32 / 64 rows, rank 16 /
+64, 1 / 4 / 8 distinct adapters in the batch with the ids sorted and interleaved, one run on the same operands, the protocol of --lora.
+(a) lora_down_multi + gemm_nf4_lora_multi over a stack of 8 adapters; (b) the best a single-adapter layer offers for a mixed batch:
+rows grouped by adapter on the host and, per group, index_select -> LoRANF4Linear -> index_copy; with one distinct adapter (b) is the
+single-adapter fused pair itself, so that column shows what the indirection alone costs.  A cell is ahead / level / behind by more
+than both replay-to-replay ranges together.  With --baseline-lib the plain and the single-adapter entry points (gemv_fused_nf4,
+gemm_fused_nf4, lora_down, gemm_lora_nf4) also run through another build of the library (the parent commit's) side by side; "within"
+as for --fused.
+
 --nested: double-quantised absmax (profiles/nf4_nested.json), bf16, the four decoder shapes, one run on the same operands, the
 protocol of --fused.  (1) fp4_hip_gemv_nested_nf4 on the compressed statistics against fp4_hip_gemv_fused_nf4 on their expansion
 (level / ahead / behind beyond both replay-to-replay ranges).  (2) The plain fp4_hip_gemv_nf4 of this tree's library and, with
@@ -428,6 +437,112 @@ def lora(args):
                       "cells": cells}))
 
 
+def multi_lora(args):
+    from torch_bnb_fp4 import fused
+
+    dev = torch.device("cuda", 0)
+    dtype, dt = torch.bfloat16, DT[torch.bfloat16]
+    N_STACK = 8
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def timed(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        med, samples = time_replays(replay, args.reps, args.launches)
+        q = sorted(samples)
+        return {"us": round(med, 2), "min_us": round(q[0], 2), "max_us": round(q[-1], 2)}
+
+    def bind(l):
+        l.fp4_hip_gemv_fused_nf4.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp]
+        l.fp4_hip_gemm_fused_nf4.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
+        l.fp4_hip_lora_down.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, vp]
+        l.fp4_hip_gemm_lora_nf4.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i32, i32, i32, vp]
+        return l
+
+    libs = {"this_tree": bind(ctypes.CDLL(pkg.HIP_LIBRARY_PATH))}
+    if args.baseline_lib:
+        libs["baseline"] = bind(ctypes.CDLL(os.path.abspath(args.baseline_lib)))
+    rng_of = lambda t: t["max_us"] - t["min_us"]  # noqa: E731
+    gen = torch.Generator(device=dev).manual_seed(0)
+    cells, unchanged = [], []
+    for M, K in SHAPES:
+        packed = torch.randint(0, 256, (M * K // 2,), dtype=torch.uint8, device=dev, generator=gen)
+        absmax = torch.rand(M * K // BS, device=dev, generator=gen) * 0.02 + 0.002
+        B_t = packed.view(-1, 1).t()
+        epi = 1 if M == 28672 else 0  # the gate|up weight of the decoder
+        base = fused.FusedNF4Linear(fused.FusedNF4Linear.from_packed(packed.view(-1, 1), absmax, (M, K), BS, dtype=dtype).quant_data, epi)
+        Mo = M // 2 if epi else M
+        if args.baseline_lib:  # the entry points that existed before, through both libraries: ISA-identical, so within the ranges
+            x1, x32 = (torch.randn(r, K, device=dev, generator=gen).to(dtype) for r in (1, 32))
+            A16 = (torch.randn(16, K, device=dev, generator=gen) / K ** 0.5).to(dtype)
+            B16 = (torch.randn(M, 16, device=dev, generator=gen) * 0.05).to(dtype)
+            sc16, t32 = torch.full((16,), 2.0, device=dev), torch.zeros(32, 16, device=dev)
+            y1, y32 = torch.empty(1, Mo, dtype=dtype, device=dev), torch.empty(32, Mo, dtype=dtype, device=dev)
+            calls = {
+                "gemv_fused_nf4": lambda l: l.fp4_hip_gemv_fused_nf4(p_(x1), p_(packed), p_(absmax), None, None, p_(y1), M, K, BS, dt, epi, s()),
+                "gemm_fused_nf4_32": lambda l: l.fp4_hip_gemm_fused_nf4(p_(x32), p_(packed), p_(absmax), None, None, p_(y32), 32, M, K, BS, dt, epi, s()),
+                "lora_down_32": lambda l: l.fp4_hip_lora_down(p_(x32), p_(A16), p_(sc16), p_(t32), 32, 16, K, dt, s()),
+                "gemm_lora_nf4_32": lambda l: l.fp4_hip_gemm_lora_nf4(p_(x32), p_(packed), p_(absmax), None, None, p_(B16), p_(t32), 16, p_(y32), 32,
+                                                                      M, K, BS, dt, epi, s()),
+            }
+            for name, call in calls.items():
+                both = {tag: timed(lambda: call(l)) for tag, l in libs.items()}
+                margin = max(rng_of(both["this_tree"]), rng_of(both["baseline"]))
+                delta = both["this_tree"]["us"] - both["baseline"]["us"]
+                unchanged.append({"M": M, "K": K, "entry": name, **both, "delta_us": round(delta, 2), "margin_us": round(margin, 2),
+                                  "within_margin": bool(abs(delta) <= margin)})
+        for R in args.lora_ranks:
+            A_stack = (torch.randn(N_STACK, R, K, device=dev, generator=gen) / K ** 0.5).to(dtype)
+            B_stack = (torch.randn(N_STACK, M, R, device=dev, generator=gen) * 0.05).to(dtype)
+            s_stack = torch.full((N_STACK, R), 2.0, device=dev)
+            singles = [fused.LoRANF4Linear.from_fused(base, A_stack[a], B_stack[a], s_stack[a]) for a in range(N_STACK)]
+            print(f"multi-lora: {M}x{K} rank {R}", file=sys.stderr, flush=True)
+            for rows in args.lora_rows:
+                if rows < 2:
+                    continue
+                x = torch.randn(rows, K, device=dev, generator=gen).to(dtype)
+                for distinct in (1, 4, 8):
+                    for order in (("sorted",) if distinct == 1 else ("sorted", "interleaved")):
+                        ids = [b * distinct // rows for b in range(rows)] if order == "sorted" else [b % distinct for b in range(rows)]
+                        idt = torch.tensor(ids, dtype=torch.int32, device=dev)
+                        groups = [torch.tensor([b for b in range(rows) if ids[b] == a], dtype=torch.int64, device=dev) for a in range(distinct)]
+
+                        def multi():
+                            t = pkg.ext.lora_down_multi(x, A_stack, s_stack, idt)
+                            return pkg.ext.gemm_nf4_lora_multi(x, B_t, absmax, BS, [M, K], None, None, epi, B_stack, idt, t)
+
+                        def grouped():
+                            if distinct == 1:  # the single-adapter fused pair, as LoRANF4Linear issues it where it is ahead
+                                return pkg.ext.gemm_nf4_lora(x, B_t, absmax, BS, [M, K], None, None, epi, B_stack[0], pkg.ext.lora_down(x, A_stack[0], s_stack[0]))
+                            out = torch.empty(rows, Mo, dtype=dtype, device=dev)
+                            for a, idx in enumerate(groups):
+                                out.index_copy_(0, idx, singles[a](x.index_select(0, idx)))
+                            return out
+
+                        same = bool(torch.equal(multi(), grouped()))
+                        ta, tb = timed(multi), timed(grouped)
+                        spread = rng_of(ta) + rng_of(tb)
+                        delta = tb["us"] - ta["us"]
+                        cells.append({"M": M, "K": K, "epilogue": "silu_mul" if epi else "none", "rank": R, "rows": rows, "distinct_adapters": distinct,
+                                      "ids": order, "lora_fused_ahead": bool(fused.lora_fused_ahead(rows, M, K, R)),
+                                      "fused_multi": ta, "baseline": tb,
+                                      "baseline_is": "single-adapter fused pair" if distinct == 1 else "grouped index_select / LoRANF4Linear / index_copy",
+                                      "same_values_as_baseline": same, "saved_us": round(delta, 2), "speedup": round(tb["us"] / ta["us"], 3),
+                                      "spread_us": round(spread, 2),
+                                      "verdict": "level" if abs(delta) <= spread else ("ahead" if delta > 0 else "behind")})
+            del A_stack, B_stack, singles
+        del packed, absmax, base
+    inside = [c for c in cells if c["lora_fused_ahead"] and c["distinct_adapters"] > 1]
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "revision": args.revision, "dtype": "bf16", "blocksize": BS, "adapters_in_stack": N_STACK,
+                      "launches_per_graph": args.launches, "reps": args.reps,
+                      "baseline_lib": "the parent commit's library, same run" if args.baseline_lib else "not measured",
+                      "pre_existing_entry_points_all_within_margin": (all(u["within_margin"] for u in unchanged) if unchanged else None),
+                      "mixed_cells_inside_lora_fused_ahead": len(inside), "of_which_ahead": sum(c["verdict"] == "ahead" for c in inside),
+                      "of_which_level": sum(c["verdict"] == "level" for c in inside), "of_which_behind": sum(c["verdict"] == "behind" for c in inside),
+                      "pre_existing_entry_points": unchanged, "cells": cells}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -441,10 +556,16 @@ def main():
     ints = lambda v: [int(i) for i in v.split(",")]  # noqa: E731
     ap.add_argument("--lora-ranks", type=ints, default=[16, 64], help="--lora: adapter ranks (multiples of 8), comma-separated")
     ap.add_argument("--lora-rows", type=ints, default=[1, 8, 32, 64], help="--lora: activation row counts (1..64), comma-separated")
+    ap.add_argument("--multi-lora", action="store_true",
+                    help="several adapters per batch, fused multi-adapter ops against rows grouped by adapter (profiles/nf4_multi_lora.json)")
     ap.add_argument("--nested", action="store_true", help="double-quantised absmax: the nested GEMV, unnest and qlinear_nf4_nested (profiles/nf4_nested.json)")
     args = ap.parse_args()
     if args.nested:
         return nested(args)
+    if args.multi_lora:
+        if args.lora_rows == [1, 8, 32, 64]:
+            args.lora_rows = [8, 32, 64]
+        return multi_lora(args)
     if args.lora:
         return lora(args)
     if args.fused:

@@ -18,6 +18,10 @@
 // LoRA adapter term (fp4_hip_gemm_lora_nf4, 2..16 rows with K % 512 == 0): the LORA instantiations (always FUSED) add
 // delta[n][row] = sum_j f32(lora_B[row][j]) * lora_t[n][j] (lora_nf4.h) to the thread's finished f32 sum ahead of the epilogue, and
 // to the up row's likewise; lora_t = s * A x is lora_down_kernel's f32 output.
+//
+// Several adapters per batch (fp4_hip_gemm_lora_multi_nf4): the MULTI instantiations (always LORA) take a stack of B arrays and read
+// the adapter of activation row n from lora_ids[n] on the device, once per (n) a thread owns; a row without an adapter is stored as
+// the FUSED instantiation stores it.
 #include "launchers.h"
 #include "nf4_mfma.h"
 
@@ -32,12 +36,16 @@ namespace {
 // follow its bytes), x image row stride 128*NBW + 16, as in the FP4 kernel.
 // FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
-template <int DT, int NBW, int XS, bool FUSED, bool LORA = false>
+// MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R] and lora_ids[n] names activation row n's adapter; a row
+// whose id names none takes the FUSED store as it is (the add is skipped, not done with zero).
+template <int DT, int NBW, int XS, bool FUSED, bool LORA = false, bool MULTI = false>
 __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
                                                             uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode,
-                                                            const uint16_t *lora_B, const float *lora_t, int R) {
+                                                            const uint16_t *lora_B, const float *lora_t, int R, const int *lora_ids,
+                                                            int n_adapters) {
     static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
+    static_assert(!MULTI || LORA, "the adapter stack comes with the adapter term");
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kXStride = 128 * NBW + 16;
     constexpr int kWImageBytes = 8 * 16 * kStageStride;
@@ -185,10 +193,19 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
                     float u = 0.0f;
 #pragma unroll
                     for (int w = 0; w < 8; ++w) u += s_part[w][tid + 1];
-                    if (row < M && n < B) store_nf4_pair<DT, LORA>(out, bias, residual, lora_B, lora_t, R, n, row, M, t, u);
+                    if constexpr (MULTI) {
+                        if (row < M && n < B) store_nf4_pair_multi<DT>(out, bias, residual, lora_B, lora_ids, n_adapters, lora_t, R, n, row, M, t, u);
+                    } else {
+                        if (row < M && n < B) store_nf4_pair<DT, LORA>(out, bias, residual, lora_B, lora_t, R, n, row, M, t, u);
+                    }
                 }
             } else if (row < M && n < B) {
-                if constexpr (LORA) t += lora_delta<DT>(lora_B + int64_t(row) * R, lora_t + n * R, R);
+                if constexpr (MULTI) {
+                    if (const uint16_t *slice = lora_stack_slice(lora_B, lora_ids, n_adapters, n, M, R))
+                        t += lora_delta<DT>(slice + int64_t(row) * R, lora_t + n * R, R);
+                } else if constexpr (LORA) {
+                    t += lora_delta<DT>(lora_B + int64_t(row) * R, lora_t + n * R, R);
+                }
                 store_small<DT>(out, bias, residual, n, row, M, t);
             }
         } else {
@@ -197,15 +214,15 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     }
 }
 
-template <int DT, int NBW, int XS, bool FUSED, bool LORA>
+template <int DT, int NBW, int XS, bool FUSED, bool LORA, bool MULTI>
 void launch_nf4_mfma(const Nf4GemmArgs &a) {
-    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED, LORA>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
+    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED, LORA, MULTI>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
                        reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
                        reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
-                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R);
+                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R, a.lora_ids, a.n_adapters);
 }
 
-template <int DT, bool FUSED, bool LORA = false>
+template <int DT, bool FUSED, bool LORA = false, bool MULTI = false>
 void dispatch_nf4_mfma(const Nf4GemmArgs &a) {
     const int B = a.B, M = a.M, K = a.K;
     const int units = K / 512;  // quant blocks per wave over the whole K
@@ -213,12 +230,12 @@ void dispatch_nf4_mfma(const Nf4GemmArgs &a) {
     // the FP4 kernel's rules: at most 4 blocks per wave and pass; x staged per wave in LDS always for <= 4 rows, for 5..8 rows only
     // while the grid is a single round anyway (the larger image leaves fewer workgroups per CU)
     if (units % 4 == 0) {
-        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED, LORA>(a);
-        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED, LORA>(a);
-        return launch_nf4_mfma<DT, 4, 0, FUSED, LORA>(a);
+        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED, LORA, MULTI>(a);
+        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED, LORA, MULTI>(a);
+        return launch_nf4_mfma<DT, 4, 0, FUSED, LORA, MULTI>(a);
     }
-    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED, LORA>(a);
-    return launch_nf4_mfma<DT, 1, 0, FUSED, LORA>(a);
+    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED, LORA, MULTI>(a);
+    return launch_nf4_mfma<DT, 1, 0, FUSED, LORA, MULTI>(a);
 }
 
 }  // namespace
@@ -237,6 +254,14 @@ void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, cons
                                 hipStream_t stream) {
     const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, lora_B, lora_t, R};
     with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true, true>(a); });
+}
+
+// the same with a stack of adapters and one id per activation row, for fp4_hip_gemm_lora_multi_nf4 (gemm_wide_nf4.hip)
+void gemm_small_nf4_lora_multi_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
+                                      const void *B_stack, const int32_t *ids, int n_adapters, const float *lora_t, int R, void *out, int B,
+                                      int M, int K, int mode, hipStream_t stream) {
+    const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, B_stack, lora_t, R, ids, n_adapters};
+    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true, true, true>(a); });
 }
 
 }  // namespace fp4

@@ -30,6 +30,10 @@
 // LoRA adapter term (fp4_hip_gemm_lora_nf4, 1..64 rows): the LORA instantiations (always FUSED) add
 // delta[n][row] = sum_j f32(lora_B[row][j]) * lora_t[n][j] (lora_nf4.h) to the thread's finished f32 sum ahead of the epilogue, and
 // to the up row's likewise; lora_t = s * A x is lora_down_kernel's f32 output.
+//
+// Several adapters per batch (fp4_hip_gemm_lora_multi_nf4, 1..64 rows): the MULTI instantiations (always LORA) take a stack of B
+// arrays and read the adapter of activation row n from lora_ids[n] on the device, once per (n) of the store loop; a row without an
+// adapter is stored as the FUSED instantiation stores it.
 #include <atomic>
 
 #include "launchers.h"
@@ -45,12 +49,16 @@ namespace {
 // Weight image (per wave): 16 * RT rows of stride 32 * NBW + 32 bytes, the row's NBW scales behind its bytes.
 // FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
-template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA = false>
+// MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R] and lora_ids[n] names activation row n's adapter; a row
+// whose id names none takes the FUSED store as it is (the add is skipped, not done with zero).
+template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA = false, bool MULTI = false>
 __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
                                                             uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode,
-                                                            const uint16_t *lora_B, const float *lora_t, int R) {
+                                                            const uint16_t *lora_B, const float *lora_t, int R, const int *lora_ids,
+                                                            int n_adapters) {
     static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
+    static_assert(!MULTI || LORA, "the adapter stack comes with the adapter term");
     constexpr int kRows = 16 * RT;
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kImageBytes = 8 * kRows * kStageStride;
@@ -214,10 +222,19 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
                     float u = 0.0f;
 #pragma unroll
                     for (int w = 0; w < 4; ++w) u += s_part[w][src + 4];
-                    if (row < M && n < B) store_nf4_pair<DT, LORA>(out, bias, residual, lora_B, lora_t, R, n, row, M, t, u);
+                    if constexpr (MULTI) {
+                        if (row < M && n < B) store_nf4_pair_multi<DT>(out, bias, residual, lora_B, lora_ids, n_adapters, lora_t, R, n, row, M, t, u);
+                    } else {
+                        if (row < M && n < B) store_nf4_pair<DT, LORA>(out, bias, residual, lora_B, lora_t, R, n, row, M, t, u);
+                    }
                 }
             } else if (row < M && n < B) {
-                if constexpr (LORA) t += lora_delta<DT>(lora_B + row * R, lora_t + n * R, R);
+                if constexpr (MULTI) {
+                    if (const uint16_t *slice = lora_stack_slice(lora_B, lora_ids, n_adapters, n, M, R))
+                        t += lora_delta<DT>(slice + row * R, lora_t + n * R, R);
+                } else if constexpr (LORA) {
+                    t += lora_delta<DT>(lora_B + row * R, lora_t + n * R, R);
+                }
                 store_small<DT>(out, bias, residual, n, (int)row, M, t);
             }
         } else {
@@ -228,15 +245,15 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
 
 std::atomic<int> g_wide_nf4_variant{-1};  // sweep hook: 1 / 2 = 16 / 32 weight rows per workgroup, anything else = the heuristic
 
-template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA>
+template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA, bool MULTI>
 void launch_wide_nf4(const Nf4GemmArgs &a) {
-    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED, LORA>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512),
+    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED, LORA, MULTI>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512),
                        0, a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
                        reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
-                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R);
+                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R, a.lora_ids, a.n_adapters);
 }
 
-template <int DT, int NT, bool FUSED, bool LORA>
+template <int DT, int NT, bool FUSED, bool LORA, bool MULTI>
 void dispatch_wide_nf4_nt(const Nf4GemmArgs &a) {
     const int M = a.M, K = a.K;
     // 32 weight rows per workgroup halve the x traffic from L2, the kernel's largest stream: taken once that still fills three
@@ -245,21 +262,21 @@ void dispatch_wide_nf4_nt(const Nf4GemmArgs &a) {
     const bool rt2 = v == 2 || (v != 1 && M >= 24 * device_cu_count());
     const bool nbw4 = K % 256 == 0;
     if (rt2) {
-        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED, LORA>(a);
-        return launch_wide_nf4<DT, NT, 2, 1, FUSED, LORA>(a);
+        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED, LORA, MULTI>(a);
+        return launch_wide_nf4<DT, NT, 2, 1, FUSED, LORA, MULTI>(a);
     }
-    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED, LORA>(a);
-    return launch_wide_nf4<DT, NT, 1, 1, FUSED, LORA>(a);
+    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED, LORA, MULTI>(a);
+    return launch_wide_nf4<DT, NT, 1, 1, FUSED, LORA, MULTI>(a);
 }
 
 // one launch: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
-template <int DT, bool FUSED, bool LORA = false>
+template <int DT, bool FUSED, bool LORA = false, bool MULTI = false>
 void dispatch_wide_nf4(const Nf4GemmArgs &a) {
     switch ((a.B + 15) / 16) {
-        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED, LORA>(a);
-        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED, LORA>(a);
-        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED, LORA>(a);
-        default: return dispatch_wide_nf4_nt<DT, 4, FUSED, LORA>(a);
+        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED, LORA, MULTI>(a);
+        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED, LORA, MULTI>(a);
+        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED, LORA, MULTI>(a);
+        default: return dispatch_wide_nf4_nt<DT, 4, FUSED, LORA, MULTI>(a);
     }
 }
 
@@ -271,13 +288,26 @@ namespace {
 
 // fused = false: fp4_hip_gemm_wide_nf4.  fused = true: fp4_hip_gemm_fused_nf4 (same coverage and forwarding, plus residual / mode).
 // lora = true (with fused): fp4_hip_gemm_lora_nf4, the fused form for at most 64 rows plus the adapter term.
+// multi = true (with lora): fp4_hip_gemm_lora_multi_nf4 - lora_B is a stack of n_adapters adapters, ids[b] the adapter of row b.
 int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                         const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode,
-                        void *stream, bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0) {
+                        void *stream, bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0,
+                        bool multi = false, const int32_t *ids = nullptr, int64_t n_adapters = 0) {
     if (const int rc = nf4_check_args(name, lora ? 64 : 128, 64, x, packed, absmax, out, B, M, K, blocksize, dtype, mode, lora, lora_B, lora_t, R))
         return rc;
     if (M == 0 || B == 0) return FP4_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (multi) {  // lora_B is the stack; the same two kernels by the same rule
+        if (const int rc = lora_check_stack(name, lora_B, ids, n_adapters, lora_t, R)) return rc;
+        if (B <= 16 && K % 512 == 0) {
+            gemm_small_nf4_lora_multi_launch(dtype, x, packed, absmax, bias, residual, lora_B, ids, (int)n_adapters, lora_t, (int)R, out, (int)B,
+                                             (int)M, (int)K, mode, s);
+            return check_launch(name);
+        }
+        const Nf4GemmArgs a{x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s, lora_B, lora_t, (int)R, ids, (int)n_adapters};
+        with_dtype(dtype, [&](auto dt) { dispatch_wide_nf4<decltype(dt)::value, true, true, true>(a); });
+        return check_launch(name);
+    }
     if (lora) {
         if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
         if (B <= 16 && K % 512 == 0) {
@@ -347,4 +377,16 @@ extern "C" int fp4_hip_gemm_lora_nf4(const void *x, const uint8_t *packed, const
     }
     return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_lora_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
                                     epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R);
+}
+
+extern "C" int fp4_hip_gemm_lora_multi_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                           const void *B_stack, const int32_t *ids, int64_t n_adapters, const float *t, int64_t R, void *out,
+                                           int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
+    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
+        fp4::set_error("fp4_hip_gemm_lora_multi_nf4: unknown epilogue %d", epilogue);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_lora_multi_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
+                                    epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, B_stack, t, R, true,
+                                    ids, n_adapters);
 }

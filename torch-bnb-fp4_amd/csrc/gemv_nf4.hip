@@ -28,6 +28,11 @@
 // partial deltas go through a second copy of the dpp chain (not through p[it]: the plain sum keeps its order and its bits) and
 // sum + delta is one f32 add.  With KSPLIT > 1 only the kw == 0 wave of a row carries the term, through a column of its own in s_part.
 //
+// Several adapters, chosen on the device (fp4_hip_gemv_lora_multi_nf4): the MULTI instantiations (always LORA) take a stack of B arrays
+// and read the row's adapter from lora_ids[0] (uniform over the grid).  With one, lora_B becomes its slice and everything is the LORA
+// kernel's; without one neither B nor t is read and the delta is not added, so the bits are the FUSED kernel's.  It exists so that a
+// captured one-row step follows an in-place change of the id.
+//
 // Nested (double-quantised) absmax (fp4_hip_gemv_nested_nf4): the NESTED instantiations (always FUSED, never LORA) read the block
 // scale as bitsandbytes' compress_statistics stores it - a uint8 code per block, an f32 scale per 256 blocks, a 256-entry f32 table
 // and an offset - and form absmax = fl32(fl32(table[code] * group) + offset) themselves (unnest_scale, nested_absmax.h): 33 instead
@@ -90,14 +95,23 @@ struct OutPtr<true> {
 // LORA = true (with FUSED): delta[row] = sum_j lora_B[row][j] * lora_t[j] (R % 8 == 0, 8 <= R <= 256) is added to the f32 row sum first.
 // NESTED = true (with FUSED, without LORA): `absmax` points at uint8 codes, one per block; the scale of block i is
 // unnest_scale(nested_code[code[i]], nested_absmax[i >> 8], nested_offset).
-template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED, bool LORA = false, bool NESTED = false>
+// MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R], lora_ids[0] names the adapter; outside 0 .. n_adapters - 1 = none.
+template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED, bool LORA = false, bool NESTED = false, bool MULTI = false>
 __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ x, const uint8_t *__restrict__ W,
                                                        const float *__restrict__ absmax, const void *__restrict__ bias,
                                                        typename OutPtr<FUSED>::type out, int M, int K, int bs_shift,
                                                        const void *residual_arg, int mode,  // new arguments last: the plain kernels keep their argument layout
                                                        const void *lora_B, const float *lora_t, int R,
-                                                       const float *nested_absmax, const float *nested_code, float nested_offset) {
+                                                       const float *nested_absmax, const float *nested_code, float nested_offset,
+                                                       const int *lora_ids, int n_adapters) {
     static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
+    static_assert(!MULTI || LORA, "the adapter stack comes with the adapter term");
+    [[maybe_unused]] bool adapted = LORA;  // MULTI: whether lora_ids[0] names an adapter (uniform)
+    if constexpr (MULTI) {
+        const int id = lora_ids[0];
+        adapted = uint32_t(id) < uint32_t(n_adapters);
+        if (adapted) lora_B = reinterpret_cast<const uint8_t *>(lora_B) + int64_t(id) * M * R * (DT == FP4_DTYPE_F32 ? 4 : 2);
+    }
     static_assert(!NESTED || (FUSED && !LORA), "nested absmax comes with the fused epilogues and without the adapter term");
     const void *residual = FUSED ? residual_arg : nullptr;
     [[maybe_unused]] const bool gated = FUSED && DT != FP4_DTYPE_F32 && (mode & kModeSiluMulPairs);
@@ -140,7 +154,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
     [[maybe_unused]] u32x4 lb[LORA ? ITERS : 1][kLbRegs];
     [[maybe_unused]] f32x4 lt[2];
     if constexpr (LORA) {
-        if (kw == 0) {
+        if (kw == 0 && (!MULTI || adapted)) {
             const bool on = 8 * l32 < R;
             const int j8 = on ? l32 : 0;
             lt[0] = reinterpret_cast<const f32x4 *>(lora_t)[2 * j8];
@@ -234,7 +248,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
         v = dpp_add<0x121>(v);
         v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));  // 32-lane row sum
         if constexpr (LORA) {
-            if (kw == 0) {  // wave-uniform
+            if (kw == 0 && (!MULTI || adapted)) {  // wave-uniform
                 f32x4 b0, b1;
                 lora_widen8<DT>(lb[it], b0, b1);
                 float d = lora_dot8(b0, b1, lt[0], lt[1], 0.0f);
@@ -274,7 +288,11 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
                     float g = 0.0f, u = 0.0f;
 #pragma unroll
                     for (int k = 0; k < KSPLIT; ++k) g += s_part[2 * tid][k], u += s_part[2 * tid + 1][k];
-                    if constexpr (LORA) g += s_part[2 * tid][KSPLIT], u += s_part[2 * tid + 1][KSPLIT];
+                    if constexpr (MULTI) {
+                        if (adapted) g += s_part[2 * tid][KSPLIT], u += s_part[2 * tid + 1][KSPLIT];
+                    } else if constexpr (LORA) {
+                        g += s_part[2 * tid][KSPLIT], u += s_part[2 * tid + 1][KSPLIT];
+                    }
                     const int row = row_base + 2 * tid;
                     if (row < M)
                         store_silu_mul<DT>(reinterpret_cast<uint16_t *>(out), reinterpret_cast<const uint16_t *>(bias),
@@ -287,7 +305,11 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
             float t = 0.0f;
 #pragma unroll
             for (int k = 0; k < KSPLIT; ++k) t += s_part[tid][k];
-            if constexpr (LORA) t += s_part[tid][KSPLIT];
+            if constexpr (MULTI) {
+                if (adapted) t += s_part[tid][KSPLIT];
+            } else if constexpr (LORA) {
+                t += s_part[tid][KSPLIT];
+            }
             const int row = row_base + tid;
             if (row < M) store_nf4_row<DT>(out, bias, residual, row, t);
         }
@@ -310,23 +332,25 @@ struct Nf4Args {
     const float *nested_absmax = nullptr;  // NESTED instantiations only (absmax then points at the uint8 codes)
     const float *nested_code = nullptr;
     float nested_offset = 0.0f;
+    const int32_t *lora_ids = nullptr;  // MULTI instantiations only: lora_B is then the stack
+    int n_adapters = 0;
 };
 
-template <int DT, int KSPLIT, int G, int ITERS, bool FUSED, bool LORA, bool NESTED>
+template <int DT, int KSPLIT, int G, int ITERS, bool FUSED, bool LORA, bool NESTED, bool MULTI>
 void launch_nf4(bool pair, const Nf4Args &a) {
     constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
     const dim3 grid((unsigned)((a.M + rows_per_block - 1) / rows_per_block)), block(256);
     if (pair)
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED, LORA, NESTED>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED, LORA, NESTED, MULTI>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
                            a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R, a.nested_absmax, a.nested_code,
-                           a.nested_offset);
+                           a.nested_offset, a.lora_ids, a.n_adapters);
     else
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED, LORA, NESTED>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED, LORA, NESTED, MULTI>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
                            a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R, a.nested_absmax, a.nested_code,
-                           a.nested_offset);
+                           a.nested_offset, a.lora_ids, a.n_adapters);
 }
 
-template <int DT, bool FUSED, bool LORA = false, bool NESTED = false>
+template <int DT, bool FUSED, bool LORA = false, bool NESTED = false, bool MULTI = false>
 void dispatch_nf4(bool pair, const Nf4Args &a) {
     const int M = a.M, K = a.K;
     const int C = K >> 5;
@@ -337,9 +361,9 @@ void dispatch_nf4(bool pair, const Nf4Args &a) {
     while (iters < 4 && M / (2 * (4 / ks) * iters * 2) >= 256) iters *= 2;
 #define NF4_ITERS(KS, GG)                                                                                          \
     switch (iters) {                                                                                               \
-        case 1: return launch_nf4<DT, KS, GG, 1, FUSED, LORA, NESTED>(pair, a);                                           \
-        case 2: return launch_nf4<DT, KS, GG, 2, FUSED, LORA, NESTED>(pair, a);                                           \
-        default: return launch_nf4<DT, KS, GG, 4, FUSED, LORA, NESTED>(pair, a);                                          \
+        case 1: return launch_nf4<DT, KS, GG, 1, FUSED, LORA, NESTED, MULTI>(pair, a);                                           \
+        case 2: return launch_nf4<DT, KS, GG, 2, FUSED, LORA, NESTED, MULTI>(pair, a);                                           \
+        default: return launch_nf4<DT, KS, GG, 4, FUSED, LORA, NESTED, MULTI>(pair, a);                                          \
     }
     if (C <= 32) { NF4_ITERS(1, 1) }
     if (C <= 64) { NF4_ITERS(2, 1) }
@@ -360,11 +384,13 @@ namespace {
 // fused = false: fp4_hip_gemv_nf4 (irregular shapes run the generic kernel).  fused = true: fp4_hip_gemv_fused_nf4 (the fast path or
 // FP4_ERR_UNSUPPORTED with nothing launched).  `name` is the entry point the messages speak for.  lora = true (with fused):
 // fp4_hip_gemv_lora_nf4, the fused form plus the adapter term.  nested_absmax != nullptr (with fused, without lora):
-// fp4_hip_gemv_nested_nf4 - `absmax` then points at the uint8 codes of the compressed statistics.
+// fp4_hip_gemv_nested_nf4 - `absmax` then points at the uint8 codes of the compressed statistics.  multi = true (with lora):
+// fp4_hip_gemv_lora_multi_nf4 - lora_B is a stack of n_adapters adapters and ids[0] names the one to apply.
 int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                    const void *residual, void *out, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream,
                    bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0,
-                   const float *nested_absmax = nullptr, const float *nested_code = nullptr, float nested_offset = 0.0f) {
+                   const float *nested_absmax = nullptr, const float *nested_code = nullptr, float nested_offset = 0.0f,
+                   bool multi = false, const int32_t *ids = nullptr, int64_t n_adapters = 0) {
     if (M < 0 || K < 0 || (K & 1) || blocksize < 2 || (blocksize & 1)) {
         set_error("%s: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", name, (long long)M, (long long)K,
                   blocksize);
@@ -410,6 +436,18 @@ int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *p
             case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, false, true>(pair, a); break;
             case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, false, true>(pair, a); break;
             default: dispatch_nf4<FP4_DTYPE_F32, true, false, true>(pair, a); break;
+        }
+        return check_launch(name);
+    }
+    if (multi) {  // lora_B is the stack
+        if (const int rc = lora_check_stack(name, lora_B, ids, n_adapters, lora_t, R)) return rc;
+        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
+        Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s, lora_B, lora_t, (int)R};
+        a.lora_ids = ids, a.n_adapters = (int)n_adapters;
+        switch (dtype) {
+            case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, true, false, true>(pair, a); break;
+            case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, true, false, true>(pair, a); break;
+            default: dispatch_nf4<FP4_DTYPE_F32, true, true, false, true>(pair, a); break;
         }
         return check_launch(name);
     }
@@ -471,6 +509,18 @@ extern "C" int fp4_hip_gemv_lora_nf4(const void *x, const uint8_t *packed, const
     }
     return fp4::gemv_nf4_entry("fp4_hip_gemv_lora_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
                                epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R);
+}
+
+extern "C" int fp4_hip_gemv_lora_multi_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                           const void *B_stack, const int32_t *ids, int64_t n_adapters, const float *t, int64_t R, void *out,
+                                           int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
+    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
+        fp4::set_error("fp4_hip_gemv_lora_multi_nf4: unknown epilogue %d", epilogue);
+        return FP4_ERR_INVALID_ARGUMENT;
+    }
+    return fp4::gemv_nf4_entry("fp4_hip_gemv_lora_multi_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
+                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, B_stack, t, R, nullptr,
+                               nullptr, 0.0f, true, ids, n_adapters);
 }
 
 extern "C" int fp4_hip_gemv_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,

@@ -60,10 +60,24 @@ __device__ __forceinline__ float lora_delta(const void *B_row, const float *t_ro
     return d;
 }
 
+// Several adapters in one batch (the MULTI instantiations): B_stack holds n_adapters arrays T[M][R] one after another and ids[n]
+// names the adapter of activation row n.  -> the slice of row n's adapter, or nullptr where ids[n] is outside 0 .. n_adapters - 1
+// ("no adapter for this row": no address is formed from such an id).  The slice offset id * M * R is 64-bit.
+template <typename T>
+__device__ __forceinline__ const T *lora_stack_slice(const T *B_stack, const int *ids, int n_adapters, int n, int M, int R) {
+    const int id = ids[n];
+    if (uint32_t(id) >= uint32_t(n_adapters)) return nullptr;
+    return B_stack + int64_t(id) * M * R;
+}
+
 }  // namespace
 
 // the adapter checks shared by fp4_hip_gemv_lora_nf4 / fp4_hip_gemm_lora_nf4 (lora_nf4.hip): FP4_OK, or the status to return with
 // the message set - a null pointer or R <= 0 is an invalid argument, a rank or an alignment the kernels do not cover is unsupported
 int lora_check_adapter(const char *name, const void *lora_B, const float *t, int64_t R);
+
+// the same for the *_lora_multi_* entry points: n_adapters < 1 or a null ids is an invalid argument, then lora_check_adapter on the
+// stack's base (R % 8 == 0 keeps every slice of an aligned stack aligned)
+int lora_check_stack(const char *name, const void *B_stack, const int32_t *ids, int64_t n_adapters, const float *t, int64_t R);
 
 }  // namespace fp4

@@ -90,6 +90,18 @@ __device__ __forceinline__ void store_nf4_pair(uint16_t *out, const uint16_t *bi
     store_small_silu_mul<DT>(out, bias, residual, n, (int)(row >> 1), M >> 1, t, u);
 }
 
+// The same for the MULTI instantiations: activation row n's adapter is read from ids[n]; with one, store_nf4_pair<LORA = true> on
+// its slice of the stack, without one store_nf4_pair<LORA = false> - the bits of the single-adapter and of the plain fused kernel.
+template <int DT, typename Row>
+__device__ __forceinline__ void store_nf4_pair_multi(uint16_t *out, const uint16_t *bias, const uint16_t *residual, const uint16_t *B_stack,
+                                                     const int *ids, int n_adapters, const float *lora_t, int R, int n, Row row, int M,
+                                                     float t, float u) {
+    if (const uint16_t *slice = lora_stack_slice(B_stack, ids, n_adapters, n, M, R))
+        store_nf4_pair<DT, true>(out, bias, residual, slice, lora_t, R, n, row, M, t, u);
+    else
+        store_nf4_pair<DT, false>(out, bias, residual, nullptr, lora_t, R, n, row, M, t, u);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 
 struct Nf4GemmArgs {
@@ -103,6 +115,8 @@ struct Nf4GemmArgs {
     const void *lora_B = nullptr;  // LORA instantiations only
     const float *lora_t = nullptr;
     int R = 0;
+    const int32_t *lora_ids = nullptr;  // MULTI instantiations only: lora_B is then the stack
+    int n_adapters = 0;
 };
 
 // runtime dtype (validated: fp16 or bf16) -> template argument: f(std::integral_constant<int, FP4_DTYPE_F16 or FP4_DTYPE_BF16>{})

@@ -17,7 +17,8 @@
 //   * FP4:    gemv_fp4_bias, gemv_fp4_fused, gemm_small_fp4, gemm_small_fp4_fused, gemv_fp4_partial, quantize_fp4;
 //   * NF4 (bitsandbytes' second 4-bit code, same shapes and dispatch): dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4,
 //     qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4, gemv_nf4_fused, gemm_nf4_fused, quantize_nf4;
-//   * LoRA adapters beside an NF4 weight: lora_down, gemv_nf4_lora, gemm_nf4_lora;
+//   * LoRA adapters beside an NF4 weight: lora_down, gemv_nf4_lora, gemm_nf4_lora; several adapters per batch, chosen per row on
+//     the device: lora_down_multi, gemv_nf4_lora_multi, gemm_nf4_lora_multi;
 //   * double-quantised absmax: absmax_unnest, absmax_nest, gemv_nf4_nested, qlinear_nf4_nested;
 //   * tensor parallelism: comm_alloc / comm_open / comm_close / comm_free / comm_status / comm_clear_status, allreduce_oneshot;
 //   * hooks: code_table, set_kernel_variant, set_qlinear_gemm.
@@ -613,6 +614,74 @@ torch::Tensor gemm_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absm
     return nf4_fused_impl("gemm_nf4_lora", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, &lora_B, &t);
 }
 
+// Several adapters in one batch, selected per activation row on the device.  ids: int32, contiguous, on the activation's device, at
+// least `rows` elements (the first `rows` are used; it is never read on the host, so a captured step follows an in-place rewrite).
+void check_ids(const char *op, const torch::Tensor &ids, const torch::Tensor &x, int64_t rows) {
+    check_gpu_contiguous(ids, "ids", op);
+    TORCH_CHECK(ids.scalar_type() == torch::kInt32 && ids.device() == x.device() && ids.numel() >= rows, op, ": ids must be a contiguous int32 "
+                "tensor on the activation's device with at least one element per activation row (", rows, ")");
+}
+// lora_down_multi: t[b] = scale_stack[ids[b]] * (x[b] @ A_stack[ids[b]]^T), +0 where ids[b] names no adapter (fp4_hip_lora_down_multi;
+// A_stack [n, R, K] of x's dtype, scale_stack float32 [n, R]).
+torch::Tensor lora_down_multi(torch::Tensor x, torch::Tensor A_stack, torch::Tensor scale_stack, torch::Tensor ids) {
+    const char *op = "lora_down_multi";
+    check_gpu_contiguous(x, "x", op);
+    check_gpu_contiguous(A_stack, "A_stack", op);
+    check_gpu_contiguous(scale_stack, "scale_stack", op);
+    TORCH_CHECK(A_stack.dim() == 3 && A_stack.size(0) >= 1, op, ": A_stack must be [n_adapters, R, in_features] with at least one adapter");
+    const int64_t n = A_stack.size(0), R = A_stack.size(1), k = A_stack.size(2);
+    TORCH_CHECK(x.dim() >= 1 && k > 0 && x.size(-1) == k, op, ": last dim of the activation must be in_features = ", k);
+    TORCH_CHECK(A_stack.scalar_type() == x.scalar_type(), op, ": A_stack must have the activation's dtype");
+    TORCH_CHECK(scale_stack.scalar_type() == torch::kFloat32 && scale_stack.dim() == 2 && scale_stack.size(0) == n && scale_stack.size(1) == R,
+                op, ": scale_stack must be a float32 [", n, ", ", R, "] tensor");
+    TORCH_CHECK(A_stack.device() == x.device() && scale_stack.device() == x.device(), op, ": all tensors must be on one device");
+    const int64_t rows = x.numel() / k;
+    check_ids(op, ids, x, rows);
+    const int dt = to_fp4_dtype(x.scalar_type(), op);
+    torch::Tensor t = torch::empty({rows, R}, x.options().dtype(torch::kFloat32));
+    c10::DeviceGuard guard(x.device());
+    check_status(fp4_hip_lora_down_multi(x.data_ptr(), A_stack.data_ptr(), scale_stack.data_ptr<float>(), ids.data_ptr<int32_t>(),
+                                         t.data_ptr<float>(), rows, n, R, k, dt, current_stream(x)));
+    return t;
+}
+// gemv_nf4_lora_multi / gemm_nf4_lora_multi: gemv_nf4_lora / gemm_nf4_lora with B_stack [n, m, R] and the adapter of row b read from
+// ids[b] on the device; a row without one is the plain fused op's (fp4_hip_gemv_lora_multi_nf4 / fp4_hip_gemm_lora_multi_nf4).
+torch::Tensor nf4_lora_multi_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
+                                  int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
+                                  const c10::optional<torch::Tensor> &residual, int epilogue, const torch::Tensor &B_stack,
+                                  const torch::Tensor &ids, const torch::Tensor &t) {
+    WeightCall w = weight_op({op, gemv ? 1 : 128}, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue);
+    check_gpu_contiguous(B_stack, "B_stack", op);
+    check_gpu_contiguous(t, "t", op);
+    TORCH_CHECK(B_stack.dim() == 3 && B_stack.size(0) >= 1 && B_stack.size(1) == w.m && B_stack.scalar_type() == A.scalar_type() &&
+                    B_stack.device() == A.device(),
+                op, ": B_stack must be a [n_adapters, ", w.m, ", R] tensor of the activation dtype on the activation's device");
+    const int64_t n = B_stack.size(0), R = B_stack.size(2);
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.numel() == w.rows * R && t.device() == A.device(), op, ": t must hold ", w.rows * R,
+                " float32 elements (lora_down_multi's output) on the activation's device");
+    check_ids(op, ids, A, w.rows);
+    c10::DeviceGuard guard(A.device());
+    if (gemv)
+        check_status(fp4_hip_gemv_lora_multi_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr,
+                                                 B_stack.data_ptr(), ids.data_ptr<int32_t>(), n, t.data_ptr<float>(), R, w.out.data_ptr(), w.m,
+                                                 w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    else
+        check_status(fp4_hip_gemm_lora_multi_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr,
+                                                 B_stack.data_ptr(), ids.data_ptr<int32_t>(), n, t.data_ptr<float>(), R, w.out.data_ptr(),
+                                                 w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    return std::move(w.out);
+}
+torch::Tensor gemv_nf4_lora_multi(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
+                                  torch::Tensor B_stack, torch::Tensor ids, torch::Tensor t) {
+    return nf4_lora_multi_impl("gemv_nf4_lora_multi", true, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, B_stack, ids, t);
+}
+torch::Tensor gemm_nf4_lora_multi(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
+                                  torch::Tensor B_stack, torch::Tensor ids, torch::Tensor t) {
+    return nf4_lora_multi_impl("gemm_nf4_lora_multi", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, B_stack, ids, t);
+}
+
 // ---- nested (double-quantised) absmax: bitsandbytes' compress_statistics ------------------------------------------------------------
 // absmax_u8 uint8 [nb], nested_absmax float32 [ceil(nb / nested_blocksize)], code float32 [256], offset a Python float (passed to the
 // kernel by value: no device read of a host scalar, no sync).
@@ -823,6 +892,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm_nf4_lora", &gemm_nf4_lora,
           "gemm_nf4_fused for 1..64 rows plus the adapter term: (A, B, absmax, blocksize, Bshape, bias|None, residual|None, epilogue, "
           "lora_B [m, R], t float32 [rows, R])");
+    m.def("lora_down_multi", &lora_down_multi,
+          "LoRA down projection with the adapter chosen per row on the device: (x, A_stack [n, R, K], scale_stack float32 [n, R], ids int32 "
+          "[>= rows]) -> t float32 [rows, R]; +0 where ids[b] is outside 0..n-1");
+    m.def("gemv_nf4_lora_multi", &gemv_nf4_lora_multi,
+          "gemv_nf4_lora over a stack of adapters: (A, B, absmax, blocksize, [m, k] of the weight, bias|None, residual|None, epilogue, "
+          "B_stack [n, m, R], ids int32 [>= 1], t float32 [1, R]); an id outside 0..n-1 gives gemv_nf4_fused");
+    m.def("gemm_nf4_lora_multi", &gemm_nf4_lora_multi,
+          "gemm_nf4_lora over a stack of adapters, one id per activation row: (A, B, absmax, blocksize, [m, k] of the weight, bias|None, "
+          "residual|None, epilogue, B_stack [n, m, R], ids int32 [>= rows], t float32 [rows, R]); rows whose id is outside 0..n-1 are "
+          "gemm_nf4_fused's");
     m.def("absmax_unnest", &absmax_unnest,
           "expand double-quantised absmax: (absmax_u8, nested_absmax, nested_code [256], offset, nested_blocksize) -> float32 [nb]");
     m.def("absmax_nest", &absmax_nest,

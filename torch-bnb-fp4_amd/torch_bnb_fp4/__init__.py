@@ -34,7 +34,7 @@ from .functional import (
     quantize_nf4,
 )
 from .comm import OneShotAllReduce
-from .fused import FusedFP4Linear, FusedNF4Linear, LoRANF4Linear
+from .fused import AdapterSelection, FusedFP4Linear, FusedNF4Linear, LoRANF4Linear, MultiLoRANF4Linear
 from .graphs import GraphedStep
 from .linear import TorchFP4Linear
 from .nested import NestedNF4Linear, expand_nested
@@ -44,9 +44,11 @@ from .serialization import fp4_linear_from_bnb_state, fp4_linear_to_bnb_state, l
 from .surgery import (
     FusedGatedMLP,
     attach_lora,
+    attach_lora_adapters,
     check_if_name_contained_in_list,
     fuse_gated_mlps,
     load_lora_adapter,
+    load_lora_adapters,
     recursively_replace_with_fp4_linear,
     set_small_batch_fused,
     swap_linear_with_bnb_linear,
@@ -91,6 +93,10 @@ __all__ = [
     "LoRANF4Linear",
     "attach_lora",
     "load_lora_adapter",
+    "AdapterSelection",
+    "MultiLoRANF4Linear",
+    "attach_lora_adapters",
+    "load_lora_adapters",
     "NestedNF4Linear",
     "expand_nested",
 ]

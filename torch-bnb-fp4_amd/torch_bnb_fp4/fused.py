@@ -430,3 +430,221 @@ class LoRANF4Linear(FusedNF4Linear):
 
     def extra_repr(self) -> str:
         return super().extra_repr() + f", lora_rank={self.rank}"
+
+
+# ---- several adapters in one batch, selected per row on the device ------------------------------------------------------------------
+ADAPTER_SELECTION_CAPACITY = 64  # the rows the fused adapter ops cover; the torch fallback needs one id per row as well
+
+
+class AdapterSelection:
+    """Which adapter each sequence of the batch uses: one int32 device tensor of capacity 64, shared by all
+    :class:`MultiLoRANF4Linear` layers of a model and read by their kernels on the device.
+
+    ``set(ids)`` copies a host sequence or a tensor into it **in place** and records its length; ``-1`` (any value outside
+    ``0 .. n_adapters - 1``) selects the bare base model for that row.  ``ids`` is the view ``forward`` uses.  The tensor is never
+    reallocated after construction, so a step captured in a graph keeps reading it: ``set`` between two replays of the same length
+    changes which sequence uses which adapter without a new capture.  ``names`` (optional) are the adapters' names in stack order for
+    :meth:`set_by_name`.  The layers' torch fallback needs one id per row as well, so ``set`` with more ids than the capacity raises;
+    a model that is also run at more than 64 rows (all of them on the fallback) builds its selection with a larger ``capacity``."""
+
+    def __init__(self, device=None, names: Optional[Sequence[str]] = None, capacity: int = ADAPTER_SELECTION_CAPACITY):
+        self._buf = torch.full((int(capacity),), -1, dtype=torch.int32, device=device)
+        self._n = 0
+        self.names = list(names) if names is not None else []
+
+    @property
+    def capacity(self) -> int:
+        return int(self._buf.numel())
+
+    @property
+    def ids(self) -> torch.Tensor:
+        return self._buf[: self._n]
+
+    def __len__(self) -> int:
+        return self._n
+
+    def set(self, ids) -> "AdapterSelection":
+        src = ids if torch.is_tensor(ids) else torch.tensor(list(ids), dtype=torch.int32)
+        src = src.reshape(-1)
+        if src.numel() > self.capacity:
+            raise ValueError(f"AdapterSelection holds at most {self.capacity} ids (one per activation row), got {src.numel()}")
+        if src.is_floating_point() or src.dtype == torch.bool:
+            raise TypeError("adapter ids must be integers")
+        n = int(src.numel())
+        self._buf[:n].copy_(src)  # in place; converts to int32 and crosses devices as needed
+        self._n = n
+        return self
+
+    def set_by_name(self, names: Sequence[Optional[str]]) -> "AdapterSelection":
+        """``set`` with adapter names; ``None`` selects the base model only."""
+        index = {name: i for i, name in enumerate(self.names)}
+        unknown = [n for n in names if n is not None and n not in index]
+        if unknown:
+            raise KeyError(f"no adapter named {unknown[0]!r} (have {self.names})")
+        return self.set([-1 if n is None else index[n] for n in names])
+
+    def __repr__(self) -> str:
+        return f"AdapterSelection(len={self._n}, capacity={self.capacity}, names={self.names})"
+
+
+def pad_adapter_to(lora_A: torch.Tensor, lora_B: torch.Tensor, scale: torch.Tensor, rank: int):
+    """:func:`pad_adapter` up to a given rank (zero rows of A, zero columns of B, zero factors): exact for the same reason."""
+    pad = rank - lora_A.shape[0]
+    if pad < 0:
+        raise ValueError(f"cannot pad an adapter of rank {lora_A.shape[0]} to {rank}")
+    if pad:
+        lora_A = torch.cat([lora_A, lora_A.new_zeros(pad, lora_A.shape[1])], 0)
+        lora_B = torch.cat([lora_B, lora_B.new_zeros(lora_B.shape[0], pad)], 1)
+        scale = torch.cat([scale, scale.new_zeros(pad)], 0)
+    return lora_A.contiguous(), lora_B.contiguous(), scale.contiguous()
+
+
+class MultiLoRANF4Linear(FusedNF4Linear):
+    """A :class:`FusedNF4Linear` with a stack of LoRA adapters and one adapter id per activation row, read on the device from an
+    :class:`AdapterSelection`: row ``b`` of ``forward(x, residual=None)`` is what a :class:`LoRANF4Linear` holding adapter
+    ``selection.ids[b]`` gives for that row, and what the bare :class:`FusedNF4Linear` gives where the id names no adapter.
+
+    ``adapters`` is a list of ``(A [r_i, K], B [M, r_i], scale)`` as for :class:`LoRANF4Linear`.  They are zero-padded to one common
+    rank - the largest rank rounded up to a multiple of 8 - which is exact, and stacked: ``lora_A_stack [n, R, K]``,
+    ``lora_B_stack [n, M, R]``, ``lora_scale_stack [n, R]``.  The stacks follow the activation dtype, cast once per dtype.
+
+    One activation row runs ``lora_down_multi`` + ``gemv_nf4_lora_multi``, 2..64 rows ``lora_down_multi`` + ``gemm_nf4_lora_multi``:
+    one pass over the packed weight whatever the mix, and nothing about the selection is read on the host, so a captured step follows
+    ``selection.set``.  The fused route is taken where :func:`lora_fused_ahead` takes it for the common rank; a common rank above 256,
+    65+ rows, shapes the ops refuse and the other cells run the base through the parent's kernels and the adapters in torch in f32 as
+    a loop over the stack with row masks, added before one cast (capturable as well, no ``rows * R * K`` temporary)."""
+
+    def __init__(self, quant_data: QuantData, epilogue: int, adapters, selection: AdapterSelection):
+        super().__init__(quant_data, epilogue)
+        adapters = list(adapters)
+        if not adapters:
+            raise ValueError("MultiLoRANF4Linear needs at least one adapter")
+        if not isinstance(selection, AdapterSelection):
+            raise TypeError("selection must be an AdapterSelection")
+        dev, M, K = self.qweight.device, int(quant_data.M), self.in_features
+        triples = []
+        for A, B, scale in adapters:
+            if A.ndim != 2 or B.ndim != 2 or A.shape[1] != K or B.shape != (M, A.shape[0]):
+                raise ValueError(f"adapter shapes {tuple(A.shape)} / {tuple(B.shape)} do not fit a [{M}, {K}] weight (need A [r, K] and B [M, r])")
+            r = int(A.shape[0])
+            if not torch.is_tensor(scale):
+                scale = torch.full((r,), float(scale))
+            if scale.numel() != r:
+                raise ValueError(f"scale must be one factor or one per adapter row ({r}), got {scale.numel()}")
+            triples.append((A.detach().to(dev), B.detach().to(dev), scale.detach().reshape(-1).to(device=dev, dtype=torch.float32)))
+        self.ranks = [int(A.shape[0]) for A, _, _ in triples]
+        rank = max(self.ranks) + (-max(self.ranks) % LORA_RANK_MULTIPLE)
+        dtype = triples[0][0].dtype
+        padded = [pad_adapter_to(A.to(dtype), B.to(dtype), s, rank) for A, B, s in triples]
+        self.register_buffer("lora_A_stack", torch.stack([p[0] for p in padded]).contiguous(), persistent=True)
+        self.register_buffer("lora_B_stack", torch.stack([p[1] for p in padded]).contiguous(), persistent=True)
+        self.register_buffer("lora_scale_stack", torch.stack([p[2] for p in padded]).contiguous(), persistent=True)
+        self.selection = selection
+        self._lora_ok = rank <= LORA_MAX_RANK  # cleared as well when lora_down_multi reports a shape as not covered
+        self._cast = {}  # activation dtype -> (A_stack, B_stack) in that dtype
+
+    # -- constructors ------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_fused(cls, layer: FusedNF4Linear, adapters, selection: AdapterSelection) -> "MultiLoRANF4Linear":
+        """From a :class:`FusedNF4Linear` (shares its packed weight); every ``B`` covers the weight's own (interleaved) rows."""
+        cls._check_code(layer.quant_data)
+        return cls(layer.quant_data, layer.epilogue, adapters, selection)
+
+    @classmethod
+    def from_linear(cls, layer, adapters, selection: AdapterSelection) -> "MultiLoRANF4Linear":
+        return cls.from_fused(FusedNF4Linear.from_linear(layer), adapters, selection)
+
+    @classmethod
+    def gate_up_from_fused(cls, layer: FusedNF4Linear, adapter_pairs, selection: AdapterSelection) -> "MultiLoRANF4Linear":
+        """``adapter_pairs``: per adapter ``(gate_adapter, up_adapter)``, each ``(A, B, scaling)`` - stacked per adapter first."""
+        if layer.epilogue != EPILOGUE_SILU_MUL_PAIRS:
+            raise ValueError("gate_up_from_fused() needs a gate|up layer (FusedNF4Linear.gate_up)")
+        return cls.from_fused(layer, [stack_gate_up_adapters(g, u) for g, u in adapter_pairs], selection)
+
+    @classmethod
+    def from_packed(cls, *args, **kwargs):
+        raise TypeError("MultiLoRANF4Linear needs adapters: build a FusedNF4Linear.from_packed(...) and pass it to from_fused()")
+
+    @classmethod
+    def gate_up_from_packed(cls, *args, **kwargs):
+        raise TypeError("MultiLoRANF4Linear needs adapters: build a FusedNF4Linear.gate_up_from_packed(...) and pass it to gate_up_from_fused()")
+
+    @property
+    def n_adapters(self) -> int:
+        return int(self.lora_A_stack.shape[0])
+
+    @property
+    def rank(self) -> int:
+        """The common (padded) rank of the stack."""
+        return int(self.lora_A_stack.shape[1])
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)  # device moves only; the selection is shared and stays where it was built
+        for name in ("lora_A_stack", "lora_B_stack", "lora_scale_stack"):
+            self._buffers[name] = self._buffers[name].to(self.qweight.device)
+        self._cast = {}
+        return self
+
+    # -- forward -----------------------------------------------------------------------------------------------------
+    def _stacks(self, dtype: torch.dtype):
+        if self.lora_A_stack.dtype == dtype:
+            return self.lora_A_stack, self.lora_B_stack
+        cast = self._cast.get(dtype)
+        if cast is None or cast[0].device != self.lora_A_stack.device:
+            cast = self._cast[dtype] = (self.lora_A_stack.to(dtype), self.lora_B_stack.to(dtype))
+        return cast
+
+    def _adapters_in_torch(self, x: torch.Tensor, residual: Optional[torch.Tensor], ids: torch.Tensor) -> torch.Tensor:
+        A, B = self._stacks(x.dtype)
+        xf = x.float().reshape(-1, x.shape[-1])
+        delta = None
+        for a in range(self.n_adapters):  # row masks: nothing about ids is read on the host
+            mask = (ids == a).to(torch.float32).unsqueeze(1)
+            d = mask * ((xf @ A[a].float().t() * self.lora_scale_stack[a]) @ B[a].float().t())
+            delta = d if delta is None else delta + d
+        delta = delta.reshape(*x.shape[:-1], delta.shape[-1])
+        if self.epilogue == EPILOGUE_SILU_MUL_PAIRS:
+            y = (self.quant_data.forward(x).float() + delta).to(x.dtype)
+            y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
+        else:
+            y = (FusedNF4Linear.forward(self, x).float() + delta).to(x.dtype)
+        return y if residual is None else y + residual
+
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        qd = self.quant_data
+        K = x.shape[-1]
+        self._fix_compute_dtype(x)
+        rows = x.numel() // K if K else 0
+        ids = self.selection.ids
+        if ids.numel() != rows:
+            raise ValueError(f"the AdapterSelection holds {ids.numel()} ids, the batch has {rows} rows: call selection.set() with one id per row")
+        if self._lora_ok and rows >= 1 and K == self.in_features and x.dtype == qd.o_type and K % qd.blocksize == 0:
+            one = rows == 1 and x.ndim in (2, 3) and self._fused_ok
+            many = (2 <= rows <= 64 and self._small_ok and x.dtype in (torch.float16, torch.bfloat16) and qd.blocksize == 64
+                    and K % 64 == 0)
+            if (one or many) and lora_fused_ahead(rows, int(qd.M), K, self.rank):
+                A, B = self._stacks(x.dtype)
+                x = x.contiguous()
+                try:
+                    t = ext.lora_down_multi(x, A, self.lora_scale_stack, ids)
+                except RuntimeError as exc:
+                    if "not covered" not in str(exc):
+                        raise
+                    self._lora_ok = False
+                    return self._adapters_in_torch(x, residual, ids)
+                in_kernel = residual is not None and self._residual_in_kernel(rows, K)  # the parent's measured exception
+                try:
+                    op = ext.gemv_nf4_lora_multi if one else ext.gemm_nf4_lora_multi
+                    y = op(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual if in_kernel else None, self.epilogue, B, ids, t)
+                    return y if in_kernel or residual is None else y + residual
+                except RuntimeError as exc:  # a refusal clears the flag of the op that refused, whatever its wording
+                    if "not available" not in str(exc) and "not covered" not in str(exc):
+                        raise
+                    if one:
+                        self._fused_ok = False
+                    else:
+                        self._small_ok = False
+        return self._adapters_in_torch(x, residual, ids)
+
+    def extra_repr(self) -> str:
+        return super().extra_repr() + f", adapters={self.n_adapters}, lora_ranks={self.ranks}, common_rank={self.rank}"

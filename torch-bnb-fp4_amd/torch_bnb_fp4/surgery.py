@@ -310,3 +310,95 @@ def load_lora_adapter(model: nn.Module, directory: str) -> int:
     state = load_file(os.path.join(directory, "adapter_model.safetensors"))
     return attach_lora(model, state, int(cfg["r"]), float(cfg["lora_alpha"]), bool(cfg.get("use_rslora", False)),
                        cfg.get("target_modules"))
+
+
+def attach_lora_adapters(model: nn.Module, adapters, target_modules=None):
+    """Attach several saved LoRA adapters at once, selectable per sequence: ``adapters`` is an ordered mapping
+    ``name -> (adapter_state, r, lora_alpha, use_rslora)``.  Every NF4 layer that some adapter's keys name becomes a
+    :class:`~torch_bnb_fp4.fused.MultiLoRANF4Linear` holding all of them in the mapping's order (the gate|up layer of an NF4
+    :class:`FusedGatedMLP` takes each adapter's gate and up parts stacked); an adapter that does not cover a target module gets a
+    zero slice there.  Key mapping, ``target_modules`` and the rule that a used key without an NF4 home raises (leaving ``model`` as
+    it was) are :func:`attach_lora`'s.  Returns the one :class:`~torch_bnb_fp4.fused.AdapterSelection` all new layers share; it
+    carries the adapters' ``names`` (``selection.set_by_name([...])``) and ``n_layers``, the number of layers replaced."""
+    return _attach_adapter_stack(model, [(name, *spec, target_modules) for name, spec in adapters.items()])
+
+
+def _attach_adapter_stack(model: nn.Module, entries):
+    """attach_lora_adapters over ``(name, adapter_state, r, lora_alpha, use_rslora, target_modules)`` entries, each with its own
+    ``target_modules`` (load_lora_adapters reads them per adapter)."""
+    from .fused import AdapterSelection, FusedNF4Linear, LoRANF4Linear, MultiLoRANF4Linear, lora_scaling
+
+    names = [e[0] for e in entries]
+    if not names:
+        raise ValueError("attach_lora_adapters needs at least one adapter")
+    targets = {}  # resolved (id(parent), attribute) -> [parent, attribute, child, {adapter index: (A, B, scaling)}]
+    for index, (name, state, r, lora_alpha, use_rslora, wanted) in enumerate(entries):
+        scaling = lora_scaling(r, lora_alpha, use_rslora)
+        tensors = _adapter_tensors(state)
+        if wanted is not None:
+            wanted = [wanted] if isinstance(wanted, str) else list(wanted)
+            tensors = {p: t for p, t in tensors.items() if any(p == n or p.endswith("." + n) for n in wanted)}
+        for path, slot in tensors.items():
+            found = _resolve(model, path) or (_resolve(model, path[len("model."):]) if path.startswith("model.") else None)
+            if found is None:
+                raise KeyError(f"adapter {name!r}, key for {path!r}: the model has no such module")
+            parent, attr, child = found
+            A, B = slot["A"], slot["B"]
+            if A.shape[0] != r or B.shape[1] != r:
+                raise ValueError(f"adapter {name!r} for {path!r} has rank {A.shape[0]} / {B.shape[1]}, the config says r = {r}")
+            if isinstance(child, FusedGatedMLP):
+                if not isinstance(child.gate_up, FusedNF4Linear):
+                    raise ValueError(f"adapter key for {path!r}: the fused MLP there is not NF4")
+                if isinstance(child.gate_up, (LoRANF4Linear, MultiLoRANF4Linear)):
+                    raise ValueError("this fused MLP already carries an adapter")
+                which = "gate" if attr == child.projection_names[0] else "up"
+                entry = targets.setdefault((id(child), "gate_up"), [child, "gate_up", child.gate_up, {}])
+                entry[3].setdefault(index, {})[which] = (A, B, scaling)
+            elif (isinstance(child, TorchFP4Linear) and child.quant_data.nf4) or type(child) is FusedNF4Linear:
+                targets.setdefault((id(parent), attr), [parent, attr, child, {}])[3][index] = (A, B, scaling)
+            else:
+                raise ValueError(f"adapter key for {path!r}: {type(child).__name__} is not an NF4 layer (quantise the model with "
+                                 f"quant_type='nf4' first; adapters are attached once)")
+    if not targets:
+        raise ValueError("no adapter key names a target module")
+    device = next(iter(targets.values()))[2].quant_data.A.device
+    selection = AdapterSelection(device, names)
+    plan = []
+    for parent, attr, child, per_adapter in targets.values():
+        ref = next(iter(per_adapter.values()))
+        if attr == "gate_up" and isinstance(parent, FusedGatedMLP):
+            M, K = child.out_features, child.in_features
+            ref = next(iter(ref.values()))[0]
+            zero = (ref.new_zeros(1, K), ref.new_zeros(M, 1), 0.0)
+            pairs = [(per_adapter.get(i, {}).get("gate", zero), per_adapter.get(i, {}).get("up", zero)) for i in range(len(names))]
+            plan.append((parent, attr, MultiLoRANF4Linear.gate_up_from_fused(child, pairs, selection)))
+        else:
+            qd = child.quant_data
+            zero = (ref[0].new_zeros(1, int(qd.N)), ref[0].new_zeros(int(qd.M), 1), 0.0)
+            stack = [per_adapter.get(i, zero) for i in range(len(names))]
+            make = MultiLoRANF4Linear.from_linear if isinstance(child, TorchFP4Linear) else MultiLoRANF4Linear.from_fused
+            plan.append((parent, attr, make(child, stack, selection)))
+    for parent, attr, layer in plan:
+        parent._modules[attr] = layer
+    selection.n_layers = len(plan)
+    return selection
+
+
+def load_lora_adapters(model: nn.Module, directories):
+    """:func:`attach_lora_adapters` from directories in peft's layout (``adapter_model.safetensors`` + ``adapter_config.json``):
+    ``directories`` is an ordered mapping ``name -> directory`` or a sequence of directories (named by their last path component).
+    Each adapter's own ``target_modules`` restricts its keys."""
+    import json
+    import os
+
+    from safetensors.torch import load_file
+
+    if not hasattr(directories, "items"):
+        directories = {os.path.basename(os.path.normpath(d)): d for d in directories}
+    entries = []
+    for name, directory in directories.items():
+        with open(os.path.join(directory, "adapter_config.json")) as f:
+            cfg = json.load(f)
+        state = load_file(os.path.join(directory, "adapter_model.safetensors"))
+        entries.append((name, state, int(cfg["r"]), float(cfg["lora_alpha"]), bool(cfg.get("use_rslora", False)), cfg.get("target_modules")))
+    return _attach_adapter_stack(model, entries)
