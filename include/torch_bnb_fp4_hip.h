@@ -410,6 +410,19 @@ FP4_HIP_API int fp4_hip_gemv_lora_multi_nf4(const void *x, const uint8_t *packed
  *   (what every bitsandbytes file holds).  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, out untouched - the caller
  *   expands the statistics and runs the plain entry points.  Error codes otherwise as fp4_hip_gemv_fused_nf4; nested_blocksize <= 0
  *   or a null nested_absmax / code256: FP4_ERR_INVALID_ARGUMENT.
+ *
+ * fp4_hip_gemm_nested_nf4: fp4_hip_gemm_fused_nf4 reading the compressed statistics directly - the same rows (1..128), shapes,
+ *   forwarding rule (1..16 rows with K % 512 == 0: the small-batch kernel, else the wide one, two chunks above 64 rows) and
+ *   epilogues; `residual` may alias `out`.  The kernels fetch the block's code and its group's scale where they fetched the f32
+ *   scale and form it by the formula above; everything after it is unchanged, so the result EQUALS fp4_hip_gemm_fused_nf4 on the
+ *   expanded absmax bit for bit.  Covered: what fp4_hip_gemm_fused_nf4 covers (blocksize 64, K % 64 == 0, fp16 / bf16), with
+ *   nested_blocksize == 256.  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, out untouched - the caller expands the
+ *   statistics with fp4_hip_absmax_unnest and runs fp4_hip_gemm_fused_nf4.  nested_blocksize <= 0, a null operand with M, K > 0, an
+ *   unknown epilogue: FP4_ERR_INVALID_ARGUMENT.
+ *
+ * fp4_hip_gemv_lora_nested_nf4 / fp4_hip_gemm_lora_nested_nf4: fp4_hip_gemv_lora_nf4 / fp4_hip_gemm_lora_nf4 (one adapter, 1 row /
+ *   1..64 rows) reading the compressed statistics, bit for bit equal to them on the expanded absmax; coverage and error codes are
+ *   theirs, with the rules for the statistics above.
  */
 FP4_HIP_API int fp4_hip_absmax_unnest(const uint8_t *absmax_u8, const float *nested_absmax, const float *code256, float offset,
                                       int nested_blocksize, int64_t nb, float *out_f32, void *stream);
@@ -418,6 +431,17 @@ FP4_HIP_API int fp4_hip_absmax_nest(const float *absmax_f32, int64_t nb, float o
 FP4_HIP_API int fp4_hip_gemv_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
                                         const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
                                         void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
+FP4_HIP_API int fp4_hip_gemm_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                        const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
+                                        void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
+FP4_HIP_API int fp4_hip_gemv_lora_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                             const float *code256, float offset, int nested_blocksize, const void *bias,
+                                             const void *residual, const void *lora_B, const float *t, int64_t R, void *out, int64_t M,
+                                             int64_t K, int blocksize, int dtype, int epilogue, void *stream);
+FP4_HIP_API int fp4_hip_gemm_lora_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                             const float *code256, float offset, int nested_blocksize, const void *bias,
+                                             const void *residual, const void *lora_B, const float *t, int64_t R, void *out, int64_t B,
+                                             int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
 
 /*
  * Tuning hook for benchmarks/sweeps: selects a kernel geometry by name

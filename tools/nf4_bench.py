@@ -47,7 +47,12 @@ as for --fused.
 protocol of --fused.  (1) fp4_hip_gemv_nested_nf4 on the compressed statistics against fp4_hip_gemv_fused_nf4 on their expansion
 (level / ahead / behind beyond both replay-to-replay ranges).  (2) The plain fp4_hip_gemv_nf4 of this tree's library and, with
 --baseline-lib, of the parent commit's, side by side; "within" as for --fused.  (3) absmax_unnest alone, and qlinear_nf4_nested
-against qlinear_nf4 at 8 and 64 rows.  (4) Device bytes of one layer's statistics, resident and expanded.
+against qlinear_nf4 at 8 and 64 rows.  (4) Device bytes of one layer's statistics, resident and expanded.  (5) 2 / 8 / 16 / 32 / 64 rows:
+gemm_nf4_nested against the parent commit's path for the same resident layer (qlinear_nf4_nested), both through the torch ops; and
+fp4_hip_gemm_nested_nf4 against fp4_hip_gemm_fused_nf4 on the expanded statistics (this tree's library and the baseline's).  (6) A
+rank-16 adapter at 1 / 8 / 32 rows: lora_down + gemv_nf4_lora_nested / gemm_nf4_lora_nested against the parent's resident path plus the
+adapter as torch ops; and the C entry points against lora_down + the un-nested LoRA forms on expanded statistics.  A cell is "ahead"
+only beyond both replay-to-replay ranges together.  --nested-rows / --nested-lora-rows replace the row lists.
 """
 import argparse
 import ctypes
@@ -314,10 +319,17 @@ def nested(args):
 
     def bind(l):
         l.fp4_hip_gemv_nf4.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+        l.fp4_hip_gemm_fused_nf4.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
+        l.fp4_hip_lora_down.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, vp]
+        l.fp4_hip_gemv_lora_nf4.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i32, i32, i32, vp]
+        l.fp4_hip_gemm_lora_nf4.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i64, i64, i32, i32, i32, vp]
         return l
 
     L.fp4_hip_gemv_fused_nf4.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp]
     L.fp4_hip_gemv_nested_nf4.argtypes = [vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, i64, i64, i32, i32, i32, vp]
+    L.fp4_hip_gemm_nested_nf4.argtypes = [vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
+    L.fp4_hip_gemv_lora_nested_nf4.argtypes = [vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, i64, vp, i64, i64, i32, i32, i32, vp]
+    L.fp4_hip_gemm_lora_nested_nf4.argtypes = [vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, i64, vp, i64, i64, i64, i32, i32, i32, vp]
     libs = {"this_tree": bind(L)}
     if args.baseline_lib:
         libs["baseline"] = bind(ctypes.CDLL(os.path.abspath(args.baseline_lib)))
@@ -376,6 +388,78 @@ def nested(args):
             a = timed(lambda: pkg.ext.qlinear_nf4_nested(xb, packed, q, nabs, code, offset, G, M, K, BS, None))
             b = timed(lambda: pkg.ext.qlinear_nf4(xb, packed, expanded, M, K, BS))
             cell[f"qlinear_rows{rows}"] = {"qlinear_nf4_nested": a, "qlinear_nf4": b, "delta_us": round(a["us"] - b["us"], 2)}
+        # (5) 2..64 rows: gemm_nf4_nested against the parent commit's path for the same resident layer (qlinear_nf4_nested: expand
+        # into a temporary, dequant + GEMM), both as the layer issues them; then the C entry point against fp4_hip_gemm_fused_nf4 on
+        # the expanded statistics, through this tree's library and the baseline's
+        B_t = packed.view(-1, 1).t()
+        verdict = lambda new, old: ("level" if abs(old["us"] - new["us"]) <= rng_of(new) + rng_of(old)  # noqa: E731
+                                    else ("ahead" if old["us"] > new["us"] else "behind"))
+        batched = []
+        for rows in args.nested_rows:
+            xb = torch.randn(rows, K, device=dev).to(dtype)
+            yb, yb2 = torch.empty(rows, M, dtype=dtype, device=dev), torch.empty(rows, M, dtype=dtype, device=dev)
+            new = lambda: pkg.ext.gemm_nf4_nested(xb, B_t, q, nabs, code, offset, G, BS, [M, K], None, None, 0)  # noqa: E731
+            old = lambda: pkg.ext.qlinear_nf4_nested(xb, packed, q, nabs, code, offset, G, M, K, BS, None)  # noqa: E731
+            same = bool(torch.equal(new(), pkg.ext.gemm_nf4_fused(xb, B_t, expanded, BS, [M, K], None, None, 0)))
+            tn, to = timed(new), timed(old)
+            c = {"rows": rows, "bit_identical_to_gemm_nf4_fused_on_expanded": same, "gemm_nf4_nested": tn, "parent_resident_path": to,
+                 "saved_us": round(to["us"] - tn["us"], 2), "speedup": round(to["us"] / tn["us"], 3),
+                 "spread_us": round(rng_of(tn) + rng_of(to), 2), "verdict": verdict(tn, to)}
+            c["c_abi_gemm_nested_nf4"] = timed(lambda: check(L, L.fp4_hip_gemm_nested_nf4(p_(xb), p_(packed), p_(q), p_(nabs), p_(code), offset, G,
+                                                                                          None, None, p_(yb), rows, M, K, BS, dt, 0, s())))
+            for tag, l in libs.items():
+                c[f"c_abi_gemm_fused_nf4_on_expanded_{tag}"] = timed(lambda: check(l, l.fp4_hip_gemm_fused_nf4(
+                    p_(xb), p_(packed), p_(expanded), None, None, p_(yb2), rows, M, K, BS, dt, 0, s())))
+            ref = c["c_abi_gemm_fused_nf4_on_expanded_" + ("baseline" if "baseline" in libs else "this_tree")]
+            c["nested_vs_fused_on_expanded"] = verdict(c["c_abi_gemm_nested_nf4"], ref)
+            batched.append(c)
+        cell["batched"] = batched
+        # (6) one rank-16 adapter: lora_down + gemv_nf4_lora_nested / gemm_nf4_lora_nested against the parent's resident path plus the
+        # adapter as torch ops in the activation dtype; then the C entry points against the un-nested LoRA forms on expanded statistics
+        R = 16
+        A = (torch.randn(R, K, device=dev) / K ** 0.5).to(dtype)
+        lB = (torch.randn(M, R, device=dev) * 0.05).to(dtype)
+        sc = torch.full((R,), 2.0, device=dev)
+        At, lBt, s_t = A.t().contiguous(), lB.t().contiguous(), sc.to(dtype)
+        with_adapter = []
+        for rows in args.nested_lora_rows:
+            xb = torch.randn(rows, K, device=dev).to(dtype)
+            yb, yb2, tb = torch.empty(rows, M, dtype=dtype, device=dev), torch.empty(rows, M, dtype=dtype, device=dev), torch.empty(rows, R, device=dev)
+            if rows == 1:
+                new = lambda: pkg.ext.gemv_nf4_lora_nested(xb, B_t, q, nabs, code, offset, G, BS, [M, K], None, None, 0, lB,  # noqa: E731
+                                                           pkg.ext.lora_down(xb, A, sc))
+                old = lambda: pkg.ext.gemv_nf4_nested(xb, B_t, q, nabs, code, offset, G, BS, [M, K], None, None, 0) + ((xb @ At) * s_t) @ lBt  # noqa: E731
+                ref_op = lambda: pkg.ext.gemv_nf4_lora(xb, B_t, expanded, BS, [M, K], None, None, 0, lB, pkg.ext.lora_down(xb, A, sc))  # noqa: E731
+                c_new = lambda l: (check(l, l.fp4_hip_lora_down(p_(xb), p_(A), p_(sc), p_(tb), rows, R, K, dt, s())),  # noqa: E731
+                                   check(l, l.fp4_hip_gemv_lora_nested_nf4(p_(xb), p_(packed), p_(q), p_(nabs), p_(code), offset, G, None, None, p_(lB),
+                                                                           p_(tb), R, p_(yb), M, K, BS, dt, 0, s())))
+                c_ref = lambda l: (check(l, l.fp4_hip_lora_down(p_(xb), p_(A), p_(sc), p_(tb), rows, R, K, dt, s())),  # noqa: E731
+                                   check(l, l.fp4_hip_gemv_lora_nf4(p_(xb), p_(packed), p_(expanded), None, None, p_(lB), p_(tb), R, p_(yb2), M, K, BS,
+                                                                    dt, 0, s())))
+            else:
+                new = lambda: pkg.ext.gemm_nf4_lora_nested(xb, B_t, q, nabs, code, offset, G, BS, [M, K], None, None, 0, lB,  # noqa: E731
+                                                           pkg.ext.lora_down(xb, A, sc))
+                old = lambda: pkg.ext.qlinear_nf4_nested(xb, packed, q, nabs, code, offset, G, M, K, BS, None) + ((xb @ At) * s_t) @ lBt  # noqa: E731
+                ref_op = lambda: pkg.ext.gemm_nf4_lora(xb, B_t, expanded, BS, [M, K], None, None, 0, lB, pkg.ext.lora_down(xb, A, sc))  # noqa: E731
+                c_new = lambda l: (check(l, l.fp4_hip_lora_down(p_(xb), p_(A), p_(sc), p_(tb), rows, R, K, dt, s())),  # noqa: E731
+                                   check(l, l.fp4_hip_gemm_lora_nested_nf4(p_(xb), p_(packed), p_(q), p_(nabs), p_(code), offset, G, None, None, p_(lB),
+                                                                           p_(tb), R, p_(yb), rows, M, K, BS, dt, 0, s())))
+                c_ref = lambda l: (check(l, l.fp4_hip_lora_down(p_(xb), p_(A), p_(sc), p_(tb), rows, R, K, dt, s())),  # noqa: E731
+                                   check(l, l.fp4_hip_gemm_lora_nf4(p_(xb), p_(packed), p_(expanded), None, None, p_(lB), p_(tb), R, p_(yb2), rows, M, K,
+                                                                    BS, dt, 0, s())))
+            same = bool(torch.equal(new(), ref_op()))
+            tn, to = timed(new), timed(old)
+            c = {"rows": rows, "rank": R, "bit_identical_to_the_lora_op_on_expanded": same, "lora_down_plus_nested_lora_op": tn,
+                 "parent_resident_path_plus_torch_adapter": to, "saved_us": round(to["us"] - tn["us"], 2), "speedup": round(to["us"] / tn["us"], 3),
+                 "spread_us": round(rng_of(tn) + rng_of(to), 2), "verdict": verdict(tn, to),
+                 "lora_fused_ahead": bool(pkg.fused.lora_fused_ahead(rows, M, K, R))}
+            c["c_abi_nested_pair"] = timed(lambda: c_new(L))
+            for tag, l in libs.items():
+                c[f"c_abi_lora_pair_on_expanded_{tag}"] = timed(lambda: c_ref(l))
+            ref = c["c_abi_lora_pair_on_expanded_" + ("baseline" if "baseline" in libs else "this_tree")]
+            c["nested_vs_lora_on_expanded"] = verdict(c["c_abi_nested_pair"], ref)
+            with_adapter.append(c)
+        cell["rank16_adapter"] = with_adapter
         resident = q.numel() + 4 * nabs.numel() + 4 * code.numel()
         cell["statistics_bytes"] = {"resident": resident, "expanded": 4 * expanded.numel(), "packed_weight": packed.numel(),
                                     "bits_per_weight_resident": round(8 * resident / n, 4), "bits_per_weight_expanded": round(32 * expanded.numel() / n, 4)}
@@ -385,7 +469,12 @@ def nested(args):
                       "launches_per_graph": args.launches, "reps": args.reps,
                       "baseline_lib": "the parent commit's library, same run" if args.baseline_lib else "not measured",
                       "plain_gemv_all_within_margin": (all(c["plain_gemv_nf4"]["within_margin"] for c in cells) if args.baseline_lib else None),
-                      "all_bit_identical": all(c["bit_identical"] for c in cells), "cells": cells}))
+                      "all_bit_identical": all(c["bit_identical"] and all(b["bit_identical_to_gemm_nf4_fused_on_expanded"] for b in c["batched"])
+                                               and all(a["bit_identical_to_the_lora_op_on_expanded"] for a in c["rank16_adapter"]) for c in cells),
+                      "batched_cells_ahead_of_the_parent_resident_path": sum(b["verdict"] == "ahead" for c in cells for b in c["batched"]),
+                      "batched_cells_total": sum(len(c["batched"]) for c in cells),
+                      "adapter_cells_ahead_of_the_parent_resident_path": sum(a["verdict"] == "ahead" for c in cells for a in c["rank16_adapter"]),
+                      "adapter_cells_total": sum(len(c["rank16_adapter"]) for c in cells), "cells": cells}))
 
 
 def lora(args):
@@ -559,6 +648,8 @@ def main():
     ap.add_argument("--multi-lora", action="store_true",
                     help="several adapters per batch, fused multi-adapter ops against rows grouped by adapter (profiles/nf4_multi_lora.json)")
     ap.add_argument("--nested", action="store_true", help="double-quantised absmax: the nested GEMV, unnest and qlinear_nf4_nested (profiles/nf4_nested.json)")
+    ap.add_argument("--nested-rows", type=ints, default=[2, 8, 16, 32, 64], help="--nested: row counts of the batched cells, comma-separated")
+    ap.add_argument("--nested-lora-rows", type=ints, default=[1, 8, 32], help="--nested: row counts of the rank-16 adapter cells, comma-separated")
     args = ap.parse_args()
     if args.nested:
         return nested(args)

@@ -22,7 +22,13 @@
 // Several adapters per batch (fp4_hip_gemm_lora_multi_nf4): the MULTI instantiations (always LORA) take a stack of B arrays and read
 // the adapter of activation row n from lora_ids[n] on the device, once per (n) a thread owns; a row without an adapter is stored as
 // the FUSED instantiation stores it.
+//
+// Nested (double-quantised) absmax (fp4_hip_gemm_nested_nf4 / fp4_hip_gemm_lora_nested_nf4): the NESTED instantiations (FUSED, or
+// FUSED + LORA) fetch the block's uint8 code and its group's f32 scale where the f32 scale was fetched, one pass ahead, and write
+// unnest_scale(table[code], group, offset) (nested_absmax.h: a multiply, then an add) into the LDS image.  Everything that reads the
+// image is unchanged, so the result equals the FUSED / LORA instantiation on the expanded absmax bit for bit.
 #include "launchers.h"
+#include "nested_absmax.h"
 #include "nf4_mfma.h"
 
 namespace fp4 {
@@ -38,14 +44,18 @@ namespace {
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
 // MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R] and lora_ids[n] names activation row n's adapter; a row
 // whose id names none takes the FUSED store as it is (the add is skipped, not done with zero).
-template <int DT, int NBW, int XS, bool FUSED, bool LORA = false, bool MULTI = false>
+// NESTED = true (with FUSED, without MULTI): `absmax` points at uint8 codes, one per block; the scale of block i is
+// unnest_scale(nested_code[code[i]], nested_absmax[i >> 8], nested_offset).
+template <int DT, int NBW, int XS, bool FUSED, bool LORA = false, bool MULTI = false, bool NESTED = false>
 __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
                                                             uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode,
                                                             const uint16_t *lora_B, const float *lora_t, int R, const int *lora_ids,
-                                                            int n_adapters) {
+                                                            int n_adapters,  // new arguments last
+                                                            const float *nested_absmax, const float *nested_code, float nested_offset) {
     static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
     static_assert(!MULTI || LORA, "the adapter stack comes with the adapter term");
+    static_assert(!NESTED || (FUSED && !MULTI), "nested absmax comes with the fused epilogues and without the adapter stack");
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kXStride = 128 * NBW + 16;
     constexpr int kWImageBytes = 8 * 16 * kStageStride;
@@ -56,6 +66,7 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     // the cross-wave partial sums reuse the images' storage after the K loop; the code table has storage of its own
     __shared__ __attribute__((aligned(16))) uint8_t s_raw[kImageBytes > kPartBytes ? kImageBytes : kPartBytes];
     __shared__ __attribute__((aligned(16))) u32x2 s_code[256];
+    __shared__ float s_ncode[NESTED ? 256 : 1];
     uint8_t *s_w = s_raw;
     uint8_t *s_x = s_raw + kWImageBytes;
     float (*s_part)[256] = reinterpret_cast<float (*)[256]>(s_raw);
@@ -76,6 +87,7 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     u32x4 xstage[kXUnits];
     u32x4 wstage[kInstr];
     float amstage;
+    [[maybe_unused]] uint32_t aqstage;  // NESTED: the block's code; amstage holds its group's scale
     auto issue_staged = [&](int pass) {  // x first (L2), then the weight stream (HBM), then the scales; all branch-free
         const int b0 = (pass * 8 + wave) * NBW;
         if constexpr (XS > 0) {
@@ -93,12 +105,21 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
             wstage[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(W) + ((row * K) >> 5) + 2 * b0 + (lane % kLanesPerRow));
         }
         const int64_t row = row0 + srow < M ? row0 + srow : M - 1;
-        amstage = absmax[row * nblk + b0 + sj0];
+        if constexpr (NESTED) {
+            const int64_t blk = row * nblk + b0 + sj0;
+            aqstage = reinterpret_cast<const uint8_t *>(absmax)[blk];
+            amstage = nested_absmax[blk >> kNestedGemvShift];
+        } else {
+            amstage = absmax[row * nblk + b0 + sj0];
+        }
     };
     issue_staged(0);
 
     // the byte table, once per workgroup, while the first pass's loads fly
     fill_code_table<DT>(s_code, tid);
+    if constexpr (NESTED) {
+        if (tid < 256) s_ncode[tid] = nested_code[tid];
+    }
     __syncthreads();
     const uint8_t *code = reinterpret_cast<const uint8_t *>(s_code);
 
@@ -121,7 +142,10 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
             const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
             if (rr < 16) *reinterpret_cast<u32x4 *>(img + rr * kStageStride + 16 * (lane % kLanesPerRow)) = wstage[i];
         }
-        reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW)[sj0] = amstage;
+        if constexpr (NESTED)
+            reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW)[sj0] = unnest_scale(s_ncode[aqstage], amstage, nested_offset);
+        else
+            reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW)[sj0] = amstage;
         if constexpr (XS > 0) {
             uint8_t *ximg = s_x + wave * XS * kXStride;
 #pragma unroll
@@ -214,15 +238,16 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     }
 }
 
-template <int DT, int NBW, int XS, bool FUSED, bool LORA, bool MULTI>
+template <int DT, int NBW, int XS, bool FUSED, bool LORA, bool MULTI, bool NESTED>
 void launch_nf4_mfma(const Nf4GemmArgs &a) {
-    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED, LORA, MULTI>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
+    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED, LORA, MULTI, NESTED>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
                        reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
                        reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
-                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R, a.lora_ids, a.n_adapters);
+                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R, a.lora_ids, a.n_adapters, a.nested_absmax, a.nested_code,
+                       a.nested_offset);
 }
 
-template <int DT, bool FUSED, bool LORA = false, bool MULTI = false>
+template <int DT, bool FUSED, bool LORA = false, bool MULTI = false, bool NESTED = false>
 void dispatch_nf4_mfma(const Nf4GemmArgs &a) {
     const int B = a.B, M = a.M, K = a.K;
     const int units = K / 512;  // quant blocks per wave over the whole K
@@ -230,12 +255,12 @@ void dispatch_nf4_mfma(const Nf4GemmArgs &a) {
     // the FP4 kernel's rules: at most 4 blocks per wave and pass; x staged per wave in LDS always for <= 4 rows, for 5..8 rows only
     // while the grid is a single round anyway (the larger image leaves fewer workgroups per CU)
     if (units % 4 == 0) {
-        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED, LORA, MULTI>(a);
-        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED, LORA, MULTI>(a);
-        return launch_nf4_mfma<DT, 4, 0, FUSED, LORA, MULTI>(a);
+        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED, LORA, MULTI, NESTED>(a);
+        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED, LORA, MULTI, NESTED>(a);
+        return launch_nf4_mfma<DT, 4, 0, FUSED, LORA, MULTI, NESTED>(a);
     }
-    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED, LORA, MULTI>(a);
-    return launch_nf4_mfma<DT, 1, 0, FUSED, LORA, MULTI>(a);
+    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED, LORA, MULTI, NESTED>(a);
+    return launch_nf4_mfma<DT, 1, 0, FUSED, LORA, MULTI, NESTED>(a);
 }
 
 }  // namespace
@@ -262,6 +287,19 @@ void gemm_small_nf4_lora_multi_launch(int dtype, const void *x, const uint8_t *W
                                       int M, int K, int mode, hipStream_t stream) {
     const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, B_stack, lora_t, R, ids, n_adapters};
     with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true, true, true>(a); });
+}
+
+// the two forms above reading double-quantised absmax, for fp4_hip_gemm_nested_nf4 / fp4_hip_gemm_lora_nested_nf4 (gemm_wide_nf4.hip),
+// which have validated the statistics as well; lora_B == nullptr: no adapter term
+void gemm_small_nf4_nested_launch(int dtype, const void *x, const uint8_t *W, const uint8_t *absmax_u8, const float *nested_absmax,
+                                  const float *nested_code, float nested_offset, const void *bias, const void *residual, const void *lora_B,
+                                  const float *lora_t, int R, void *out, int B, int M, int K, int mode, hipStream_t stream) {
+    Nf4GemmArgs a{x, W, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, B, M, K, mode, stream, lora_B, lora_t, R};
+    a.nested_absmax = nested_absmax, a.nested_code = nested_code, a.nested_offset = nested_offset;
+    with_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        lora_B ? dispatch_nf4_mfma<DT, true, true, false, true>(a) : dispatch_nf4_mfma<DT, true, false, false, true>(a);
+    });
 }
 
 }  // namespace fp4

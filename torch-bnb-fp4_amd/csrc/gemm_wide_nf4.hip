@@ -34,9 +34,15 @@
 // Several adapters per batch (fp4_hip_gemm_lora_multi_nf4, 1..64 rows): the MULTI instantiations (always LORA) take a stack of B
 // arrays and read the adapter of activation row n from lora_ids[n] on the device, once per (n) of the store loop; a row without an
 // adapter is stored as the FUSED instantiation stores it.
+//
+// Nested (double-quantised) absmax (fp4_hip_gemm_nested_nf4 / fp4_hip_gemm_lora_nested_nf4): the NESTED instantiations (FUSED, or
+// FUSED + LORA) fetch the block's uint8 code and its group's f32 scale where the f32 scale was fetched, one pass ahead, and write
+// unnest_scale(table[code], group, offset) (nested_absmax.h: a multiply, then an add) into the LDS image.  Everything that reads the
+// image is unchanged, so the result equals the FUSED / LORA instantiation on the expanded absmax bit for bit.
 #include <atomic>
 
 #include "launchers.h"
+#include "nested_absmax.h"
 #include "nf4_mfma.h"
 
 namespace fp4 {
@@ -51,14 +57,18 @@ namespace {
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
 // MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R] and lora_ids[n] names activation row n's adapter; a row
 // whose id names none takes the FUSED store as it is (the add is skipped, not done with zero).
-template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA = false, bool MULTI = false>
+// NESTED = true (with FUSED, without MULTI): `absmax` points at uint8 codes, one per block; the scale of block i is
+// unnest_scale(nested_code[code[i]], nested_absmax[i >> 8], nested_offset).
+template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA = false, bool MULTI = false, bool NESTED = false>
 __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                             const float *__restrict__ absmax, const uint16_t *__restrict__ bias,
                                                             uint16_t *out, int B, int M, int K, const uint16_t *residual, int mode,
                                                             const uint16_t *lora_B, const float *lora_t, int R, const int *lora_ids,
-                                                            int n_adapters) {
+                                                            int n_adapters,  // new arguments last
+                                                            const float *nested_absmax, const float *nested_code, float nested_offset) {
     static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
     static_assert(!MULTI || LORA, "the adapter stack comes with the adapter term");
+    static_assert(!NESTED || (FUSED && !MULTI), "nested absmax comes with the fused epilogues and without the adapter stack");
     constexpr int kRows = 16 * RT;
     constexpr int kStageStride = 32 * NBW + 32;
     constexpr int kImageBytes = 8 * kRows * kStageStride;
@@ -67,6 +77,7 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
     // the cross-wave partial sums reuse the images' storage after the K loop; the code table has storage of its own
     __shared__ __attribute__((aligned(16))) uint8_t s_raw[kImageBytes > kPartBytes ? kImageBytes : kPartBytes];
     __shared__ __attribute__((aligned(16))) u32x2 s_code[256];
+    __shared__ float s_ncode[NESTED ? 256 : 1];
     float (*s_part)[kTiles * 256] = reinterpret_cast<float (*)[kTiles * 256]>(s_raw);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -82,6 +93,7 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
     constexpr int kScaleInstr = (kRows * NBW + 63) / 64;  // with fewer than 64 scales the upper lanes repeat rows: same address, same value
     u32x4 wstage[kInstr];
     float amstage[kScaleInstr];
+    [[maybe_unused]] uint32_t aqstage[NESTED ? kScaleInstr : 1];  // NESTED: the block's code; amstage holds its group's scale
     auto issue_staged = [&](int pass) {  // the weight stream (HBM), then the scales; branch-free, a unit past the end is clamped
         const int u = pass * 8 + wave;
         const int b0 = (u < nunits ? u : nunits - 1) * NBW;
@@ -95,7 +107,13 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
         for (int i = 0; i < kScaleInstr; ++i) {
             const int idx = i * 64 + lane, rr = (idx / NBW) % kRows;
             const int64_t row = row0 + rr < M ? row0 + rr : int64_t(M) - 1;
-            amstage[i] = absmax[row * nblk + b0 + idx % NBW];
+            if constexpr (NESTED) {
+                const int64_t blk = row * nblk + b0 + idx % NBW;
+                aqstage[i] = reinterpret_cast<const uint8_t *>(absmax)[blk];
+                amstage[i] = nested_absmax[blk >> kNestedGemvShift];
+            } else {
+                amstage[i] = absmax[row * nblk + b0 + idx % NBW];
+            }
         }
     };
     // the x fragments of one block: rows past B are clamped (computed, never stored)
@@ -117,6 +135,9 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
 
     // the byte table, once per workgroup, while the first pass's loads fly
     fill_code_table<DT>(s_code, tid);
+    if constexpr (NESTED) {
+        if (tid < 256) s_ncode[tid] = nested_code[tid];
+    }
     __syncthreads();
     const uint8_t *code = reinterpret_cast<const uint8_t *>(s_code);
     uint8_t *img = s_raw + wave * kRows * kStageStride;
@@ -142,7 +163,10 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
 #pragma unroll
         for (int i = 0; i < kScaleInstr; ++i) {
             const int idx = i * 64 + lane, rr = (idx / NBW) % kRows;
-            reinterpret_cast<float *>(img + rr * kStageStride + 32 * NBW)[idx % NBW] = amstage[i];
+            if constexpr (NESTED)
+                reinterpret_cast<float *>(img + rr * kStageStride + 32 * NBW)[idx % NBW] = unnest_scale(s_ncode[aqstage[i]], amstage[i], nested_offset);
+            else
+                reinterpret_cast<float *>(img + rr * kStageStride + 32 * NBW)[idx % NBW] = amstage[i];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -245,15 +269,16 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
 
 std::atomic<int> g_wide_nf4_variant{-1};  // sweep hook: 1 / 2 = 16 / 32 weight rows per workgroup, anything else = the heuristic
 
-template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA, bool MULTI>
+template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA, bool MULTI, bool NESTED>
 void launch_wide_nf4(const Nf4GemmArgs &a) {
-    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED, LORA, MULTI>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512),
-                       0, a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
-                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
-                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R, a.lora_ids, a.n_adapters);
+    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED, LORA, MULTI, NESTED>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))),
+                       dim3(512), 0, a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax,
+                       reinterpret_cast<const uint16_t *>(a.bias), reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K,
+                       reinterpret_cast<const uint16_t *>(a.residual), a.mode, reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R,
+                       a.lora_ids, a.n_adapters, a.nested_absmax, a.nested_code, a.nested_offset);
 }
 
-template <int DT, int NT, bool FUSED, bool LORA, bool MULTI>
+template <int DT, int NT, bool FUSED, bool LORA, bool MULTI, bool NESTED>
 void dispatch_wide_nf4_nt(const Nf4GemmArgs &a) {
     const int M = a.M, K = a.K;
     // 32 weight rows per workgroup halve the x traffic from L2, the kernel's largest stream: taken once that still fills three
@@ -262,21 +287,21 @@ void dispatch_wide_nf4_nt(const Nf4GemmArgs &a) {
     const bool rt2 = v == 2 || (v != 1 && M >= 24 * device_cu_count());
     const bool nbw4 = K % 256 == 0;
     if (rt2) {
-        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED, LORA, MULTI>(a);
-        return launch_wide_nf4<DT, NT, 2, 1, FUSED, LORA, MULTI>(a);
+        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED, LORA, MULTI, NESTED>(a);
+        return launch_wide_nf4<DT, NT, 2, 1, FUSED, LORA, MULTI, NESTED>(a);
     }
-    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED, LORA, MULTI>(a);
-    return launch_wide_nf4<DT, NT, 1, 1, FUSED, LORA, MULTI>(a);
+    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED, LORA, MULTI, NESTED>(a);
+    return launch_wide_nf4<DT, NT, 1, 1, FUSED, LORA, MULTI, NESTED>(a);
 }
 
 // one launch: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
-template <int DT, bool FUSED, bool LORA = false, bool MULTI = false>
+template <int DT, bool FUSED, bool LORA = false, bool MULTI = false, bool NESTED = false>
 void dispatch_wide_nf4(const Nf4GemmArgs &a) {
     switch ((a.B + 15) / 16) {
-        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED, LORA, MULTI>(a);
-        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED, LORA, MULTI>(a);
-        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED, LORA, MULTI>(a);
-        default: return dispatch_wide_nf4_nt<DT, 4, FUSED, LORA, MULTI>(a);
+        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED, LORA, MULTI, NESTED>(a);
+        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED, LORA, MULTI, NESTED>(a);
+        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED, LORA, MULTI, NESTED>(a);
+        default: return dispatch_wide_nf4_nt<DT, 4, FUSED, LORA, MULTI, NESTED>(a);
     }
 }
 
@@ -292,11 +317,47 @@ namespace {
 int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                         const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode,
                         void *stream, bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0,
-                        bool multi = false, const int32_t *ids = nullptr, int64_t n_adapters = 0) {
+                        bool multi = false, const int32_t *ids = nullptr, int64_t n_adapters = 0, const float *nested_absmax = nullptr,
+                        const float *nested_code = nullptr, float nested_offset = 0.0f) {
     if (const int rc = nf4_check_args(name, lora ? 64 : 128, 64, x, packed, absmax, out, B, M, K, blocksize, dtype, mode, lora, lora_B, lora_t, R))
         return rc;
     if (M == 0 || B == 0) return FP4_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (nested_absmax) {  // `absmax` points at the uint8 codes; the same two kernels by the same rules, with or without the adapter term
+        if (lora) {
+            if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
+        }
+        if (B <= 16 && K % 512 == 0) {
+            gemm_small_nf4_nested_launch(dtype, x, packed, reinterpret_cast<const uint8_t *>(absmax), nested_absmax, nested_code, nested_offset,
+                                         bias, residual, lora ? lora_B : nullptr, lora_t, (int)R, out, (int)B, (int)M, (int)K, mode, s);
+            return check_launch(name);
+        }
+        const int64_t M_out = (mode & kModeSiluMulPairs) ? M / 2 : M;
+        const int64_t first = B > 64 ? (B + 1) / 2 : B;  // with an adapter B <= 64: one chunk
+        for (int64_t b0 = 0; b0 < B; b0 += first) {
+            const int rows = (int)(B - b0 < first ? B - b0 : first);
+            Nf4GemmArgs a{static_cast<const uint8_t *>(x) + b0 * K * 2,
+                          packed,
+                          absmax,
+                          bias,
+                          residual ? static_cast<const uint8_t *>(residual) + b0 * M_out * 2 : nullptr,
+                          static_cast<uint8_t *>(out) + b0 * M_out * 2,
+                          rows,
+                          (int)M,
+                          (int)K,
+                          mode,
+                          s,
+                          lora_B,
+                          lora_t,
+                          (int)R};
+            a.nested_absmax = nested_absmax, a.nested_code = nested_code, a.nested_offset = nested_offset;
+            with_dtype(dtype, [&](auto dt) {
+                constexpr int DT = decltype(dt)::value;
+                lora ? dispatch_wide_nf4<DT, true, true, false, true>(a) : dispatch_wide_nf4<DT, true, false, false, true>(a);
+            });
+        }
+        return check_launch(name);
+    }
     if (multi) {  // lora_B is the stack; the same two kernels by the same rule
         if (const int rc = lora_check_stack(name, lora_B, ids, n_adapters, lora_t, R)) return rc;
         if (B <= 16 && K % 512 == 0) {
@@ -389,4 +450,29 @@ extern "C" int fp4_hip_gemm_lora_multi_nf4(const void *x, const uint8_t *packed,
     return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_lora_multi_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
                                     epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, B_stack, t, R, true,
                                     ids, n_adapters);
+}
+
+extern "C" int fp4_hip_gemm_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                       const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
+                                       void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
+    const char *name = "fp4_hip_gemm_nested_nf4";
+    if (const int rc = fp4::nested_check_args(name, "GEMM", "fp4_hip_gemm_fused_nf4", epilogue, nested_blocksize, B > 0 ? M : 0, K, nested_absmax,
+                                              code256))
+        return rc;
+    return fp4::gemm_wide_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, B, M, K, blocksize,
+                                    dtype, epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, false, nullptr, nullptr,
+                                    0, false, nullptr, 0, nested_absmax, code256, offset);
+}
+
+extern "C" int fp4_hip_gemm_lora_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                            const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
+                                            const void *lora_B, const float *t, int64_t R, void *out, int64_t B, int64_t M, int64_t K,
+                                            int blocksize, int dtype, int epilogue, void *stream) {
+    const char *name = "fp4_hip_gemm_lora_nested_nf4";
+    if (const int rc = fp4::nested_check_args(name, "GEMM", "fp4_hip_gemm_lora_nf4", epilogue, nested_blocksize, B > 0 ? M : 0, K, nested_absmax,
+                                              code256))
+        return rc;
+    return fp4::gemm_wide_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, B, M, K, blocksize,
+                                    dtype, epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R, false,
+                                    nullptr, 0, nested_absmax, code256, offset);
 }

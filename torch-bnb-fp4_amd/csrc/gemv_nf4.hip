@@ -33,12 +33,13 @@
 // kernel's; without one neither B nor t is read and the delta is not added, so the bits are the FUSED kernel's.  It exists so that a
 // captured one-row step follows an in-place change of the id.
 //
-// Nested (double-quantised) absmax (fp4_hip_gemv_nested_nf4): the NESTED instantiations (always FUSED, never LORA) read the block
+// Nested (double-quantised) absmax (fp4_hip_gemv_nested_nf4, with the adapter term fp4_hip_gemv_lora_nested_nf4): the NESTED
+// instantiations (always FUSED, with or without LORA, never MULTI) read the block
 // scale as bitsandbytes' compress_statistics stores it - a uint8 code per block, an f32 scale per 256 blocks, a 256-entry f32 table
 // and an offset - and form absmax = fl32(fl32(table[code] * group) + offset) themselves (unnest_scale, nested_absmax.h): 33 instead
 // of 36 bytes streamed per 64 weights and a quarter of the resident statistics.  The table sits in LDS beside the NF4 table; the
 // code byte and the group scale are requested where the f32 scale was.  Everything after the scale is the FUSED kernel's, so the
-// result equals fp4_hip_gemv_fused_nf4 on the expanded absmax bit for bit.
+// result equals fp4_hip_gemv_fused_nf4 (with LORA: fp4_hip_gemv_lora_nf4) on the expanded absmax bit for bit.
 #include <atomic>
 
 #include "gemv_common.h"
@@ -93,7 +94,7 @@ struct OutPtr<true> {
 // FUSED = false: `residual` and `mode` are ignored (fp4_hip_gemv_nf4).  FUSED = true: the row epilogue adds the residual, and with
 // kModeSiluMulPairs (16-bit DT only, M even) rows (2i, 2i + 1) are a gate / up pair and out[i] = silu(gate_i) * up_i (+ residual[i]).
 // LORA = true (with FUSED): delta[row] = sum_j lora_B[row][j] * lora_t[j] (R % 8 == 0, 8 <= R <= 256) is added to the f32 row sum first.
-// NESTED = true (with FUSED, without LORA): `absmax` points at uint8 codes, one per block; the scale of block i is
+// NESTED = true (with FUSED, without MULTI): `absmax` points at uint8 codes, one per block; the scale of block i is
 // unnest_scale(nested_code[code[i]], nested_absmax[i >> 8], nested_offset).
 // MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R], lora_ids[0] names the adapter; outside 0 .. n_adapters - 1 = none.
 template <int DT, int KSPLIT, int G, int ITERS, bool PAIR, bool FUSED, bool LORA = false, bool NESTED = false, bool MULTI = false>
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
         adapted = uint32_t(id) < uint32_t(n_adapters);
         if (adapted) lora_B = reinterpret_cast<const uint8_t *>(lora_B) + int64_t(id) * M * R * (DT == FP4_DTYPE_F32 ? 4 : 2);
     }
-    static_assert(!NESTED || (FUSED && !LORA), "nested absmax comes with the fused epilogues and without the adapter term");
+    static_assert(!NESTED || (FUSED && !MULTI), "nested absmax comes with the fused epilogues and without the adapter stack");
     const void *residual = FUSED ? residual_arg : nullptr;
     [[maybe_unused]] const bool gated = FUSED && DT != FP4_DTYPE_F32 && (mode & kModeSiluMulPairs);
     constexpr int RG = 4 / KSPLIT;
@@ -383,8 +384,8 @@ namespace {
 
 // fused = false: fp4_hip_gemv_nf4 (irregular shapes run the generic kernel).  fused = true: fp4_hip_gemv_fused_nf4 (the fast path or
 // FP4_ERR_UNSUPPORTED with nothing launched).  `name` is the entry point the messages speak for.  lora = true (with fused):
-// fp4_hip_gemv_lora_nf4, the fused form plus the adapter term.  nested_absmax != nullptr (with fused, without lora):
-// fp4_hip_gemv_nested_nf4 - `absmax` then points at the uint8 codes of the compressed statistics.  multi = true (with lora):
+// fp4_hip_gemv_lora_nf4, the fused form plus the adapter term.  nested_absmax != nullptr (with fused, without multi):
+// fp4_hip_gemv_nested_nf4, with lora fp4_hip_gemv_lora_nested_nf4 - `absmax` then points at the uint8 codes of the compressed statistics.  multi = true (with lora):
 // fp4_hip_gemv_lora_multi_nf4 - lora_B is a stack of n_adapters adapters and ids[0] names the one to apply.
 int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                    const void *residual, void *out, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream,
@@ -432,6 +433,16 @@ int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *p
         const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
         Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s};
         a.nested_absmax = nested_absmax, a.nested_code = nested_code, a.nested_offset = nested_offset;
+        if (lora) {
+            if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
+            a.lora_B = lora_B, a.lora_t = lora_t, a.R = (int)R;
+            switch (dtype) {
+                case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, true, true>(pair, a); break;
+                case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, true, true>(pair, a); break;
+                default: dispatch_nf4<FP4_DTYPE_F32, true, true, true>(pair, a); break;
+            }
+            return check_launch(name);
+        }
         switch (dtype) {
             case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, false, true>(pair, a); break;
             case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, false, true>(pair, a); break;
@@ -527,25 +538,22 @@ extern "C" int fp4_hip_gemv_nested_nf4(const void *x, const uint8_t *packed, con
                                        const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
                                        void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemv_nested_nf4";
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("%s: unknown epilogue %d", name, epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    if (nested_blocksize <= 0) {
-        fp4::set_error("%s: nested_blocksize=%d (need a positive group size)", name, nested_blocksize);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    if (M > 0 && K > 0 && (!nested_absmax || !code256)) {  // absmax_u8 is checked with the other operands
-        fp4::set_error("%s: null pointer", name);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    if (nested_blocksize != (1 << fp4::kNestedGemvShift)) {
-        fp4::set_error("%s: nested_blocksize %d is not covered (the GEMV reads groups of 256 blocks); expand the statistics with "
-                       "fp4_hip_absmax_unnest and run fp4_hip_gemv_fused_nf4", name, nested_blocksize);
-        return FP4_ERR_UNSUPPORTED;
-    }
+    if (const int rc = fp4::nested_check_args(name, "GEMV", "fp4_hip_gemv_fused_nf4", epilogue, nested_blocksize, M, K, nested_absmax, code256))
+        return rc;
     // K == 0 never reaches a kernel: the fused form refuses it (not the fast path) before the statistics are looked at
     return fp4::gemv_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, M, K, blocksize, dtype,
                                epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, false, nullptr, nullptr, 0,
                                nested_absmax, code256, offset);
+}
+
+extern "C" int fp4_hip_gemv_lora_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
+                                            const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
+                                            const void *lora_B, const float *t, int64_t R, void *out, int64_t M, int64_t K, int blocksize,
+                                            int dtype, int epilogue, void *stream) {
+    const char *name = "fp4_hip_gemv_lora_nested_nf4";
+    if (const int rc = fp4::nested_check_args(name, "GEMV", "fp4_hip_gemv_lora_nf4", epilogue, nested_blocksize, M, K, nested_absmax, code256))
+        return rc;
+    return fp4::gemv_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, M, K, blocksize, dtype,
+                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R, nested_absmax,
+                               code256, offset);
 }

@@ -17,6 +17,9 @@ void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, cons
 void gemm_small_nf4_lora_multi_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
                                       const void *B_stack, const int32_t *ids, int n_adapters, const float *lora_t, int R, void *out, int B,
                                       int M, int K, int mode, hipStream_t stream);
+void gemm_small_nf4_nested_launch(int dtype, const void *x, const uint8_t *W, const uint8_t *absmax_u8, const float *nested_absmax,
+                                  const float *nested_code, float nested_offset, const void *bias, const void *residual, const void *lora_B,
+                                  const float *lora_t, int R, void *out, int B, int M, int K, int mode, hipStream_t stream);
 
 // gemm_wide_fp4.hip, gemm_splitk_fp4.hip, for gemm_small_fp4.hip: FP4_OK after the launch, -1 where the shape is not theirs
 int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,

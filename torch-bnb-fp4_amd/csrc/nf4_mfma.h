@@ -117,6 +117,9 @@ struct Nf4GemmArgs {
     int R = 0;
     const int32_t *lora_ids = nullptr;  // MULTI instantiations only: lora_B is then the stack
     int n_adapters = 0;
+    const float *nested_absmax = nullptr;  // NESTED instantiations only (absmax then points at the uint8 codes)
+    const float *nested_code = nullptr;
+    float nested_offset = 0.0f;
 };
 
 // runtime dtype (validated: fp16 or bf16) -> template argument: f(std::integral_constant<int, FP4_DTYPE_F16 or FP4_DTYPE_BF16>{})

@@ -19,7 +19,8 @@
 //     qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4, gemv_nf4_fused, gemm_nf4_fused, quantize_nf4;
 //   * LoRA adapters beside an NF4 weight: lora_down, gemv_nf4_lora, gemm_nf4_lora; several adapters per batch, chosen per row on
 //     the device: lora_down_multi, gemv_nf4_lora_multi, gemm_nf4_lora_multi;
-//   * double-quantised absmax: absmax_unnest, absmax_nest, gemv_nf4_nested, qlinear_nf4_nested;
+//   * double-quantised absmax: absmax_unnest, absmax_nest, gemv_nf4_nested, gemm_nf4_nested, gemv_nf4_lora_nested,
+//     gemm_nf4_lora_nested, qlinear_nf4_nested;
 //   * tensor parallelism: comm_alloc / comm_open / comm_close / comm_free / comm_status / comm_clear_status, allreduce_oneshot;
 //   * hooks: code_table, set_kernel_variant, set_qlinear_gemm.
 // The fused 4-bit weight ops (every *_fused, gemm_small_*, gemm_wide_nf4, *_lora, gemv_nf4_nested, gemv_fp4_partial) validate their
@@ -743,6 +744,56 @@ torch::Tensor gemv_nf4_nested(torch::Tensor A, torch::Tensor B, torch::Tensor ab
     return std::move(w.out);
 }
 
+// gemm_nf4_fused, gemv_nf4_lora and gemm_nf4_lora reading the compressed statistics (fp4_hip_gemm_nested_nf4,
+// fp4_hip_gemv_lora_nested_nf4, fp4_hip_gemm_lora_nested_nf4): the un-nested op's shapes, with the statistics in absmax's place
+torch::Tensor nf4_nested_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax_u8,
+                              const torch::Tensor &nested_absmax, const torch::Tensor &code, double offset, int64_t nested_blocksize,
+                              int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
+                              const c10::optional<torch::Tensor> &residual, int epilogue, const torch::Tensor *lora_B = nullptr,
+                              const torch::Tensor *lora_t = nullptr) {
+    TORCH_CHECK(blocksize > 0, op, ": blocksize must be positive");
+    WeightCall w = weight_op({op, gemv ? 1 : 128}, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue);
+    check_nested(op, absmax_u8, nested_absmax, code, nested_blocksize, (w.m * w.k + blocksize - 1) / blocksize);
+    check_on_device(op, "absmax_u8", absmax_u8, A);
+    const int64_t R = lora_B ? check_lora(op, A, w, *lora_B, *lora_t) : 0;
+    c10::DeviceGuard guard(A.device());
+    if (!lora_B)
+        check_status(fp4_hip_gemm_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(), nested_absmax.data_ptr<float>(),
+                                             code.data_ptr<float>(), (float)offset, (int)nested_blocksize, w.bias_ptr, w.res_ptr,
+                                             w.out.data_ptr(), w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    else if (gemv)
+        check_status(fp4_hip_gemv_lora_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(),
+                                                  nested_absmax.data_ptr<float>(), code.data_ptr<float>(), (float)offset, (int)nested_blocksize,
+                                                  w.bias_ptr, w.res_ptr, lora_B->data_ptr(), lora_t->data_ptr<float>(), R, w.out.data_ptr(), w.m,
+                                                  w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    else
+        check_status(fp4_hip_gemm_lora_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(),
+                                                  nested_absmax.data_ptr<float>(), code.data_ptr<float>(), (float)offset, (int)nested_blocksize,
+                                                  w.bias_ptr, w.res_ptr, lora_B->data_ptr(), lora_t->data_ptr<float>(), R, w.out.data_ptr(),
+                                                  w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    return std::move(w.out);
+}
+torch::Tensor gemm_nf4_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
+                              double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
+                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    return nf4_nested_impl("gemm_nf4_nested", false, A, B, absmax_u8, nested_absmax, code, offset, nested_blocksize, blocksize, Bshape, bias,
+                           residual, epilogue);
+}
+torch::Tensor gemv_nf4_lora_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
+                                   double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
+                                   c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
+                                   torch::Tensor lora_B, torch::Tensor t) {
+    return nf4_nested_impl("gemv_nf4_lora_nested", true, A, B, absmax_u8, nested_absmax, code, offset, nested_blocksize, blocksize, Bshape, bias,
+                           residual, epilogue, &lora_B, &t);
+}
+torch::Tensor gemm_nf4_lora_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
+                                   double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
+                                   c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
+                                   torch::Tensor lora_B, torch::Tensor t) {
+    return nf4_nested_impl("gemm_nf4_lora_nested", false, A, B, absmax_u8, nested_absmax, code, offset, nested_blocksize, blocksize, Bshape, bias,
+                           residual, epilogue, &lora_B, &t);
+}
+
 // unnest into a temporary from the caching allocator (stream-ordered: no sync, capturable), then qlinear_nf4 / qlinear_nf4_bias
 torch::Tensor qlinear_nf4_nested(torch::Tensor A_in, torch::Tensor A, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
                                  double offset, int64_t nested_blocksize, int M, int N, int blocksize, c10::optional<torch::Tensor> bias) {
@@ -909,6 +960,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemv_nf4_nested", &gemv_nf4_nested,
           "gemv_nf4_fused reading double-quantised absmax: (A, B, absmax_u8, nested_absmax, nested_code, offset, nested_blocksize, blocksize, "
           "Bshape, bias|None, residual|None, epilogue)");
+    m.def("gemm_nf4_nested", &gemm_nf4_nested,
+          "gemm_nf4_fused reading double-quantised absmax: (A, B, absmax_u8, nested_absmax, nested_code, offset, nested_blocksize, blocksize, "
+          "[m, k] of the weight, bias|None, residual|None, epilogue)");
+    m.def("gemv_nf4_lora_nested", &gemv_nf4_lora_nested,
+          "gemv_nf4_lora reading double-quantised absmax: (A, B, absmax_u8, nested_absmax, nested_code, offset, nested_blocksize, blocksize, "
+          "[m, k] of the weight, bias|None, residual|None, epilogue, lora_B [m, R], t float32 [1, R])");
+    m.def("gemm_nf4_lora_nested", &gemm_nf4_lora_nested,
+          "gemm_nf4_lora reading double-quantised absmax: (A, B, absmax_u8, nested_absmax, nested_code, offset, nested_blocksize, blocksize, "
+          "[m, k] of the weight, bias|None, residual|None, epilogue, lora_B [m, R], t float32 [rows, R])");
     m.def("qlinear_nf4_nested", &qlinear_nf4_nested,
           "absmax_unnest + NF4 dequant + linear: (A_in, A, absmax_u8, nested_absmax, nested_code, offset, nested_blocksize, M, N, blocksize, bias|None)");
     m.def("quantize_nf4", &quantize_nf4, "blockwise NF4 quantiser: (W, blocksize) -> (packed, absmax)");

@@ -15,7 +15,9 @@ behind ``nf4_wide=True`` (``QuantData.wide_batch_fused_nf4``, off by default) a 
 in_features % 512 != 0 (``ext.gemm_wide_nf4``; blocksize 64, in_features % 64 == 0, fp16 / bf16); everything else is NF4 dequant + GEMM.
 Double-quantised (nested) absmax - ``bnb_4bit_use_double_quant=True`` - loads either expanded to f32 once (the default: every kernel
 above applies) or, with ``load_fp4_layers(..., nested="resident")``, stays compressed on the device in :class:`NestedNF4Linear`, whose
-one-token path is a GEMV that reads the compressed statistics directly (:mod:`torch_bnb_fp4.nested`).
+one-token path is a GEMV that reads the compressed statistics directly (:mod:`torch_bnb_fp4.nested`); the two NF4 switches above route
+its 2..64-row calls to the same fused kernels reading the compressed statistics (``ext.gemm_nf4_nested``), and ``attach_lora`` gives
+it an adapter (:class:`LoRANestedNF4Linear`).
 bitsandbytes is optional: :mod:`torch_bnb_fp4.nn` provides attribute-compatible ``LinearFP4`` /
 ``Params4bit`` / ``QuantState`` and the quantiser runs on the GPU through this package.
 """
@@ -37,7 +39,7 @@ from .comm import OneShotAllReduce
 from .fused import AdapterSelection, FusedFP4Linear, FusedNF4Linear, LoRANF4Linear, MultiLoRANF4Linear
 from .graphs import GraphedStep
 from .linear import TorchFP4Linear
-from .nested import NestedNF4Linear, expand_nested
+from .nested import LoRANestedNF4Linear, NestedNF4Linear, expand_nested
 from .nn import Linear4bit, LinearFP4, LinearNF4, Params4bit, QuantState, nf4_code
 from .quant_data import QuantData
 from .serialization import fp4_linear_from_bnb_state, fp4_linear_to_bnb_state, load_fp4_layers, save_fp4_model
@@ -98,6 +100,7 @@ __all__ = [
     "attach_lora_adapters",
     "load_lora_adapters",
     "NestedNF4Linear",
+    "LoRANestedNF4Linear",
     "expand_nested",
 ]
 __version__ = "0.1.0"

@@ -303,7 +303,44 @@ def lora_scaling(r: int, lora_alpha: float, use_rslora: bool = False) -> float:
     return float(lora_alpha) / (math.sqrt(r) if use_rslora else r)
 
 
-class LoRANF4Linear(FusedNF4Linear):
+class LoRAAdapterMixin:
+    """One LoRA adapter held beside a 4-bit weight, shared by :class:`LoRANF4Linear` and
+    :class:`~torch_bnb_fp4.nested.LoRANestedNF4Linear`: the buffers ``lora_A`` / ``lora_B`` / ``lora_scale`` padded to a multiple of 8
+    (:func:`pad_adapter`), ``rank``, ``_lora_ok`` and the per-dtype casts."""
+
+    def _init_adapter(self, lora_A: torch.Tensor, lora_B: torch.Tensor, scale, M: int, K: int, dev) -> None:
+        if lora_A.ndim != 2 or lora_B.ndim != 2 or lora_A.shape[1] != K or lora_B.shape != (M, lora_A.shape[0]):
+            raise ValueError(f"adapter shapes {tuple(lora_A.shape)} / {tuple(lora_B.shape)} do not fit a [{M}, {K}] weight (need A [r, K] "
+                             "and B [M, r])")
+        self.rank = int(lora_A.shape[0])
+        if not torch.is_tensor(scale):
+            scale = torch.full((self.rank,), float(scale))
+        if scale.numel() != self.rank:
+            raise ValueError(f"scale must be one factor or one per adapter row ({self.rank}), got {scale.numel()}")
+        A, B, sc = pad_adapter(lora_A.detach().to(dev), lora_B.detach().to(dev), scale.detach().reshape(-1).to(device=dev, dtype=torch.float32))
+        self.register_buffer("lora_A", A, persistent=True)
+        self.register_buffer("lora_B", B, persistent=True)
+        self.register_buffer("lora_scale", sc, persistent=True)
+        self._lora_ok = A.shape[0] <= LORA_MAX_RANK  # cleared as well when lora_down reports a shape as not covered
+        self._cast = {}  # activation dtype -> (A, B) in that dtype
+
+    def _adapter(self, dtype: torch.dtype):
+        # the adapter follows the activation dtype, as the bias does; the buffers stay as attached and every cast starts from them,
+        # so a layer that meets two activation dtypes rounds the adapter once for each, never twice in a row
+        if self.lora_A.dtype == dtype:
+            return self.lora_A, self.lora_B
+        cast = self._cast.get(dtype)
+        if cast is None or cast[0].device != self.lora_A.device:
+            cast = self._cast[dtype] = (self.lora_A.to(dtype), self.lora_B.to(dtype))
+        return cast
+
+    def _adapter_delta(self, x: torch.Tensor) -> torch.Tensor:
+        """The adapter term in torch, in f32: ``(x.float() @ A.float().T * scale) @ B.float().T``."""
+        A, B = self._adapter(x.dtype)
+        return (x.float() @ A.float().t() * self.lora_scale) @ B.float().t()
+
+
+class LoRANF4Linear(LoRAAdapterMixin, FusedNF4Linear):
     """A :class:`FusedNF4Linear` with a LoRA adapter: ``forward(x, residual=None)`` = epilogue of ``W x + B (s * A x)``.
 
     ``lora_A`` is ``[r, K]``, ``lora_B`` ``[M, r]`` over the weight's own rows (``M`` = all rows of an interleaved gate|up weight),
@@ -319,21 +356,7 @@ class LoRANF4Linear(FusedNF4Linear):
 
     def __init__(self, quant_data: QuantData, epilogue: int, lora_A: torch.Tensor, lora_B: torch.Tensor, scale):
         super().__init__(quant_data, epilogue)
-        if lora_A.ndim != 2 or lora_B.ndim != 2 or lora_A.shape[1] != self.in_features or lora_B.shape != (int(quant_data.M), lora_A.shape[0]):
-            raise ValueError(f"adapter shapes {tuple(lora_A.shape)} / {tuple(lora_B.shape)} do not fit a [{int(quant_data.M)}, "
-                             f"{self.in_features}] weight (need A [r, K] and B [M, r])")
-        self.rank = int(lora_A.shape[0])
-        dev = self.qweight.device
-        if not torch.is_tensor(scale):
-            scale = torch.full((self.rank,), float(scale))
-        if scale.numel() != self.rank:
-            raise ValueError(f"scale must be one factor or one per adapter row ({self.rank}), got {scale.numel()}")
-        A, B, sc = pad_adapter(lora_A.detach().to(dev), lora_B.detach().to(dev), scale.detach().reshape(-1).to(device=dev, dtype=torch.float32))
-        self.register_buffer("lora_A", A, persistent=True)
-        self.register_buffer("lora_B", B, persistent=True)
-        self.register_buffer("lora_scale", sc, persistent=True)
-        self._lora_ok = A.shape[0] <= LORA_MAX_RANK  # cleared as well when lora_down reports a shape as not covered
-        self._cast = {}  # activation dtype -> (A, B) in that dtype
+        self._init_adapter(lora_A, lora_B, scale, int(quant_data.M), self.in_features, self.qweight.device)
 
     # -- constructors ------------------------------------------------------------------------------------------------
     @classmethod
@@ -374,19 +397,8 @@ class LoRANF4Linear(FusedNF4Linear):
         return self
 
     # -- forward -----------------------------------------------------------------------------------------------------
-    def _adapter(self, dtype: torch.dtype):
-        # the adapter follows the activation dtype, as the bias does; the buffers stay as attached and every cast starts from them,
-        # so a layer that meets two activation dtypes rounds the adapter once for each, never twice in a row
-        if self.lora_A.dtype == dtype:
-            return self.lora_A, self.lora_B
-        cast = self._cast.get(dtype)
-        if cast is None or cast[0].device != self.lora_A.device:
-            cast = self._cast[dtype] = (self.lora_A.to(dtype), self.lora_B.to(dtype))
-        return cast
-
     def _adapter_in_torch(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
-        A, B = self._adapter(x.dtype)
-        delta = (x.float() @ A.float().t() * self.lora_scale) @ B.float().t()
+        delta = self._adapter_delta(x)
         if self.epilogue == EPILOGUE_SILU_MUL_PAIRS:
             y = (self.quant_data.forward(x).float() + delta).to(x.dtype)
             y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]

@@ -146,9 +146,21 @@ def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = F
     ``small_batch_fused_nf4`` is set as well - 2..16 rows of fp16 / bf16 activations go to the fused NF4 matrix-core kernel
     (blocksize 64, K % 512 == 0; anything else stays on dequant + GEMM) - and those layers are counted too.  ``nf4_wide=True``
     sets every NF4 layer's ``wide_batch_fused_nf4``: 17..64 rows, and 2..16 rows where K % 512 != 0, go to the one-pass NF4
-    kernel (``ext.gemm_wide_nf4``; blocksize 64, K % 64 == 0); an NF4 layer is counted once whichever of the two is set."""
+    kernel (``ext.gemm_wide_nf4``; blocksize 64, K % 64 == 0); an NF4 layer is counted once whichever of the two is set.
+    A resident :class:`~torch_bnb_fp4.nested.NestedNF4Linear` (NF4, statistics compressed on the device) takes the two NF4 switches
+    the same way and is counted like an NF4 layer: the same cells then run ``ext.gemm_nf4_nested`` instead of its expand path."""
+    from .nested import NestedNF4Linear
+
     n = 0
     for m in module.modules():
+        if isinstance(m, NestedNF4Linear):
+            if nf4 or nf4_wide:
+                if nf4:
+                    m.small_batch_fused_nf4 = bool(enabled)
+                if nf4_wide:
+                    m.wide_batch_fused_nf4 = bool(enabled)
+                n += 1
+            continue
         if not isinstance(m, TorchFP4Linear):
             continue
         if not m.quant_data.nf4:
@@ -191,7 +203,8 @@ def fuse_gated_mlps(module: nn.Module, gate: str = "gate_proj", up: str = "up_pr
     :class:`FusedGatedMLP`.  Single-token calls then pay one launch for gate + up + activation + product instead of four; other
     shapes run the unfused sequence.  Returns how many were replaced.  Not in the reference (its surface stops at the Linear).
     NF4 MLPs are left alone unless ``nf4=True`` (then their gate / up pair becomes a ``FusedNF4Linear``); a pair whose two
-    projections use different codes is never fused."""
+    projections use different codes is never fused.  Resident :class:`~torch_bnb_fp4.nested.NestedNF4Linear` projections are
+    ignored: a compressed group spans rows, so interleaving them would re-quantise (``expand_nested`` first)."""
     count = 0
     for name, child in list(module.named_children()):
         g, u, d, a = (getattr(child, n, None) for n in (gate, up, down, act))
@@ -250,12 +263,15 @@ def attach_lora(model: nn.Module, adapter_state, r: int, lora_alpha: float, use_
     """Attach a saved LoRA adapter to the NF4 layers of ``model``: every NF4 :class:`TorchFP4Linear` (or
     :class:`~torch_bnb_fp4.fused.FusedNF4Linear`) an adapter key names becomes a :class:`~torch_bnb_fp4.fused.LoRANF4Linear`, and
     the gate|up layer of an NF4 :class:`FusedGatedMLP` (``fuse_gated_mlps(model, nf4=True)``) takes the gate and the up adapter
-    stacked (a projection without one gets a zero adapter).  ``adapter_state`` uses peft's saved key names, with or without the
+    stacked (a projection without one gets a zero adapter).  A resident :class:`~torch_bnb_fp4.nested.NestedNF4Linear` becomes a
+    :class:`~torch_bnb_fp4.nested.LoRANestedNF4Linear` and is counted too, its statistics still compressed (several adapters at
+    once, :func:`attach_lora_adapters`, stay expand-first: ``expand_nested`` before them).  ``adapter_state`` uses peft's saved key names, with or without the
     ``base_model.model.`` prefix and an adapter-name segment; the factor is ``lora_alpha / r`` (``/ sqrt(r)`` with
     ``use_rslora``).  ``target_modules`` (names, as in peft's config) restricts which keys are used; a key that is used but has no
     NF4 home in ``model`` raises, and a call that raises leaves ``model`` as it was.  Adapters are not merged: 4-bit weights cannot absorb them without re-quantising.  Returns the
     number of layers replaced.  peft itself is not needed."""
     from .fused import FusedNF4Linear, LoRANF4Linear, lora_scaling
+    from .nested import LoRANestedNF4Linear, NestedNF4Linear
 
     scaling = lora_scaling(r, lora_alpha, use_rslora)
     adapters = _adapter_tensors(adapter_state)
@@ -281,6 +297,8 @@ def attach_lora(model: nn.Module, adapter_state, r: int, lora_alpha: float, use_
             plan.append((parent, name, LoRANF4Linear.from_linear(child, A, B, scaling)))
         elif type(child) is FusedNF4Linear:
             plan.append((parent, name, LoRANF4Linear.from_fused(child, A, B, scaling)))
+        elif type(child) is NestedNF4Linear:
+            plan.append((parent, name, LoRANestedNF4Linear.from_nested(child, A, B, scaling)))
         else:
             raise ValueError(f"adapter key for {path!r}: {type(child).__name__} is not an NF4 layer (quantise the model with "
                              f"quant_type='nf4' first; an adapter is attached once)")
