@@ -27,6 +27,10 @@
 // FUSED + LORA) fetch the block's uint8 code and its group's f32 scale where the f32 scale was fetched, one pass ahead, and write
 // unnest_scale(table[code], group, offset) (nested_absmax.h: a multiply, then an add) into the LDS image.  Everything that reads the
 // image is unchanged, so the result equals the FUSED / LORA instantiation on the expanded absmax bit for bit.
+//
+// Host side: fp4_hip_gemm_small_nf4 (the plain form) and gemm_small_nf4_launch (any form, for the entry points of gemm_wide_nf4.hip)
+// take an Nf4Call (nf4_call.h); dispatch_nf4_mfma goes from its form and dtype (with_nf4_form, with_dtype) to the geometry to the
+// launch (launch_nf4_mfma, the only place that spells the kernel's flag order).
 #include "launchers.h"
 #include "nested_absmax.h"
 #include "nf4_mfma.h"
@@ -238,78 +242,56 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     }
 }
 
-template <int DT, int NBW, int XS, bool FUSED, bool LORA, bool MULTI, bool NESTED>
-void launch_nf4_mfma(const Nf4GemmArgs &a) {
-    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, FUSED, LORA, MULTI, NESTED>), dim3((unsigned)((a.M + 15) / 16)), dim3(512), 0, a.stream,
-                       reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
-                       reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K, reinterpret_cast<const uint16_t *>(a.residual), a.mode,
-                       reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R, a.lora_ids, a.n_adapters, a.nested_absmax, a.nested_code,
-                       a.nested_offset);
+// Form: the Nf4Form of the call (nf4_call.h).  The kernel's own flag order is spelt here and nowhere else on the host.
+template <int DT, int NBW, int XS, typename Form>
+void launch_nf4_mfma(const Nf4Call &a) {
+    hipLaunchKernelGGL((gemm_nf4_mfma_kernel<DT, NBW, XS, Form::fused, Form::lora, Form::multi, Form::nested>), dim3((unsigned)((a.M + 15) / 16)),
+                       dim3(512), 0, a.stream, static_cast<const uint16_t *>(a.x), a.W, static_cast<const float *>(a.scales),
+                       static_cast<const uint16_t *>(a.bias), static_cast<uint16_t *>(a.out), (int)a.B, (int)a.M, (int)a.K,
+                       static_cast<const uint16_t *>(a.residual), a.mode, static_cast<const uint16_t *>(a.adapter.B), a.adapter.t,
+                       (int)a.adapter.R, a.adapter.ids, (int)a.adapter.n_adapters, a.nested_stats.group, a.nested_stats.table,
+                       a.nested_stats.offset);
 }
 
-template <int DT, bool FUSED, bool LORA = false, bool MULTI = false, bool NESTED = false>
-void dispatch_nf4_mfma(const Nf4GemmArgs &a) {
-    const int B = a.B, M = a.M, K = a.K;
+template <int DT, typename Form>
+void dispatch_nf4_mfma_shape(const Nf4Call &a) {
+    const int B = (int)a.B, M = (int)a.M, K = (int)a.K;
     const int units = K / 512;  // quant blocks per wave over the whole K
     const int blocks = (M + 15) / 16;
     // the FP4 kernel's rules: at most 4 blocks per wave and pass; x staged per wave in LDS always for <= 4 rows, for 5..8 rows only
     // while the grid is a single round anyway (the larger image leaves fewer workgroups per CU)
     if (units % 4 == 0) {
-        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, FUSED, LORA, MULTI, NESTED>(a);
-        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, FUSED, LORA, MULTI, NESTED>(a);
-        return launch_nf4_mfma<DT, 4, 0, FUSED, LORA, MULTI, NESTED>(a);
+        if (B <= 4) return launch_nf4_mfma<DT, 4, 4, Form>(a);
+        if (B <= 8 && blocks <= device_cu_count()) return launch_nf4_mfma<DT, 4, 8, Form>(a);
+        return launch_nf4_mfma<DT, 4, 0, Form>(a);
     }
-    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, FUSED, LORA, MULTI, NESTED>(a);
-    return launch_nf4_mfma<DT, 1, 0, FUSED, LORA, MULTI, NESTED>(a);
+    if (units % 2 == 0) return launch_nf4_mfma<DT, 2, 0, Form>(a);
+    return launch_nf4_mfma<DT, 1, 0, Form>(a);
+}
+
+// a validated call of any form -> its kernel
+void dispatch_nf4_mfma(const Nf4Call &a) {
+    with_nf4_form(a, [&](auto form) {
+        with_dtype(a.dtype, [&](auto dt) { dispatch_nf4_mfma_shape<decltype(dt)::value, decltype(form)>(a); });
+    });
 }
 
 }  // namespace
 
-// the fused-epilogue form for fp4_hip_gemm_fused_nf4 (gemm_wide_nf4.hip), which has validated the arguments: 1..16 rows,
+// for the entry points of gemm_wide_nf4.hip, which have validated the call - operands, adapter and statistics: 1..16 rows,
 // K % 512 == 0, fp16 / bf16, M even for the gate|up epilogue.  Launches only.
-void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                 void *out, int B, int M, int K, int mode, hipStream_t stream) {
-    const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream};
-    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true>(a); });
-}
-
-// the same with the adapter term, for fp4_hip_gemm_lora_nf4 (gemm_wide_nf4.hip), which has validated the adapter as well
-void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                const void *lora_B, const float *lora_t, int R, void *out, int B, int M, int K, int mode,
-                                hipStream_t stream) {
-    const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, lora_B, lora_t, R};
-    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true, true>(a); });
-}
-
-// the same with a stack of adapters and one id per activation row, for fp4_hip_gemm_lora_multi_nf4 (gemm_wide_nf4.hip)
-void gemm_small_nf4_lora_multi_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                      const void *B_stack, const int32_t *ids, int n_adapters, const float *lora_t, int R, void *out, int B,
-                                      int M, int K, int mode, hipStream_t stream) {
-    const Nf4GemmArgs a{x, W, absmax, bias, residual, out, B, M, K, mode, stream, B_stack, lora_t, R, ids, n_adapters};
-    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, true, true, true>(a); });
-}
-
-// the two forms above reading double-quantised absmax, for fp4_hip_gemm_nested_nf4 / fp4_hip_gemm_lora_nested_nf4 (gemm_wide_nf4.hip),
-// which have validated the statistics as well; lora_B == nullptr: no adapter term
-void gemm_small_nf4_nested_launch(int dtype, const void *x, const uint8_t *W, const uint8_t *absmax_u8, const float *nested_absmax,
-                                  const float *nested_code, float nested_offset, const void *bias, const void *residual, const void *lora_B,
-                                  const float *lora_t, int R, void *out, int B, int M, int K, int mode, hipStream_t stream) {
-    Nf4GemmArgs a{x, W, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, B, M, K, mode, stream, lora_B, lora_t, R};
-    a.nested_absmax = nested_absmax, a.nested_code = nested_code, a.nested_offset = nested_offset;
-    with_dtype(dtype, [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;
-        lora_B ? dispatch_nf4_mfma<DT, true, true, false, true>(a) : dispatch_nf4_mfma<DT, true, false, false, true>(a);
-    });
-}
+void gemm_small_nf4_launch(const Nf4Call &call) { dispatch_nf4_mfma(call); }
 
 }  // namespace fp4
 
 extern "C" int fp4_hip_gemm_small_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                                       int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
     using namespace fp4;
-    if (const int rc = nf4_check_args("fp4_hip_gemm_small_nf4", 16, 512, x, packed, absmax, out, B, M, K, blocksize, dtype, 0)) return rc;
+    const char *name = "fp4_hip_gemm_small_nf4";
+    const Nf4Call c{.x = x, .W = packed, .scales = absmax, .bias = bias, .out = out, .B = B, .M = M, .K = K, .blocksize = blocksize,
+                    .dtype = dtype, .stream = static_cast<hipStream_t>(stream)};
+    if (const int rc = nf4_check_args(name, c, 16, 512)) return rc;
     if (M == 0 || B == 0) return FP4_OK;
-    const Nf4GemmArgs a{x, packed, absmax, bias, nullptr, out, (int)B, (int)M, (int)K, 0, static_cast<hipStream_t>(stream)};
-    with_dtype(dtype, [&](auto dt) { dispatch_nf4_mfma<decltype(dt)::value, false>(a); });
-    return check_launch("fp4_hip_gemm_small_nf4");
+    dispatch_nf4_mfma(c);
+    return check_launch(name);
 }

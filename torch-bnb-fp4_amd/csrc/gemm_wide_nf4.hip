@@ -39,6 +39,11 @@
 // FUSED + LORA) fetch the block's uint8 code and its group's f32 scale where the f32 scale was fetched, one pass ahead, and write
 // unnest_scale(table[code], group, offset) (nested_absmax.h: a multiply, then an add) into the LDS image.  Everything that reads the
 // image is unchanged, so the result equals the FUSED / LORA instantiation on the expanded absmax bit for bit.
+//
+// Host side: the six extern "C" entry points each fill an Nf4Call (nf4_call.h) and share one path, gemm_wide_nf4_entry(name, call):
+// one check, one adapter check, one hand-over to the 2..16-row kernel (gemm_small_nf4_launch), one chunk loop.  dispatch_wide_nf4 goes
+// from the call's form and dtype (with_nf4_form, with_dtype) to the tile counts to the launch (launch_wide_nf4, the only place that
+// spells the kernel's flag order).
 #include <atomic>
 
 #include "launchers.h"
@@ -269,199 +274,133 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
 
 std::atomic<int> g_wide_nf4_variant{-1};  // sweep hook: 1 / 2 = 16 / 32 weight rows per workgroup, anything else = the heuristic
 
-template <int DT, int NT, int RT, int NBW, bool FUSED, bool LORA, bool MULTI, bool NESTED>
-void launch_wide_nf4(const Nf4GemmArgs &a) {
-    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, FUSED, LORA, MULTI, NESTED>), dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))),
-                       dim3(512), 0, a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax,
-                       reinterpret_cast<const uint16_t *>(a.bias), reinterpret_cast<uint16_t *>(a.out), a.B, a.M, a.K,
-                       reinterpret_cast<const uint16_t *>(a.residual), a.mode, reinterpret_cast<const uint16_t *>(a.lora_B), a.lora_t, a.R,
-                       a.lora_ids, a.n_adapters, a.nested_absmax, a.nested_code, a.nested_offset);
+// Form: the Nf4Form of the call (nf4_call.h).  The kernel's own flag order is spelt here and nowhere else on the host.
+template <int DT, int NT, int RT, int NBW, typename Form>
+void launch_wide_nf4(const Nf4Call &a) {
+    hipLaunchKernelGGL((gemm_wide_nf4_kernel<DT, NT, RT, NBW, Form::fused, Form::lora, Form::multi, Form::nested>),
+                       dim3((unsigned)((a.M + 16 * RT - 1) / (16 * RT))), dim3(512), 0, a.stream, static_cast<const uint16_t *>(a.x), a.W,
+                       static_cast<const float *>(a.scales), static_cast<const uint16_t *>(a.bias), static_cast<uint16_t *>(a.out), (int)a.B,
+                       (int)a.M, (int)a.K, static_cast<const uint16_t *>(a.residual), a.mode, static_cast<const uint16_t *>(a.adapter.B),
+                       a.adapter.t, (int)a.adapter.R, a.adapter.ids, (int)a.adapter.n_adapters, a.nested_stats.group, a.nested_stats.table,
+                       a.nested_stats.offset);
 }
 
-template <int DT, int NT, bool FUSED, bool LORA, bool MULTI, bool NESTED>
-void dispatch_wide_nf4_nt(const Nf4GemmArgs &a) {
-    const int M = a.M, K = a.K;
+template <int DT, int NT, typename Form>
+void dispatch_wide_nf4_nt(const Nf4Call &a) {
+    const int M = (int)a.M, K = (int)a.K;
     // 32 weight rows per workgroup halve the x traffic from L2, the kernel's largest stream: taken once that still fills three
     // quarters of the chip (the FP4 wide kernels' rule; measured here on either side of it, profiles/nf4_wide_batch.json)
     const int v = g_wide_nf4_variant.load(std::memory_order_relaxed);
     const bool rt2 = v == 2 || (v != 1 && M >= 24 * device_cu_count());
     const bool nbw4 = K % 256 == 0;
     if (rt2) {
-        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, FUSED, LORA, MULTI, NESTED>(a);
-        return launch_wide_nf4<DT, NT, 2, 1, FUSED, LORA, MULTI, NESTED>(a);
+        if (nbw4) return launch_wide_nf4<DT, NT, 2, 4, Form>(a);
+        return launch_wide_nf4<DT, NT, 2, 1, Form>(a);
     }
-    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, FUSED, LORA, MULTI, NESTED>(a);
-    return launch_wide_nf4<DT, NT, 1, 1, FUSED, LORA, MULTI, NESTED>(a);
+    if (nbw4) return launch_wide_nf4<DT, NT, 1, 4, Form>(a);
+    return launch_wide_nf4<DT, NT, 1, 1, Form>(a);
 }
 
-// one launch: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
-template <int DT, bool FUSED, bool LORA = false, bool MULTI = false, bool NESTED = false>
-void dispatch_wide_nf4(const Nf4GemmArgs &a) {
-    switch ((a.B + 15) / 16) {
-        case 1: return dispatch_wide_nf4_nt<DT, 1, FUSED, LORA, MULTI, NESTED>(a);
-        case 2: return dispatch_wide_nf4_nt<DT, 2, FUSED, LORA, MULTI, NESTED>(a);
-        case 3: return dispatch_wide_nf4_nt<DT, 3, FUSED, LORA, MULTI, NESTED>(a);
-        default: return dispatch_wide_nf4_nt<DT, 4, FUSED, LORA, MULTI, NESTED>(a);
+// one launch of a validated call of any form: 1..64 rows, NT = ceil(B / 16) column tiles, the last one ragged
+void dispatch_wide_nf4(const Nf4Call &a) {
+    with_nf4_form(a, [&](auto form) {
+        with_dtype(a.dtype, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value;
+            using Form = decltype(form);
+            switch ((a.B + 15) / 16) {
+                case 1: return dispatch_wide_nf4_nt<DT, 1, Form>(a);
+                case 2: return dispatch_wide_nf4_nt<DT, 2, Form>(a);
+                case 3: return dispatch_wide_nf4_nt<DT, 3, Form>(a);
+                default: return dispatch_wide_nf4_nt<DT, 4, Form>(a);
+            }
+        });
+    });
+}
+
+// The one path of the six entry points below; `name` is the entry point the messages speak for.  A call with an adapter covers at
+// most 64 rows (one launch), the others 128.
+int gemm_wide_nf4_entry(const char *name, const Nf4Call &c) {
+    const int64_t B = c.B, M = c.M, K = c.K;
+    if (const int rc = nf4_check_args(name, c, c.lora() ? 64 : 128, 64)) return rc;
+    if (M == 0 || B == 0) return FP4_OK;
+    if (const int rc = nf4_check_adapter(name, c)) return rc;
+    // 1..16 rows on a K the 2..16-row kernel covers: that kernel, bit for bit
+    if (B <= 16 && K % 512 == 0) {
+        gemm_small_nf4_launch(c);
+        return check_launch(name);
     }
+    const int esize = 2;
+    const int64_t M_out = c.gated() ? M / 2 : M;
+    // 65..128 rows: two even chunks of at most 64, one pass over the weight each (with an adapter B <= 64: one chunk, so t and ids
+    // need no offset)
+    const int64_t first = B > 64 ? (B + 1) / 2 : B;
+    for (int64_t b0 = 0; b0 < B; b0 += first) {
+        Nf4Call chunk = c;
+        chunk.B = B - b0 < first ? B - b0 : first;
+        chunk.x = static_cast<const uint8_t *>(c.x) + b0 * K * esize;
+        if (c.residual) chunk.residual = static_cast<const uint8_t *>(c.residual) + b0 * M_out * esize;
+        chunk.out = static_cast<uint8_t *>(c.out) + b0 * M_out * esize;
+        dispatch_wide_nf4(chunk);
+    }
+    return check_launch(name);
 }
 
 }  // namespace
 
 void set_wide_nf4_variant(int v) { g_wide_nf4_variant.store(v, std::memory_order_relaxed); }
 
-namespace {
-
-// fused = false: fp4_hip_gemm_wide_nf4.  fused = true: fp4_hip_gemm_fused_nf4 (same coverage and forwarding, plus residual / mode).
-// lora = true (with fused): fp4_hip_gemm_lora_nf4, the fused form for at most 64 rows plus the adapter term.
-// multi = true (with lora): fp4_hip_gemm_lora_multi_nf4 - lora_B is a stack of n_adapters adapters, ids[b] the adapter of row b.
-int gemm_wide_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
-                        const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode,
-                        void *stream, bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0,
-                        bool multi = false, const int32_t *ids = nullptr, int64_t n_adapters = 0, const float *nested_absmax = nullptr,
-                        const float *nested_code = nullptr, float nested_offset = 0.0f) {
-    if (const int rc = nf4_check_args(name, lora ? 64 : 128, 64, x, packed, absmax, out, B, M, K, blocksize, dtype, mode, lora, lora_B, lora_t, R))
-        return rc;
-    if (M == 0 || B == 0) return FP4_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (nested_absmax) {  // `absmax` points at the uint8 codes; the same two kernels by the same rules, with or without the adapter term
-        if (lora) {
-            if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
-        }
-        if (B <= 16 && K % 512 == 0) {
-            gemm_small_nf4_nested_launch(dtype, x, packed, reinterpret_cast<const uint8_t *>(absmax), nested_absmax, nested_code, nested_offset,
-                                         bias, residual, lora ? lora_B : nullptr, lora_t, (int)R, out, (int)B, (int)M, (int)K, mode, s);
-            return check_launch(name);
-        }
-        const int64_t M_out = (mode & kModeSiluMulPairs) ? M / 2 : M;
-        const int64_t first = B > 64 ? (B + 1) / 2 : B;  // with an adapter B <= 64: one chunk
-        for (int64_t b0 = 0; b0 < B; b0 += first) {
-            const int rows = (int)(B - b0 < first ? B - b0 : first);
-            Nf4GemmArgs a{static_cast<const uint8_t *>(x) + b0 * K * 2,
-                          packed,
-                          absmax,
-                          bias,
-                          residual ? static_cast<const uint8_t *>(residual) + b0 * M_out * 2 : nullptr,
-                          static_cast<uint8_t *>(out) + b0 * M_out * 2,
-                          rows,
-                          (int)M,
-                          (int)K,
-                          mode,
-                          s,
-                          lora_B,
-                          lora_t,
-                          (int)R};
-            a.nested_absmax = nested_absmax, a.nested_code = nested_code, a.nested_offset = nested_offset;
-            with_dtype(dtype, [&](auto dt) {
-                constexpr int DT = decltype(dt)::value;
-                lora ? dispatch_wide_nf4<DT, true, true, false, true>(a) : dispatch_wide_nf4<DT, true, false, false, true>(a);
-            });
-        }
-        return check_launch(name);
-    }
-    if (multi) {  // lora_B is the stack; the same two kernels by the same rule
-        if (const int rc = lora_check_stack(name, lora_B, ids, n_adapters, lora_t, R)) return rc;
-        if (B <= 16 && K % 512 == 0) {
-            gemm_small_nf4_lora_multi_launch(dtype, x, packed, absmax, bias, residual, lora_B, ids, (int)n_adapters, lora_t, (int)R, out, (int)B,
-                                             (int)M, (int)K, mode, s);
-            return check_launch(name);
-        }
-        const Nf4GemmArgs a{x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s, lora_B, lora_t, (int)R, ids, (int)n_adapters};
-        with_dtype(dtype, [&](auto dt) { dispatch_wide_nf4<decltype(dt)::value, true, true, true>(a); });
-        return check_launch(name);
-    }
-    if (lora) {
-        if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
-        if (B <= 16 && K % 512 == 0) {
-            gemm_small_nf4_lora_launch(dtype, x, packed, absmax, bias, residual, lora_B, lora_t, (int)R, out, (int)B, (int)M, (int)K, mode, s);
-            return check_launch(name);
-        }
-        const Nf4GemmArgs a{x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s, lora_B, lora_t, (int)R};
-        with_dtype(dtype, [&](auto dt) { dispatch_wide_nf4<decltype(dt)::value, true, true>(a); });
-        return check_launch(name);
-    }
-    // 1..16 rows on a K the 2..16-row kernel covers: that kernel, bit for bit
-    if (B <= 16 && K % 512 == 0) {
-        if (!fused) return fp4_hip_gemm_small_nf4(x, packed, absmax, bias, out, B, M, K, blocksize, dtype, stream);
-        gemm_small_nf4_fused_launch(dtype, x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s);
-        return check_launch(name);
-    }
-    const int esize = 2;
-    const int64_t M_out = (mode & kModeSiluMulPairs) ? M / 2 : M;
-    // 65..128 rows: two even chunks of at most 64, one pass over the weight each
-    const int64_t first = B > 64 ? (B + 1) / 2 : B;
-    for (int64_t b0 = 0; b0 < B; b0 += first) {
-        const int rows = (int)(B - b0 < first ? B - b0 : first);
-        const Nf4GemmArgs a{static_cast<const uint8_t *>(x) + b0 * K * esize,
-                            packed,
-                            absmax,
-                            bias,
-                            residual ? static_cast<const uint8_t *>(residual) + b0 * M_out * esize : nullptr,
-                            static_cast<uint8_t *>(out) + b0 * M_out * esize,
-                            rows,
-                            (int)M,
-                            (int)K,
-                            mode,
-                            s};
-        with_dtype(dtype, [&](auto dt) {
-            constexpr int DT = decltype(dt)::value;
-            fused ? dispatch_wide_nf4<DT, true>(a) : dispatch_wide_nf4<DT, false>(a);
-        });
-    }
-    return check_launch(name);
-}
-
-}  // namespace
 }  // namespace fp4
 
 extern "C" int fp4_hip_gemm_wide_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                                      int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
-    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_wide_nf4", false, x, packed, absmax, bias, nullptr, out, B, M, K, blocksize, dtype, 0,
-                                    stream);
+    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_wide_nf4",
+                                    {.x = x, .W = packed, .scales = absmax, .bias = bias, .out = out, .B = B, .M = M, .K = K,
+                                     .blocksize = blocksize, .dtype = dtype, .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                       void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemm_fused_nf4: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_fused_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
-                                    epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
+    const char *name = "fp4_hip_gemm_fused_nf4";
+    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemm_wide_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .B = B,
+                                           .M = M, .K = K, .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true,
+                                           .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int fp4_hip_gemm_lora_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                      const void *lora_B, const float *t, int64_t R, void *out, int64_t B, int64_t M, int64_t K,
                                      int blocksize, int dtype, int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemm_lora_nf4: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_lora_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
-                                    epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R);
+    const char *name = "fp4_hip_gemm_lora_nf4";
+    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemm_wide_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .B = B,
+                                           .M = M, .K = K, .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true,
+                                           .stream = static_cast<hipStream_t>(stream),
+                                           .adapter = {.given = true, .B = lora_B, .t = t, .R = R}});
 }
 
 extern "C" int fp4_hip_gemm_lora_multi_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                            const void *B_stack, const int32_t *ids, int64_t n_adapters, const float *t, int64_t R, void *out,
                                            int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemm_lora_multi_nf4: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemm_wide_nf4_entry("fp4_hip_gemm_lora_multi_nf4", true, x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
-                                    epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, B_stack, t, R, true,
-                                    ids, n_adapters);
+    const char *name = "fp4_hip_gemm_lora_multi_nf4";
+    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemm_wide_nf4_entry(
+        name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .B = B, .M = M, .K = K,
+               .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true, .stream = static_cast<hipStream_t>(stream),
+               .adapter = {.given = true, .stack = true, .B = B_stack, .t = t, .R = R, .ids = ids, .n_adapters = n_adapters}});
 }
 
 extern "C" int fp4_hip_gemm_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
                                        const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
                                        void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemm_nested_nf4";
-    if (const int rc = fp4::nested_check_args(name, "GEMM", "fp4_hip_gemm_fused_nf4", epilogue, nested_blocksize, B > 0 ? M : 0, K, nested_absmax,
-                                              code256))
-        return rc;
-    return fp4::gemm_wide_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, B, M, K, blocksize,
-                                    dtype, epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, false, nullptr, nullptr,
-                                    0, false, nullptr, 0, nested_absmax, code256, offset);
+    fp4::Nf4Call c{.x = x, .W = packed, .scales = absmax_u8, .bias = bias, .residual = residual, .out = out, .B = B, .M = M, .K = K,
+                   .blocksize = blocksize, .dtype = dtype, .fused = true, .stream = static_cast<hipStream_t>(stream),
+                   .nested_stats = {.given = true, .group = nested_absmax, .table = code256, .offset = offset}};
+    if (const int rc = fp4::nested_check_args(name, "GEMM", "fp4_hip_gemm_fused_nf4", epilogue, nested_blocksize, c)) return rc;
+    return fp4::gemm_wide_nf4_entry(name, c);
 }
 
 extern "C" int fp4_hip_gemm_lora_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
@@ -469,10 +408,10 @@ extern "C" int fp4_hip_gemm_lora_nested_nf4(const void *x, const uint8_t *packed
                                             const void *lora_B, const float *t, int64_t R, void *out, int64_t B, int64_t M, int64_t K,
                                             int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemm_lora_nested_nf4";
-    if (const int rc = fp4::nested_check_args(name, "GEMM", "fp4_hip_gemm_lora_nf4", epilogue, nested_blocksize, B > 0 ? M : 0, K, nested_absmax,
-                                              code256))
-        return rc;
-    return fp4::gemm_wide_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, B, M, K, blocksize,
-                                    dtype, epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R, false,
-                                    nullptr, 0, nested_absmax, code256, offset);
+    fp4::Nf4Call c{.x = x, .W = packed, .scales = absmax_u8, .bias = bias, .residual = residual, .out = out, .B = B, .M = M, .K = K,
+                   .blocksize = blocksize, .dtype = dtype, .fused = true, .stream = static_cast<hipStream_t>(stream),
+                   .adapter = {.given = true, .B = lora_B, .t = t, .R = R},
+                   .nested_stats = {.given = true, .group = nested_absmax, .table = code256, .offset = offset}};
+    if (const int rc = fp4::nested_check_args(name, "GEMM", "fp4_hip_gemm_lora_nf4", epilogue, nested_blocksize, c)) return rc;
+    return fp4::gemm_wide_nf4_entry(name, c);
 }

@@ -31,6 +31,7 @@
 #include <atomic>
 
 #include "gemv_common.h"
+#include "launchers.h"
 
 #ifdef FP4_EXP_STAMPS
 // Diagnostic build only (tools/exp_gemv.hip -DFP4_EXP_STAMPS): per-wave wall-clock stamps (s_memrealtime, 100 MHz) of the register-x

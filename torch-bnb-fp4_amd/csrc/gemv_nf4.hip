@@ -40,16 +40,16 @@
 // of 36 bytes streamed per 64 weights and a quarter of the resident statistics.  The table sits in LDS beside the NF4 table; the
 // code byte and the group scale are requested where the f32 scale was.  Everything after the scale is the FUSED kernel's, so the
 // result equals fp4_hip_gemv_fused_nf4 (with LORA: fp4_hip_gemv_lora_nf4) on the expanded absmax bit for bit.
+//
+// Host side: the six extern "C" entry points each fill an Nf4Call (nf4_call.h) and share one path, gemv_nf4_entry(name, call): the
+// checks, one read of the variant hook, one dispatch.  dispatch_nf4 goes from the call's form and dtype (with_nf4_form, with_dtype)
+// to the geometry (dispatch_nf4_shape) to the launch (launch_nf4, the only place that spells the kernel's flag order).
 #include <atomic>
 
-#include "gemv_common.h"
-#include "lora_nf4.h"
-#include "nested_absmax.h"
+#include "launchers.h"
+#include "nf4_call.h"
 
 namespace fp4 {
-
-int gemv_generic_table(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int64_t M, int64_t K,
-                       int blocksize, int dtype, int table, hipStream_t stream);
 
 namespace {
 
@@ -319,52 +319,34 @@ __global__ __launch_bounds__(256) void gemv_nf4_kernel(const void *__restrict__ 
 
 std::atomic<int> g_gemv_nf4_variant{-1};  // sweep hook: 0 = 16-entry table, 1 = pair table, -1 = default
 
-struct Nf4Args {
-    const void *x;
-    const uint8_t *W;
-    const float *absmax;
-    const void *bias, *residual;
-    void *out;
-    int M, K, bs_shift, mode;
-    hipStream_t stream;
-    const void *lora_B = nullptr;  // LORA instantiations only
-    const float *lora_t = nullptr;
-    int R = 0;
-    const float *nested_absmax = nullptr;  // NESTED instantiations only (absmax then points at the uint8 codes)
-    const float *nested_code = nullptr;
-    float nested_offset = 0.0f;
-    const int32_t *lora_ids = nullptr;  // MULTI instantiations only: lora_B is then the stack
-    int n_adapters = 0;
-};
-
-template <int DT, int KSPLIT, int G, int ITERS, bool FUSED, bool LORA, bool NESTED, bool MULTI>
-void launch_nf4(bool pair, const Nf4Args &a) {
+// Form: the Nf4Form of the call (nf4_call.h).  The kernel's own flag order is spelt here and nowhere else on the host.
+template <int DT, int KSPLIT, int G, int ITERS, typename Form>
+void launch_nf4(bool pair, const Nf4Call &a) {
     constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
     const dim3 grid((unsigned)((a.M + rows_per_block - 1) / rows_per_block)), block(256);
-    if (pair)
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, true, FUSED, LORA, NESTED, MULTI>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
-                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R, a.nested_absmax, a.nested_code,
-                           a.nested_offset, a.lora_ids, a.n_adapters);
-    else
-        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, false, FUSED, LORA, NESTED, MULTI>), grid, block, 0, a.stream, a.x, a.W, a.absmax,
-                           a.bias, a.out, a.M, a.K, a.bs_shift, a.residual, a.mode, a.lora_B, a.lora_t, a.R, a.nested_absmax, a.nested_code,
-                           a.nested_offset, a.lora_ids, a.n_adapters);
+    auto launch = [&](auto pair_table) {
+        hipLaunchKernelGGL((gemv_nf4_kernel<DT, KSPLIT, G, ITERS, decltype(pair_table)::value, Form::fused, Form::lora, Form::nested, Form::multi>),
+                           grid, block, 0, a.stream, a.x, a.W, static_cast<const float *>(a.scales), a.bias, a.out, (int)a.M, (int)a.K,
+                           ilog2_exact(a.blocksize), a.residual, a.mode, a.adapter.B, a.adapter.t, (int)a.adapter.R, a.nested_stats.group,
+                           a.nested_stats.table, a.nested_stats.offset, a.adapter.ids, (int)a.adapter.n_adapters);
+    };
+    pair ? launch(std::true_type{}) : launch(std::false_type{});
 }
 
-template <int DT, bool FUSED, bool LORA = false, bool NESTED = false, bool MULTI = false>
-void dispatch_nf4(bool pair, const Nf4Args &a) {
-    const int M = a.M, K = a.K;
-    const int C = K >> 5;
+template <int DT, typename Form>
+void dispatch_nf4_shape(bool pair, const Nf4Call &a) {
+    const int M = (int)a.M;
+    const int C = (int)a.K >> 5;
     const int ks = C <= 32 ? 1 : (C <= 64 ? 2 : 4);
     // the x slice is re-read by every workgroup: amortise it over up to 4 row pairs per lane while >= ~256 workgroups remain
     // (the FP4 f32 kernel's rule, gemv_fp4.hip dispatch32_regx)
     int iters = 1;
     while (iters < 4 && M / (2 * (4 / ks) * iters * 2) >= 256) iters *= 2;
-#define NF4_ITERS(KS, GG)                                                                                          \
-    switch (iters) {                                                                                               \
-        case 1: return launch_nf4<DT, KS, GG, 1, FUSED, LORA, NESTED, MULTI>(pair, a);                                           \
-        case 2: return launch_nf4<DT, KS, GG, 2, FUSED, LORA, NESTED, MULTI>(pair, a);                                           \
-        default: return launch_nf4<DT, KS, GG, 4, FUSED, LORA, NESTED, MULTI>(pair, a);                                          \
+#define NF4_ITERS(KS, GG)                                             \
+    switch (iters) {                                                  \
+        case 1: return launch_nf4<DT, KS, GG, 1, Form>(pair, a);      \
+        case 2: return launch_nf4<DT, KS, GG, 2, Form>(pair, a);      \
+        default: return launch_nf4<DT, KS, GG, 4, Form>(pair, a);     \
     }
     if (C <= 32) { NF4_ITERS(1, 1) }
     if (C <= 64) { NF4_ITERS(2, 1) }
@@ -373,25 +355,18 @@ void dispatch_nf4(bool pair, const Nf4Args &a) {
 #undef NF4_ITERS
 }
 
-}  // namespace
+// the fast path: a validated call of any form and dtype -> its kernel
+void dispatch_nf4(bool pair, const Nf4Call &a) {
+    with_nf4_form(a, [&](auto form) {
+        with_dtype<true>(a.dtype, [&](auto dt) { dispatch_nf4_shape<decltype(dt)::value, decltype(form)>(pair, a); });
+    });
+}
 
-void set_gemv_nf4_variant(int v) { g_gemv_nf4_variant.store(v, std::memory_order_relaxed); }
-
-}  // namespace fp4
-
-namespace fp4 {
-namespace {
-
-// fused = false: fp4_hip_gemv_nf4 (irregular shapes run the generic kernel).  fused = true: fp4_hip_gemv_fused_nf4 (the fast path or
-// FP4_ERR_UNSUPPORTED with nothing launched).  `name` is the entry point the messages speak for.  lora = true (with fused):
-// fp4_hip_gemv_lora_nf4, the fused form plus the adapter term.  nested_absmax != nullptr (with fused, without multi):
-// fp4_hip_gemv_nested_nf4, with lora fp4_hip_gemv_lora_nested_nf4 - `absmax` then points at the uint8 codes of the compressed statistics.  multi = true (with lora):
-// fp4_hip_gemv_lora_multi_nf4 - lora_B is a stack of n_adapters adapters and ids[0] names the one to apply.
-int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *packed, const float *absmax, const void *bias,
-                   const void *residual, void *out, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream,
-                   bool lora = false, const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0,
-                   const float *nested_absmax = nullptr, const float *nested_code = nullptr, float nested_offset = 0.0f,
-                   bool multi = false, const int32_t *ids = nullptr, int64_t n_adapters = 0) {
+// The one path of the six GEMV entry points; `name` is the entry point the messages speak for.  The plain form runs irregular
+// shapes on the generic kernel; every other form is the fast path or FP4_ERR_UNSUPPORTED with nothing launched.
+int gemv_nf4_entry(const char *name, const Nf4Call &c) {
+    const int64_t M = c.M, K = c.K;
+    const int blocksize = c.blocksize, dtype = c.dtype;
     if (M < 0 || K < 0 || (K & 1) || blocksize < 2 || (blocksize & 1)) {
         set_error("%s: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", name, (long long)M, (long long)K,
                   blocksize);
@@ -401,16 +376,16 @@ int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *p
         set_error("%s: unsupported dtype %d", name, dtype);
         return FP4_ERR_UNSUPPORTED;
     }
-    if ((mode & kModeSiluMulPairs) && (M & 1)) {
+    if (c.gated() && (M & 1)) {
         set_error("%s: the gate|up epilogue needs an even row count, got M=%lld", name, (long long)M);
         return FP4_ERR_INVALID_ARGUMENT;
     }
-    if (lora && R < 0) {
-        set_error("%s: R=%lld (need R >= 0)", name, (long long)R);
+    if (c.lora() && c.adapter.R < 0) {
+        set_error("%s: R=%lld (need R >= 0)", name, (long long)c.adapter.R);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     if (M == 0) return FP4_OK;
-    if (!out || (K > 0 && (!x || !packed || !absmax)) || (lora && (!lora_B || !lora_t))) {
+    if (!c.out || (K > 0 && (!c.x || !c.W || !c.scales)) || (c.lora() && (!c.adapter.B || !c.adapter.t))) {
         set_error("%s: null pointer", name);
         return FP4_ERR_INVALID_ARGUMENT;
     }
@@ -418,132 +393,77 @@ int gemv_nf4_entry(const char *name, bool fused, const void *x, const uint8_t *p
         set_error("%s: M=%lld K=%lld too large", name, (long long)M, (long long)K);
         return FP4_ERR_UNSUPPORTED;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int bs_shift = ilog2_exact(blocksize);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
-    const bool fast = K > 0 && (K % 32) == 0 && bs_shift >= 5 && (K % blocksize) == 0 && (align & 15u) == 0;
-    if (fused && (!fast || ((mode & kModeSiluMulPairs) && dtype == FP4_DTYPE_F32))) {
+    const uintptr_t align = reinterpret_cast<uintptr_t>(c.W) | reinterpret_cast<uintptr_t>(c.x);
+    const bool fast = K > 0 && (K % 32) == 0 && ilog2_exact(blocksize) >= 5 && (K % blocksize) == 0 && (align & 15u) == 0;
+    if (c.fused && (!fast || (c.gated() && dtype == FP4_DTYPE_F32))) {
         set_error("%s: the fused epilogue is not available for M=%lld K=%lld blocksize=%d dtype=%d epilogue=%d (needs K %% 32 == 0, a "
                   "power-of-two blocksize >= 32 that divides K, 16-byte aligned x and packed; the gate|up epilogue a 16-bit dtype); run "
                   "the plain GEMV and apply the epilogue separately",
-                  name, (long long)M, (long long)K, blocksize, dtype, (mode & kModeSiluMulPairs) ? 1 : 0);
+                  name, (long long)M, (long long)K, blocksize, dtype, c.gated() ? 1 : 0);
         return FP4_ERR_UNSUPPORTED;
     }
-    if (nested_absmax) {
-        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
-        Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s};
-        a.nested_absmax = nested_absmax, a.nested_code = nested_code, a.nested_offset = nested_offset;
-        if (lora) {
-            if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
-            a.lora_B = lora_B, a.lora_t = lora_t, a.R = (int)R;
-            switch (dtype) {
-                case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, true, true>(pair, a); break;
-                case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, true, true>(pair, a); break;
-                default: dispatch_nf4<FP4_DTYPE_F32, true, true, true>(pair, a); break;
-            }
-            return check_launch(name);
-        }
-        switch (dtype) {
-            case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, false, true>(pair, a); break;
-            case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, false, true>(pair, a); break;
-            default: dispatch_nf4<FP4_DTYPE_F32, true, false, true>(pair, a); break;
-        }
-        return check_launch(name);
-    }
-    if (multi) {  // lora_B is the stack
-        if (const int rc = lora_check_stack(name, lora_B, ids, n_adapters, lora_t, R)) return rc;
-        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
-        Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s, lora_B, lora_t, (int)R};
-        a.lora_ids = ids, a.n_adapters = (int)n_adapters;
-        switch (dtype) {
-            case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, true, false, true>(pair, a); break;
-            case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, true, false, true>(pair, a); break;
-            default: dispatch_nf4<FP4_DTYPE_F32, true, true, false, true>(pair, a); break;
-        }
-        return check_launch(name);
-    }
-    if (lora) {
-        if (const int rc = lora_check_adapter(name, lora_B, lora_t, R)) return rc;
-        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
-        const Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s, lora_B, lora_t, (int)R};
-        switch (dtype) {
-            case FP4_DTYPE_F16: dispatch_nf4<FP4_DTYPE_F16, true, true>(pair, a); break;
-            case FP4_DTYPE_BF16: dispatch_nf4<FP4_DTYPE_BF16, true, true>(pair, a); break;
-            default: dispatch_nf4<FP4_DTYPE_F32, true, true>(pair, a); break;
-        }
-        return check_launch(name);
-    }
-    if (fast) {
-        const bool pair = g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1;
-        const Nf4Args a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s};
-        switch (dtype) {
-            case FP4_DTYPE_F16:
-                fused ? dispatch_nf4<FP4_DTYPE_F16, true>(pair, a) : dispatch_nf4<FP4_DTYPE_F16, false>(pair, a);
-                break;
-            case FP4_DTYPE_BF16:
-                fused ? dispatch_nf4<FP4_DTYPE_BF16, true>(pair, a) : dispatch_nf4<FP4_DTYPE_BF16, false>(pair, a);
-                break;
-            default:
-                fused ? dispatch_nf4<FP4_DTYPE_F32, true>(pair, a) : dispatch_nf4<FP4_DTYPE_F32, false>(pair, a);
-                break;
-        }
-    } else {
-        gemv_generic_table(x, packed, absmax, bias, out, M, K, blocksize, dtype, FP4_TABLE_NF4, s);
-    }
+    if (const int rc = nf4_check_adapter(name, c)) return rc;
+    if (fast)
+        dispatch_nf4(g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1, c);
+    else  // the plain form only
+        gemv_generic_table(c.x, c.W, static_cast<const float *>(c.scales), c.bias, c.out, M, K, blocksize, dtype, FP4_TABLE_NF4, c.stream);
     return check_launch(name);
 }
 
 }  // namespace
+
+void set_gemv_nf4_variant(int v) { g_gemv_nf4_variant.store(v, std::memory_order_relaxed); }
+
 }  // namespace fp4
 
 extern "C" int fp4_hip_gemv_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out, int64_t M,
                                 int64_t K, int blocksize, int dtype, void *stream) {
-    return fp4::gemv_nf4_entry("fp4_hip_gemv_nf4", false, x, packed, absmax, bias, nullptr, out, M, K, blocksize, dtype, 0, stream);
+    return fp4::gemv_nf4_entry("fp4_hip_gemv_nf4", {.x = x, .W = packed, .scales = absmax, .bias = bias, .out = out, .M = M, .K = K,
+                                                    .blocksize = blocksize, .dtype = dtype, .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int fp4_hip_gemv_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                       void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemv_fused_nf4: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemv_nf4_entry("fp4_hip_gemv_fused_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
-                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
+    const char *name = "fp4_hip_gemv_fused_nf4";
+    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemv_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
+                                      .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true,
+                                      .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int fp4_hip_gemv_lora_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                      const void *lora_B, const float *t, int64_t R, void *out, int64_t M, int64_t K, int blocksize,
                                      int dtype, int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemv_lora_nf4: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemv_nf4_entry("fp4_hip_gemv_lora_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
-                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R);
+    const char *name = "fp4_hip_gemv_lora_nf4";
+    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemv_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
+                                      .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true, .stream = static_cast<hipStream_t>(stream),
+                                      .adapter = {.given = true, .B = lora_B, .t = t, .R = R}});
 }
 
 extern "C" int fp4_hip_gemv_lora_multi_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                            const void *B_stack, const int32_t *ids, int64_t n_adapters, const float *t, int64_t R, void *out,
                                            int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemv_lora_multi_nf4: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemv_nf4_entry("fp4_hip_gemv_lora_multi_nf4", true, x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
-                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, B_stack, t, R, nullptr,
-                               nullptr, 0.0f, true, ids, n_adapters);
+    const char *name = "fp4_hip_gemv_lora_multi_nf4";
+    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemv_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
+                                      .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true, .stream = static_cast<hipStream_t>(stream),
+                                      .adapter = {.given = true, .stack = true, .B = B_stack, .t = t, .R = R, .ids = ids, .n_adapters = n_adapters}});
 }
 
 extern "C" int fp4_hip_gemv_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
                                        const float *code256, float offset, int nested_blocksize, const void *bias, const void *residual,
                                        void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemv_nested_nf4";
-    if (const int rc = fp4::nested_check_args(name, "GEMV", "fp4_hip_gemv_fused_nf4", epilogue, nested_blocksize, M, K, nested_absmax, code256))
-        return rc;
+    fp4::Nf4Call c{.x = x, .W = packed, .scales = absmax_u8, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
+                   .blocksize = blocksize, .dtype = dtype, .fused = true, .stream = static_cast<hipStream_t>(stream),
+                   .nested_stats = {.given = true, .group = nested_absmax, .table = code256, .offset = offset}};
+    if (const int rc = fp4::nested_check_args(name, "GEMV", "fp4_hip_gemv_fused_nf4", epilogue, nested_blocksize, c)) return rc;
     // K == 0 never reaches a kernel: the fused form refuses it (not the fast path) before the statistics are looked at
-    return fp4::gemv_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, M, K, blocksize, dtype,
-                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, false, nullptr, nullptr, 0,
-                               nested_absmax, code256, offset);
+    return fp4::gemv_nf4_entry(name, c);
 }
 
 extern "C" int fp4_hip_gemv_lora_nested_nf4(const void *x, const uint8_t *packed, const uint8_t *absmax_u8, const float *nested_absmax,
@@ -551,9 +471,10 @@ extern "C" int fp4_hip_gemv_lora_nested_nf4(const void *x, const uint8_t *packed
                                             const void *lora_B, const float *t, int64_t R, void *out, int64_t M, int64_t K, int blocksize,
                                             int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemv_lora_nested_nf4";
-    if (const int rc = fp4::nested_check_args(name, "GEMV", "fp4_hip_gemv_lora_nf4", epilogue, nested_blocksize, M, K, nested_absmax, code256))
-        return rc;
-    return fp4::gemv_nf4_entry(name, true, x, packed, reinterpret_cast<const float *>(absmax_u8), bias, residual, out, M, K, blocksize, dtype,
-                               epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream, true, lora_B, t, R, nested_absmax,
-                               code256, offset);
+    fp4::Nf4Call c{.x = x, .W = packed, .scales = absmax_u8, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
+                   .blocksize = blocksize, .dtype = dtype, .fused = true, .stream = static_cast<hipStream_t>(stream),
+                   .adapter = {.given = true, .B = lora_B, .t = t, .R = R},
+                   .nested_stats = {.given = true, .group = nested_absmax, .table = code256, .offset = offset}};
+    if (const int rc = fp4::nested_check_args(name, "GEMV", "fp4_hip_gemv_lora_nf4", epilogue, nested_blocksize, c)) return rc;
+    return fp4::gemv_nf4_entry(name, c);
 }

@@ -1,25 +1,20 @@
 // Host functions that one translation unit defines and another calls.  The calling file includes this header, and so does the
-// defining file among the matrix-core sources (gemm_*_fp4.hip, gemm_*_nf4.hip), so one declaration is read beside the definition
-// and beside every call instead of a hand-written copy at the point of use.  The four sweep hooks of the GEMV, dequant and quantiser sources are declared here
-// for capi.hip only; a file that defines one should include this header the next time it is edited.
+// defining file among the matrix-core and GEMV sources (gemm_*_fp4.hip, gemm_*_nf4.hip, gemv_*.hip), so one declaration is read beside
+// the definition and beside every call instead of a hand-written copy at the point of use.  The sweep hooks of the dequant and
+// quantiser sources are declared here for capi.hip only; a file that defines one should include this header the next time it is edited.
 #pragma once
 
 #include "fp4_common.h"
 
 namespace fp4 {
 
-// gemm_small_nf4.hip, for the fused entry points of gemm_wide_nf4.hip (which validate): 1..16 rows, K % 512 == 0.  Launch only.
-void gemm_small_nf4_fused_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                 void *out, int B, int M, int K, int mode, hipStream_t stream);
-void gemm_small_nf4_lora_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                const void *lora_B, const float *lora_t, int R, void *out, int B, int M, int K, int mode,
-                                hipStream_t stream);
-void gemm_small_nf4_lora_multi_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual,
-                                      const void *B_stack, const int32_t *ids, int n_adapters, const float *lora_t, int R, void *out, int B,
-                                      int M, int K, int mode, hipStream_t stream);
-void gemm_small_nf4_nested_launch(int dtype, const void *x, const uint8_t *W, const uint8_t *absmax_u8, const float *nested_absmax,
-                                  const float *nested_code, float nested_offset, const void *bias, const void *residual, const void *lora_B,
-                                  const float *lora_t, int R, void *out, int B, int M, int K, int mode, hipStream_t stream);
+// gemm_small_nf4.hip, for the entry points of gemm_wide_nf4.hip (which validate): 1..16 rows, K % 512 == 0, any form.  Launch only.
+struct Nf4Call;  // nf4_call.h
+void gemm_small_nf4_launch(const Nf4Call &call);
+
+// gemv_fp4.hip, for the plain NF4 GEMV's irregular shapes (gemv_nf4.hip): the generic kernel with `table` as its code
+int gemv_generic_table(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int64_t M, int64_t K,
+                       int blocksize, int dtype, int table, hipStream_t stream);
 
 // gemm_wide_fp4.hip, gemm_splitk_fp4.hip, for gemm_small_fp4.hip: FP4_OK after the launch, -1 where the shape is not theirs
 int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,

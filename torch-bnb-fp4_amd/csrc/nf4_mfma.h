@@ -1,5 +1,6 @@
-// What the two NF4 matrix-core kernels (gemm_small_nf4.hip: 1..16 activation rows, gemm_wide_nf4.hip: up to 128) share: the hi / lo
-// decode, the gate|up store of the fused epilogues, and on the host the argument struct, the dtype fan-out and the argument check.
+// What the two NF4 matrix-core kernels (gemm_small_nf4.hip: 1..16 activation rows, gemm_wide_nf4.hip: up to 128) share on the device:
+// the hi / lo decode and the gate|up store of the fused epilogues.  Their host side - the call descriptor, the form and dtype fan-out
+// and the argument check - is nf4_call.h, shared with the GEMV, which needs none of what follows.
 //
 // The FP4 kernels build 12*|code| in 8 bits with v_perm; the 16 NF4 codes are arbitrary f32 values, exact in neither bf16 nor fp16,
 // and T(code) alone misses the project's error bar (|err| <= 1e-5 * sum|x*w| beside the final rounding) by up to 31.6x in bf16 and
@@ -16,10 +17,8 @@
 // before the block's absmax is applied.  bf16 has f32's exponent range: both instructions share one accumulator.
 #pragma once
 
-#include <type_traits>
-
-#include "lora_nf4.h"
 #include "mfma_common.h"
+#include "nf4_call.h"
 
 namespace fp4 {
 namespace {
@@ -100,67 +99,6 @@ __device__ __forceinline__ void store_nf4_pair_multi(uint16_t *out, const uint16
         store_nf4_pair<DT, true>(out, bias, residual, slice, lora_t, R, n, row, M, t, u);
     else
         store_nf4_pair<DT, false>(out, bias, residual, nullptr, lora_t, R, n, row, M, t, u);
-}
-
-// ---- host side ------------------------------------------------------------------------------------------------------------------
-
-struct Nf4GemmArgs {
-    const void *x;
-    const uint8_t *W;
-    const float *absmax;
-    const void *bias, *residual;
-    void *out;
-    int B, M, K, mode;
-    hipStream_t stream;
-    const void *lora_B = nullptr;  // LORA instantiations only
-    const float *lora_t = nullptr;
-    int R = 0;
-    const int32_t *lora_ids = nullptr;  // MULTI instantiations only: lora_B is then the stack
-    int n_adapters = 0;
-    const float *nested_absmax = nullptr;  // NESTED instantiations only (absmax then points at the uint8 codes)
-    const float *nested_code = nullptr;
-    float nested_offset = 0.0f;
-};
-
-// runtime dtype (validated: fp16 or bf16) -> template argument: f(std::integral_constant<int, FP4_DTYPE_F16 or FP4_DTYPE_BF16>{})
-template <typename F>
-inline void with_dtype(int dtype, F &&f) {
-    if (dtype == FP4_DTYPE_F16)
-        f(std::integral_constant<int, FP4_DTYPE_F16>{});
-    else
-        f(std::integral_constant<int, FP4_DTYPE_BF16>{});
-}
-
-// The argument check of the NF4 matrix-core entry points: FP4_OK, or the status to return with the message set.  An empty problem
-// (M == 0 or B == 0) is FP4_OK whatever the pointers are: the caller returns on it before it launches.  `adapter`: the entry point
-// takes lora_B / lora_t / R (their own checks are lora_check_adapter's).
-inline int nf4_check_args(const char *name, int max_rows, int k_multiple, const void *x, const uint8_t *packed, const float *absmax,
-                          const void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode, bool adapter = false,
-                          const void *lora_B = nullptr, const float *lora_t = nullptr, int64_t R = 0) {
-    if (B < 0 || M < 0 || K <= 0 || blocksize <= 0 || (adapter && R < 0)) {
-        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d (need B, M >= 0, K, blocksize > 0)", name, (long long)B, (long long)M,
-                  (long long)K, blocksize);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    if ((mode & kModeSiluMulPairs) && (M & 1)) {
-        set_error("%s: the gate|up epilogue needs an even row count, got M=%lld", name, (long long)M);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
-    // the kernels address with 64-bit element offsets: M * K may pass 2^32; the bounds keep the int row / block arithmetic in range
-    if (B > max_rows || blocksize != 64 || (K % k_multiple) != 0 || (dtype != FP4_DTYPE_F16 && dtype != FP4_DTYPE_BF16) ||
-        (align & 15u) != 0 || M > (int64_t(1) << 30) || K > (int64_t(1) << 24)) {
-        set_error("%s: B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered (1..%d rows, blocksize 64, "
-                  "K %% %d == 0, fp16 / bf16, 16-byte aligned x and packed); use dequant + GEMM",
-                  name, (long long)B, (long long)M, (long long)K, blocksize, dtype, max_rows, k_multiple);
-        return FP4_ERR_UNSUPPORTED;
-    }
-    if (M == 0 || B == 0) return FP4_OK;
-    if (!x || !packed || !absmax || !out || (adapter && (!lora_B || !lora_t))) {
-        set_error("%s: null pointer", name);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return FP4_OK;
 }
 
 }  // namespace

@@ -539,49 +539,21 @@ torch::Tensor gemm_wide_nf4(torch::Tensor A, torch::Tensor B, torch::Tensor absm
     return gemm_nf4_impl({"gemm_wide_nf4", 128}, fp4_hip_gemm_wide_nf4, A, B, absmax, blocksize, Bshape, bias);
 }
 
-// the operands of the LoRA forms: lora_B [m, R] of the activation dtype over the weight's rows, t [rows, R] float32 (lora_down); -> R
-int64_t check_lora(const char *op, const torch::Tensor &A, const WeightCall &w, const torch::Tensor &lora_B, const torch::Tensor &t) {
-    check_gpu_contiguous(lora_B, "lora_B", op);
+// the operands of the LoRA forms: lora_B [m, R] of the activation dtype over the weight's rows - with `stack` B_stack [n_adapters, m, R] -
+// and t [rows, R] float32 (lora_down's output, with `stack` lora_down_multi's); -> R
+int64_t check_lora(const char *op, const torch::Tensor &A, const WeightCall &w, const torch::Tensor &lora_B, const torch::Tensor &t,
+                   bool stack = false) {
+    const char *name = stack ? "B_stack" : "lora_B";
+    const int64_t lead = stack ? 1 : 0;  // the dimensions ahead of [m, R]
+    check_gpu_contiguous(lora_B, name, op);
     check_gpu_contiguous(t, "t", op);
-    TORCH_CHECK(lora_B.dim() == 2 && lora_B.size(0) == w.m && lora_B.scalar_type() == A.scalar_type() && lora_B.device() == A.device(), op,
-                ": lora_B must be a [", w.m, ", R] tensor of the activation dtype on the activation's device");
-    const int64_t R = lora_B.size(1);
+    TORCH_CHECK(lora_B.dim() == 2 + lead && (!stack || lora_B.size(0) >= 1) && lora_B.size(lead) == w.m &&
+                    lora_B.scalar_type() == A.scalar_type() && lora_B.device() == A.device(),
+                op, ": ", name, " must be a [", stack ? "n_adapters, " : "", w.m, ", R] tensor of the activation dtype on the activation's device");
+    const int64_t R = lora_B.size(lead + 1);
     TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.numel() == w.rows * R && t.device() == A.device(), op, ": t must hold ", w.rows * R,
-                " float32 elements (lora_down's output) on the activation's device");
+                " float32 elements (", stack ? "lora_down_multi" : "lora_down", "'s output) on the activation's device");
     return R;
-}
-
-// the NF4 twins of gemv_fp4_fused / gemm_small_fp4_fused (fp4_hip_gemv_fused_nf4 / fp4_hip_gemm_fused_nf4) and, given lora_B and
-// lora_t, their LoRA forms (fp4_hip_gemv_lora_nf4 / fp4_hip_gemm_lora_nf4)
-torch::Tensor nf4_fused_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
-                             int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
-                             const c10::optional<torch::Tensor> &residual, int epilogue, const torch::Tensor *lora_B = nullptr,
-                             const torch::Tensor *lora_t = nullptr) {
-    WeightCall w = weight_op({op, gemv ? 1 : 128}, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue);
-    const int64_t R = lora_B ? check_lora(op, A, w, *lora_B, *lora_t) : 0;
-    c10::DeviceGuard guard(A.device());
-    if (lora_B && gemv)
-        check_status(fp4_hip_gemv_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, lora_B->data_ptr(),
-                                           lora_t->data_ptr<float>(), R, w.out.data_ptr(), w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    else if (lora_B)
-        check_status(fp4_hip_gemm_lora_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, lora_B->data_ptr(),
-                                           lora_t->data_ptr<float>(), R, w.out.data_ptr(), w.rows, w.m, w.k, blocksize, w.dt, epilogue,
-                                           current_stream(A)));
-    else if (gemv)
-        check_status(fp4_hip_gemv_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, w.out.data_ptr(),
-                                            w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    else
-        check_status(fp4_hip_gemm_fused_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, w.out.data_ptr(),
-                                            w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    return std::move(w.out);
-}
-torch::Tensor gemv_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                             c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
-    return nf4_fused_impl("gemv_nf4_fused", true, A, B, absmax, blocksize, Bshape, bias, residual, epilogue);
-}
-torch::Tensor gemm_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                             c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
-    return nf4_fused_impl("gemm_nf4_fused", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue);
 }
 
 // LoRA adapters beside an NF4 weight.  lora_down: t = scale * (x @ A^T) as float32 [rows, R] (fp4_hip_lora_down; x [.., K] with
@@ -604,17 +576,6 @@ torch::Tensor lora_down(torch::Tensor x, torch::Tensor A, torch::Tensor scale) {
     check_status(fp4_hip_lora_down(x.data_ptr(), A.data_ptr(), scale.data_ptr<float>(), t.data_ptr<float>(), rows, R, k, dt, current_stream(x)));
     return t;
 }
-torch::Tensor gemv_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                            c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue, torch::Tensor lora_B,
-                            torch::Tensor t) {
-    return nf4_fused_impl("gemv_nf4_lora", true, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, &lora_B, &t);
-}
-torch::Tensor gemm_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                            c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue, torch::Tensor lora_B,
-                            torch::Tensor t) {
-    return nf4_fused_impl("gemm_nf4_lora", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, &lora_B, &t);
-}
-
 // Several adapters in one batch, selected per activation row on the device.  ids: int32, contiguous, on the activation's device, at
 // least `rows` elements (the first `rows` are used; it is never read on the host, so a captured step follows an in-place rewrite).
 void check_ids(const char *op, const torch::Tensor &ids, const torch::Tensor &x, int64_t rows) {
@@ -645,44 +606,6 @@ torch::Tensor lora_down_multi(torch::Tensor x, torch::Tensor A_stack, torch::Ten
                                          t.data_ptr<float>(), rows, n, R, k, dt, current_stream(x)));
     return t;
 }
-// gemv_nf4_lora_multi / gemm_nf4_lora_multi: gemv_nf4_lora / gemm_nf4_lora with B_stack [n, m, R] and the adapter of row b read from
-// ids[b] on the device; a row without one is the plain fused op's (fp4_hip_gemv_lora_multi_nf4 / fp4_hip_gemm_lora_multi_nf4).
-torch::Tensor nf4_lora_multi_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax,
-                                  int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
-                                  const c10::optional<torch::Tensor> &residual, int epilogue, const torch::Tensor &B_stack,
-                                  const torch::Tensor &ids, const torch::Tensor &t) {
-    WeightCall w = weight_op({op, gemv ? 1 : 128}, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue);
-    check_gpu_contiguous(B_stack, "B_stack", op);
-    check_gpu_contiguous(t, "t", op);
-    TORCH_CHECK(B_stack.dim() == 3 && B_stack.size(0) >= 1 && B_stack.size(1) == w.m && B_stack.scalar_type() == A.scalar_type() &&
-                    B_stack.device() == A.device(),
-                op, ": B_stack must be a [n_adapters, ", w.m, ", R] tensor of the activation dtype on the activation's device");
-    const int64_t n = B_stack.size(0), R = B_stack.size(2);
-    TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.numel() == w.rows * R && t.device() == A.device(), op, ": t must hold ", w.rows * R,
-                " float32 elements (lora_down_multi's output) on the activation's device");
-    check_ids(op, ids, A, w.rows);
-    c10::DeviceGuard guard(A.device());
-    if (gemv)
-        check_status(fp4_hip_gemv_lora_multi_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr,
-                                                 B_stack.data_ptr(), ids.data_ptr<int32_t>(), n, t.data_ptr<float>(), R, w.out.data_ptr(), w.m,
-                                                 w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    else
-        check_status(fp4_hip_gemm_lora_multi_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr,
-                                                 B_stack.data_ptr(), ids.data_ptr<int32_t>(), n, t.data_ptr<float>(), R, w.out.data_ptr(),
-                                                 w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    return std::move(w.out);
-}
-torch::Tensor gemv_nf4_lora_multi(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
-                                  torch::Tensor B_stack, torch::Tensor ids, torch::Tensor t) {
-    return nf4_lora_multi_impl("gemv_nf4_lora_multi", true, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, B_stack, ids, t);
-}
-torch::Tensor gemm_nf4_lora_multi(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
-                                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
-                                  torch::Tensor B_stack, torch::Tensor ids, torch::Tensor t) {
-    return nf4_lora_multi_impl("gemm_nf4_lora_multi", false, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, B_stack, ids, t);
-}
-
 // ---- nested (double-quantised) absmax: bitsandbytes' compress_statistics ------------------------------------------------------------
 // absmax_u8 uint8 [nb], nested_absmax float32 [ceil(nb / nested_blocksize)], code float32 [256], offset a Python float (passed to the
 // kernel by value: no device read of a host scalar, no sync).
@@ -728,70 +651,142 @@ std::tuple<torch::Tensor, torch::Tensor> absmax_nest(torch::Tensor absmax, doubl
     return {q, nested};
 }
 
-// gemv_nf4_fused reading the compressed statistics (fp4_hip_gemv_nested_nf4): A [1, K] / [1, 1, K] -> [.., m] or [.., m / 2]
-torch::Tensor gemv_nf4_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
-                              double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
-                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
-    const char *op = "gemv_nf4_nested";
-    TORCH_CHECK(blocksize > 0, op, ": blocksize must be positive");
-    WeightCall w = weight_op({op, 1}, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue);
-    check_nested(op, absmax_u8, nested_absmax, code, nested_blocksize, (w.m * w.k + blocksize - 1) / blocksize);
-    check_on_device(op, "absmax_u8", absmax_u8, A);
+// ---- the NF4 decode ops: one wrapper for the ten C entry points -----------------------------------------------------------------------
+// gemv_nf4_fused / gemm_nf4_fused are the NF4 twins of gemv_fp4_fused / gemm_small_fp4_fused (fp4_hip_gemv_fused_nf4 / fp4_hip_gemm_fused_nf4).
+// An op may add ONE of: an adapter (*_lora: lora_B @ t added to the f32 row sums before the rounding) or a stack of adapters
+// (*_lora_multi: B_stack [n, m, R], the adapter of row b read from ids[b] on the device; a row without one is the plain fused op's),
+// and, without a stack, read the statistics compressed (*_nested, *_lora_nested: the un-nested op's shapes with absmax_u8,
+// nested_absmax, code, offset, nested_blocksize in absmax's place).  One allocation each.
+struct LoraOperands {
+    const torch::Tensor &lora_B, &t;
+};
+struct StackOperands {
+    const torch::Tensor &B_stack, &ids, &t;
+};
+struct NestedOperands {
+    const torch::Tensor &absmax_u8, &nested_absmax, &code;
+    double offset;
+    int64_t nested_blocksize;
+};
+
+// absmax: the float32 scales, or nullptr with `nested`
+torch::Tensor nf4_decode_op(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor *absmax, int blocksize,
+                            const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
+                            const c10::optional<torch::Tensor> &residual, int epilogue, const LoraOperands *adapter, const StackOperands *stack,
+                            const NestedOperands *nested) {
+    if (nested) TORCH_CHECK(blocksize > 0, op, ": blocksize must be positive");
+    WeightCall w = weight_op({op, gemv ? 1 : 128}, A, B, absmax, blocksize, Bshape, bias, residual, epilogue);
+    if (nested) {
+        check_nested(op, nested->absmax_u8, nested->nested_absmax, nested->code, nested->nested_blocksize, (w.m * w.k + blocksize - 1) / blocksize);
+        check_on_device(op, "absmax_u8", nested->absmax_u8, A);
+    }
+    int64_t R = 0;
+    if (adapter) R = check_lora(op, A, w, adapter->lora_B, adapter->t);
+    if (stack) {
+        R = check_lora(op, A, w, stack->B_stack, stack->t, true);
+        check_ids(op, stack->ids, A, w.rows);
+    }
     c10::DeviceGuard guard(A.device());
-    check_status(fp4_hip_gemv_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(), nested_absmax.data_ptr<float>(),
-                                         code.data_ptr<float>(), (float)offset, (int)nested_blocksize, w.bias_ptr, w.res_ptr, w.out.data_ptr(),
-                                         w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    const void *x = A.data_ptr();
+    const uint8_t *W = B.data_ptr<uint8_t>();
+    void *out = w.out.data_ptr(), *s = current_stream(A);
+    int rc;
+    if (nested) {
+        const uint8_t *q = nested->absmax_u8.data_ptr<uint8_t>();
+        const float *group = nested->nested_absmax.data_ptr<float>(), *table = nested->code.data_ptr<float>(), offset = (float)nested->offset;
+        const int g = (int)nested->nested_blocksize;
+        if (!adapter)
+            rc = gemv ? fp4_hip_gemv_nested_nf4(x, W, q, group, table, offset, g, w.bias_ptr, w.res_ptr, out, w.m, w.k, blocksize, w.dt, epilogue, s)
+                      : fp4_hip_gemm_nested_nf4(x, W, q, group, table, offset, g, w.bias_ptr, w.res_ptr, out, w.rows, w.m, w.k, blocksize, w.dt,
+                                                epilogue, s);
+        else
+            rc = gemv ? fp4_hip_gemv_lora_nested_nf4(x, W, q, group, table, offset, g, w.bias_ptr, w.res_ptr, adapter->lora_B.data_ptr(),
+                                                     adapter->t.data_ptr<float>(), R, out, w.m, w.k, blocksize, w.dt, epilogue, s)
+                      : fp4_hip_gemm_lora_nested_nf4(x, W, q, group, table, offset, g, w.bias_ptr, w.res_ptr, adapter->lora_B.data_ptr(),
+                                                     adapter->t.data_ptr<float>(), R, out, w.rows, w.m, w.k, blocksize, w.dt, epilogue, s);
+    } else {
+        const float *am = absmax->data_ptr<float>();
+        if (stack) {
+            const void *Bs = stack->B_stack.data_ptr();
+            const int32_t *ids = stack->ids.data_ptr<int32_t>();
+            const int64_t n = stack->B_stack.size(0);
+            const float *t = stack->t.data_ptr<float>();
+            rc = gemv ? fp4_hip_gemv_lora_multi_nf4(x, W, am, w.bias_ptr, w.res_ptr, Bs, ids, n, t, R, out, w.m, w.k, blocksize, w.dt, epilogue, s)
+                      : fp4_hip_gemm_lora_multi_nf4(x, W, am, w.bias_ptr, w.res_ptr, Bs, ids, n, t, R, out, w.rows, w.m, w.k, blocksize, w.dt,
+                                                    epilogue, s);
+        } else if (adapter) {
+            const void *lb = adapter->lora_B.data_ptr();
+            const float *t = adapter->t.data_ptr<float>();
+            rc = gemv ? fp4_hip_gemv_lora_nf4(x, W, am, w.bias_ptr, w.res_ptr, lb, t, R, out, w.m, w.k, blocksize, w.dt, epilogue, s)
+                      : fp4_hip_gemm_lora_nf4(x, W, am, w.bias_ptr, w.res_ptr, lb, t, R, out, w.rows, w.m, w.k, blocksize, w.dt, epilogue, s);
+        } else {
+            rc = gemv ? fp4_hip_gemv_fused_nf4(x, W, am, w.bias_ptr, w.res_ptr, out, w.m, w.k, blocksize, w.dt, epilogue, s)
+                      : fp4_hip_gemm_fused_nf4(x, W, am, w.bias_ptr, w.res_ptr, out, w.rows, w.m, w.k, blocksize, w.dt, epilogue, s);
+        }
+    }
+    check_status(rc);
     return std::move(w.out);
 }
 
-// gemm_nf4_fused, gemv_nf4_lora and gemm_nf4_lora reading the compressed statistics (fp4_hip_gemm_nested_nf4,
-// fp4_hip_gemv_lora_nested_nf4, fp4_hip_gemm_lora_nested_nf4): the un-nested op's shapes, with the statistics in absmax's place
-torch::Tensor nf4_nested_impl(const char *op, bool gemv, const torch::Tensor &A, const torch::Tensor &B, const torch::Tensor &absmax_u8,
-                              const torch::Tensor &nested_absmax, const torch::Tensor &code, double offset, int64_t nested_blocksize,
-                              int blocksize, const std::vector<uint32_t> &Bshape, const c10::optional<torch::Tensor> &bias,
-                              const c10::optional<torch::Tensor> &residual, int epilogue, const torch::Tensor *lora_B = nullptr,
-                              const torch::Tensor *lora_t = nullptr) {
-    TORCH_CHECK(blocksize > 0, op, ": blocksize must be positive");
-    WeightCall w = weight_op({op, gemv ? 1 : 128}, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue);
-    check_nested(op, absmax_u8, nested_absmax, code, nested_blocksize, (w.m * w.k + blocksize - 1) / blocksize);
-    check_on_device(op, "absmax_u8", absmax_u8, A);
-    const int64_t R = lora_B ? check_lora(op, A, w, *lora_B, *lora_t) : 0;
-    c10::DeviceGuard guard(A.device());
-    if (!lora_B)
-        check_status(fp4_hip_gemm_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(), nested_absmax.data_ptr<float>(),
-                                             code.data_ptr<float>(), (float)offset, (int)nested_blocksize, w.bias_ptr, w.res_ptr,
-                                             w.out.data_ptr(), w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    else if (gemv)
-        check_status(fp4_hip_gemv_lora_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(),
-                                                  nested_absmax.data_ptr<float>(), code.data_ptr<float>(), (float)offset, (int)nested_blocksize,
-                                                  w.bias_ptr, w.res_ptr, lora_B->data_ptr(), lora_t->data_ptr<float>(), R, w.out.data_ptr(), w.m,
-                                                  w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    else
-        check_status(fp4_hip_gemm_lora_nested_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax_u8.data_ptr<uint8_t>(),
-                                                  nested_absmax.data_ptr<float>(), code.data_ptr<float>(), (float)offset, (int)nested_blocksize,
-                                                  w.bias_ptr, w.res_ptr, lora_B->data_ptr(), lora_t->data_ptr<float>(), R, w.out.data_ptr(),
-                                                  w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
-    return std::move(w.out);
+torch::Tensor gemv_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                             c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    return nf4_decode_op("gemv_nf4_fused", true, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue, nullptr, nullptr, nullptr);
+}
+torch::Tensor gemm_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                             c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    return nf4_decode_op("gemm_nf4_fused", false, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue, nullptr, nullptr, nullptr);
+}
+torch::Tensor gemv_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                            c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue, torch::Tensor lora_B,
+                            torch::Tensor t) {
+    const LoraOperands adapter{lora_B, t};
+    return nf4_decode_op("gemv_nf4_lora", true, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue, &adapter, nullptr, nullptr);
+}
+torch::Tensor gemm_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                            c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue, torch::Tensor lora_B,
+                            torch::Tensor t) {
+    const LoraOperands adapter{lora_B, t};
+    return nf4_decode_op("gemm_nf4_lora", false, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue, &adapter, nullptr, nullptr);
+}
+torch::Tensor gemv_nf4_lora_multi(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
+                                  torch::Tensor B_stack, torch::Tensor ids, torch::Tensor t) {
+    const StackOperands stack{B_stack, ids, t};
+    return nf4_decode_op("gemv_nf4_lora_multi", true, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue, nullptr, &stack, nullptr);
+}
+torch::Tensor gemm_nf4_lora_multi(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                                  c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
+                                  torch::Tensor B_stack, torch::Tensor ids, torch::Tensor t) {
+    const StackOperands stack{B_stack, ids, t};
+    return nf4_decode_op("gemm_nf4_lora_multi", false, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue, nullptr, &stack, nullptr);
+}
+torch::Tensor gemv_nf4_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
+                              double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
+                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    const NestedOperands nested{absmax_u8, nested_absmax, code, offset, nested_blocksize};
+    return nf4_decode_op("gemv_nf4_nested", true, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue, nullptr, nullptr, &nested);
 }
 torch::Tensor gemm_nf4_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
                               double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
                               c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
-    return nf4_nested_impl("gemm_nf4_nested", false, A, B, absmax_u8, nested_absmax, code, offset, nested_blocksize, blocksize, Bshape, bias,
-                           residual, epilogue);
+    const NestedOperands nested{absmax_u8, nested_absmax, code, offset, nested_blocksize};
+    return nf4_decode_op("gemm_nf4_nested", false, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue, nullptr, nullptr, &nested);
 }
 torch::Tensor gemv_nf4_lora_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
                                    double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
                                    c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
                                    torch::Tensor lora_B, torch::Tensor t) {
-    return nf4_nested_impl("gemv_nf4_lora_nested", true, A, B, absmax_u8, nested_absmax, code, offset, nested_blocksize, blocksize, Bshape, bias,
-                           residual, epilogue, &lora_B, &t);
+    const NestedOperands nested{absmax_u8, nested_absmax, code, offset, nested_blocksize};
+    const LoraOperands adapter{lora_B, t};
+    return nf4_decode_op("gemv_nf4_lora_nested", true, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue, &adapter, nullptr, &nested);
 }
 torch::Tensor gemm_nf4_lora_nested(torch::Tensor A, torch::Tensor B, torch::Tensor absmax_u8, torch::Tensor nested_absmax, torch::Tensor code,
                                    double offset, int64_t nested_blocksize, int blocksize, std::vector<uint32_t> Bshape,
                                    c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue,
                                    torch::Tensor lora_B, torch::Tensor t) {
-    return nf4_nested_impl("gemm_nf4_lora_nested", false, A, B, absmax_u8, nested_absmax, code, offset, nested_blocksize, blocksize, Bshape, bias,
-                           residual, epilogue, &lora_B, &t);
+    const NestedOperands nested{absmax_u8, nested_absmax, code, offset, nested_blocksize};
+    const LoraOperands adapter{lora_B, t};
+    return nf4_decode_op("gemm_nf4_lora_nested", false, A, B, nullptr, blocksize, Bshape, bias, residual, epilogue, &adapter, nullptr, &nested);
 }
 
 // unnest into a temporary from the caching allocator (stream-ordered: no sync, capturable), then qlinear_nf4 / qlinear_nf4_bias
