@@ -110,6 +110,22 @@ FP4_HIP_API int fp4_hip_gemv(const void *x, const uint8_t *packed, const float *
  * 16-bit dtypes with K % 32 == 0 and a power-of-two blocksize >= 32 dividing K (the decode fast path) support both
  * epilogues; other shapes / f32 support EPILOGUE_NONE only and return FP4_ERR_UNSUPPORTED for the gated one, so the
  * caller can run the plain GEMV and the separate ops.  Not in the reference.
+ *
+ * At edge values every epilogue of this header (this entry point, the 2..128-row ones and the NF4, LoRA, multi-adapter and
+ * nested forms) returns what those separate torch ops return on this device, value for value; a NaN is a NaN, payload and
+ * sign unspecified.  Measured at every 16-bit gate pattern and at every call site (tests/test_gpu_epilogue_values.py):
+ *   - s is the f32 FORMULA g / (1 + expf(-g)), not true silu.  A NaN gate gives NaN and so does g = -inf (-inf / inf);
+ *     g = +inf gives +inf.  For g < -88.72 expf overflows and s is -0, where true silu would be a (tiny) normal number;
+ *     from g = 16.64 on (expf(-g) <= 2^-24) 1 + e is 1 and s = g.  A sum or sum + bias beyond T's range makes the gate +-inf first.
+ *   - bias and residual take part as ordinary rounded adds: a NaN or infinite bias or residual gives the NaN or infinity of
+ *     IEEE addition (inf - inf and 0 * inf, through the up row, are NaN); a sum, add or product beyond T's largest value
+ *     rounds to +-inf, ties go to even at every rounding.
+ *   - signed zeros are IEEE's: -0 * u and s * -0 keep the sign of the product, x + -x is +0, -0 + -0 is -0; a sum of products
+ *     that are all zero is +0 whatever their signs.
+ *   - subnormals are kept everywhere: fp16 subnormals, and bf16 subnormals (f32 subnormals once widened), as gate, up row,
+ *     bias, residual, sum and result; nothing is flushed.
+ *   - the 16-bit FP4 kernels form f32(12 code x absmax) before the final * (1/12): a row sum whose magnitude passes
+ *     f32 max / 12 = 2.8e37 (bf16 only) is +-inf although T could hold it.  The NF4 kernels and the f32 paths do not scale.
  */
 enum fp4_epilogue { FP4_EPILOGUE_NONE = 0, FP4_EPILOGUE_SILU_MUL_PAIRS = 1 };
 FP4_HIP_API int fp4_hip_gemv_fused(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,

@@ -138,13 +138,15 @@ def test_quantiser_and_dequant_past_2_to_the_31_elements(dtype):
     want_p, want_a = o.quantize_fp4(pat_t.float().cpu().numpy(), BS)
     w = pat_t.repeat(reps)
     assert w.numel() == n and n > (1 << 31)
-    for variant in (4, 1002, 0):  # persistent kernel, tiles kernel, the library's choice
-        hipabi.set_variant("quantize", variant)
-        packed, absmax = hipabi.quantize(w, BS)
-        p2, a2 = packed.view(reps, unit // 2), absmax.view(reps, unit // BS)
-        assert np.array_equal(p2[0].cpu().numpy(), want_p) and np.array_equal(a2[0].cpu().numpy(), want_a), variant
-        assert bool((p2 == p2[0]).all()) and bool((a2 == a2[0]).all()), variant  # every repetition, the ones past 2^31 included
-    hipabi.set_variant("quantize", 0)
+    try:
+        for variant in (4, 1002, 0):  # persistent kernel, tiles kernel, the library's choice
+            hipabi.set_variant("quantize", variant)
+            packed, absmax = hipabi.quantize(w, BS)
+            p2, a2 = packed.view(reps, unit // 2), absmax.view(reps, unit // BS)
+            assert np.array_equal(p2[0].cpu().numpy(), want_p) and np.array_equal(a2[0].cpu().numpy(), want_a), variant
+            assert bool((p2 == p2[0]).all()) and bool((a2 == a2[0]).all()), variant  # every repetition, the ones past 2^31 included
+    finally:
+        hipabi.set_variant("quantize", 0)
     del w
     out = hipabi.dequantize(packed, absmax, BS, n, torch.bfloat16)
     o2 = out.view(reps, unit).view(torch.int16)

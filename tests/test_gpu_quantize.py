@@ -100,13 +100,15 @@ def _check(w_t, bs):
     kernel forced (4 workgroups per CU) and the one-shot tiles kernel with 1 / 2 / 4 loads per lane (1001 / 1002 / 1004; it applies to
     whole tiles with blocks of at most 512 elements and hands everything else to the persistent kernel)."""
     want_p, want_a = o.quantize_fp4(w_t.float().cpu().numpy().reshape(-1), bs)
-    for variant in (0, 4, 1001, 1002, 1004):
-        hipabi.set_variant("quantize", variant)
-        packed, absmax = hipabi.quantize(w_t.to(dev()), bs)
-        np.testing.assert_array_equal(absmax.cpu().numpy(), want_a)  # NaN == NaN here
-        bad = np.flatnonzero(packed.cpu().numpy() != want_p)
-        assert bad.size == 0, (variant, bad[:8], packed.cpu().numpy()[bad[:8]], want_p[bad[:8]])
-    hipabi.set_variant("quantize", 0)
+    try:
+        for variant in (0, 4, 1001, 1002, 1004):
+            hipabi.set_variant("quantize", variant)
+            packed, absmax = hipabi.quantize(w_t.to(dev()), bs)
+            np.testing.assert_array_equal(absmax.cpu().numpy(), want_a)  # NaN == NaN here
+            bad = np.flatnonzero(packed.cpu().numpy() != want_p)
+            assert bad.size == 0, (variant, bad[:8], packed.cpu().numpy()[bad[:8]], want_p[bad[:8]])
+    finally:
+        hipabi.set_variant("quantize", 0)
 
 
 def test_quantize_threshold_neighbourhoods():
