@@ -23,22 +23,18 @@ reference checkout):
 
 Pinning status
 --------------
-The reference cannot be compiled here (its .cu files need nvcc + CUB, neither
-exists in the image) nor imported (``bitsandbytes`` and the built extension are
-absent: ordinary ModuleNotFoundError).  The reference holds no test vectors.
-The oracle is therefore pinned by what the reference *does* hold:
+The reference cannot be built as CUDA here (no nvcc, no CUB, no NVIDIA GPU) nor imported (``bitsandbytes`` and the built
+extension are absent: ordinary ModuleNotFoundError), and it holds no test vectors.  Its KERNEL TEXT, however, runs: oracle/ref_cpu.py
+compiles the two .cu files' kernels unedited as C++ against a small CUDA/CUB shim (one OS thread per CUDA thread), and
+tests/golden/reference_vectors.npz records what they compute.  tests/test_reference_vectors_host.py holds this module to those
+vectors bit for bit: :func:`dequantize` (index rule incl. blocksize % 16 != 0, both tables, conversions, scales of 0 / subnormal /
+FLT_MAX / Inf / NaN / negative) and :func:`gemv_reference_emulated` in both contraction modes.  What stays a restatement by reading:
+the lane order inside ``cub::WarpReduce::Sum`` (the shim restates it too), NaN payloads and :func:`expected_dispatch`.
+Pinned besides: the code-table literals of the .cu files (tests/test_oracle.py re-derives the hex constants below from the decimal
+literals with a real C compiler, via oracle/fp4_oracle.c), and the published acceptance statistic, mean|dense - fp4| in [0.045, 0.065] with the nine README values 0.049-0.057
+(README.md:90-91,113-115,137-139,161-163; sanity_check.py:130-179), reproduced in tests/test_oracle.py.
 
-* the code-table literals of the .cu files (tests/test_oracle.py re-derives
-  the hex constants below from the decimal literals with a real C compiler,
-  via oracle/fp4_oracle.c), and
-* the published acceptance statistic, mean|dense - fp4| in [0.045, 0.065] with
-  the nine README values 0.049-0.057 (README.md:90-91,113-115,137-139,161-163;
-  sanity_check.py:130-179), reproduced in tests/test_oracle.py.
-
-The dequant/GEMV consumer side is fully specified by the .cu sources, so its
-parity is pinned by construction from those sources.  The *quantiser*
-(bitsandbytes) is "parity unpinned": no reference-held vector covers its exact
-tie/threshold bits.
+The *quantiser* (bitsandbytes) is "parity unpinned": no reference-held vector covers its exact tie/threshold bits.
 """
 from __future__ import annotations
 
