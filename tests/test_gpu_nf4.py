@@ -339,7 +339,8 @@ def test_linear_nf4_every_dispatch_row(dtype):
     h = HALF_ULP[dtype]  # batch > 1 runs dequant (weights rounded to T) + GEMM: allow one rounding per weight and one of the result
     for shape in [(1, K), (1, 1, K), (4, K), (2, 3, K), (1, 2, K), (K,), (200, K)]:
         x = torch.randn(*shape, device=dev()).to(dtype)
-        y = layer(x)
+        with torch.no_grad():  # the wrapped layer's bias is a Parameter that requires grad: outside no_grad the batch > 1 rows carry
+            y = layer(x)       # a grad_fn, as the reference's F.linear does (tests/test_gpu_qlinear_exact.py); this test is inference
         exact, scale = _restated(layer, x.float())
         assert tuple(y.shape) == tuple(shape[:-1]) + (M,)
         err = np.abs(y.double().cpu().numpy() - exact)
@@ -450,11 +451,13 @@ def test_nf4_single_token_with_k_not_a_multiple_of_the_blocksize_takes_qlinear_n
         layer(x)  # compute dtype set on the first call
         calls.clear()
         monkeypatch.setattr(qd_mod, "ext", Recording())
-        y = layer(x)
+        with torch.no_grad():  # inference: the bias Parameter requires grad, and outside no_grad qlinear_nf4_bias returns a grad_fn
+            y = layer(x)
         monkeypatch.undo()
         assert calls == ["qlinear_nf4_bias" if bias else "qlinear_nf4"], calls
-        direct = (pkg.ext.qlinear_nf4_bias(x, qd.A, qd.absmax, qd.M, qd.N, qd.blocksize, qd.bias) if bias else
-                  pkg.ext.qlinear_nf4(x, qd.A, qd.absmax, qd.M, qd.N, qd.blocksize))
+        with torch.no_grad():
+            direct = (pkg.ext.qlinear_nf4_bias(x, qd.A, qd.absmax, qd.M, qd.N, qd.blocksize, qd.bias) if bias else
+                      pkg.ext.qlinear_nf4(x, qd.A, qd.absmax, qd.M, qd.N, qd.blocksize))
         assert torch.equal(y, direct)
         exact, scale = _restated(layer, x.float())
         err = np.abs(y.double().cpu().numpy() - exact)

@@ -13,9 +13,11 @@ import torch
 import nf4_ref as R
 from gpu_util import case, dev
 from oracle import fp4_oracle as o
+from qlinear_constructed import routed
 
 pytestmark = pytest.mark.gpu
 BS = 64
+COUNTER = {"hipblaslt": "direct", "aten": "aten"}  # set_qlinear_gemm's name of a route -> its counter in qlinear_gemm_stats()
 TOL = {torch.float32: (2e-5, 2e-5), torch.float16: (2e-3, 2e-3), torch.bfloat16: (1.6e-2, 1.6e-2)}
 
 
@@ -66,7 +68,8 @@ def test_both_gemm_routes_against_float64(dtype, M, K, shape):
             outs = {}
             for route in ("hipblaslt", "aten"):
                 P.ext.set_qlinear_gemm(route)
-                y = op()
+                with routed(P.ext, COUNTER[route], calls=1):  # the route named is the route that ran
+                    y = op()
                 assert y.shape == (*shape[:-1], M) and y.dtype == dtype
                 outs[route] = y.double().cpu().numpy().reshape(-1, M)
                 err = np.abs(outs[route] - want).max()
@@ -107,7 +110,8 @@ def test_nf4_both_gemm_routes_against_float64(dtype, M, K, shape):
         outs = {}
         for route in ("hipblaslt", "aten"):
             P.ext.set_qlinear_gemm(route)
-            y = op()
+            with routed(P.ext, COUNTER[route], calls=1):
+                y = op()
             assert y.shape == (*shape[:-1], M) and y.dtype == dtype
             outs[route] = y.double().cpu().numpy().reshape(-1, M)
             err = np.abs(outs[route] - want).max()

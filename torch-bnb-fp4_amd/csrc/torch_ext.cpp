@@ -22,9 +22,11 @@
 //   * double-quantised absmax: absmax_unnest, absmax_nest, gemv_nf4_nested, gemm_nf4_nested, gemv_nf4_lora_nested,
 //     gemm_nf4_lora_nested, qlinear_nf4_nested;
 //   * tensor parallelism: comm_alloc / comm_open / comm_close / comm_free / comm_status / comm_clear_status, allreduce_oneshot;
-//   * hooks: code_table, set_kernel_variant, set_qlinear_gemm.
+//   * hooks: code_table, set_kernel_variant, set_qlinear_gemm, qlinear_gemm_stats.
 // The fused 4-bit weight ops (every *_fused, gemm_small_*, gemm_wide_nf4, *_lora, gemv_nf4_nested, gemv_fp4_partial) validate their
 // operands in one place, weight_op() below.
+#include <ATen/autocast_mode.h>
+#include <ATen/core/grad_mode.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -162,7 +164,20 @@ torch::Tensor dequantize_nf4(torch::Tensor A, torch::Tensor absmax, int blocksiz
 // f32 accumulation (HIPBLAS_COMPUTE_32F, no reduced-precision f32 mode), bias through the library's epilogue, one rounding to T.
 // Anything this path does not cover - other dtypes, a bias of another dtype, no algorithm returned, the first call of a device
 // arriving under stream capture - goes to at::linear; FP4_QLINEAR_GEMM=aten (or set_qlinear_gemm("aten")) forces that route.
+// The library call is a product and nothing else: it records no autograd node and knows no cast policy.  Where at::linear means
+// more than the product the direct route steps aside (qlinear_impl): grad mode on with an activation or a bias that requires
+// grad (the reference's F.linear sends gradient to both), or autocast enabled for the activation's device type.  no_grad,
+// inference_mode and inputs that do not require grad keep the direct route.  qlinear_gemm_stats() counts the calls each route
+// served, process-wide (no reset: take differences).
 std::atomic<int> g_qlinear_gemm{-1};  // -1 = not decided yet (environment), 0 = at::linear, 1 = hipBLASLt direct
+std::atomic<uint64_t> g_qlinear_direct_calls{0}, g_qlinear_aten_calls{0};
+
+py::dict qlinear_gemm_stats() {
+    py::dict d;
+    d["direct"] = g_qlinear_direct_calls.load(std::memory_order_relaxed);
+    d["aten"] = g_qlinear_aten_calls.load(std::memory_order_relaxed);
+    return d;
+}
 
 bool qlinear_gemm_direct() {
     int v = g_qlinear_gemm.load(std::memory_order_relaxed);
@@ -332,11 +347,17 @@ torch::Tensor qlinear_impl(const torch::Tensor &A_in, const torch::Tensor &A, co
     torch::Tensor weight = torch::empty({M, N}, A_in.options());
     // the GEMM below reads the weight straight back: keep it in L2 / Infinity Cache (plain stores)
     dequant_into(A, absmax, weight, blocksize, int64_t(M) * N, table, FP4_DEQUANT_KEEP_CACHED);
-    if (qlinear_gemm_direct()) {
+    // at::linear is more than a product under autograd (gradient to the activation and the bias) and under autocast (its cast policy)
+    const bool wants_grad = at::GradMode::is_enabled() && (A_in.requires_grad() || (bias.has_value() && bias->requires_grad()));
+    if (qlinear_gemm_direct() && !wants_grad && !at::autocast::is_autocast_enabled(A_in.device().type())) {
         c10::DeviceGuard guard(A_in.device());
         torch::Tensor out;
-        if (lt_linear(A_in, weight, bias, out)) return out;
+        if (lt_linear(A_in, weight, bias, out)) {
+            g_qlinear_direct_calls.fetch_add(1, std::memory_order_relaxed);
+            return out;
+        }
     }
+    g_qlinear_aten_calls.fetch_add(1, std::memory_order_relaxed);
     return bias.has_value() ? at::linear(A_in, weight, *bias) : at::linear(A_in, weight);
 }
 
@@ -972,6 +993,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("set_qlinear_gemm", &set_qlinear_gemm,
           "which dense GEMM the qlinear* ops call after the dequant: 'hipblaslt' (direct, cached plans; default) or 'aten' (at::linear); "
           "returns the previous setting");
+    m.def("qlinear_gemm_stats", &qlinear_gemm_stats,
+          "calls of the qlinear* ops served by each GEMM route since the process started: {'direct': n, 'aten': n}");
     m.attr("EPILOGUE_NONE") = (int)FP4_EPILOGUE_NONE;
     m.attr("EPILOGUE_SILU_MUL_PAIRS") = (int)FP4_EPILOGUE_SILU_MUL_PAIRS;
     m.attr("abi_version") = fp4_hip_abi_version();
