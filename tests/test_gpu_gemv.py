@@ -382,6 +382,27 @@ def test_split_k_with_workspace(dtype, B, M, K):
         assert int(d.max()) <= 1 and float((d == 0).float().mean()) >= 0.995
 
 
+def test_a_workspace_does_not_make_another_blocksize_than_64_a_split_k_shape():
+    """The split-K kernel reads one scale per 64 weights.  33 rows on 16 x 8192 is its shape at blocksize 64: a workspace is asked for
+    and the result is fp4_hip_gemm_small_fused's bit for bit.  The same weight bytes declared as blocksize 128, with the same real
+    workspace: no workspace is asked for, the call is refused as fp4_hip_gemm_small_fused refuses it, and `out` is not touched."""
+    B, M, K, dtype = 33, 16, 8192, torch.bfloat16
+    c = case(M, K, seed=shape_seed(M, K))
+    x_t, b_t, _, _ = c.rows(B, B * 13 + K, dtype)
+    y, want = hipabi.gemm_small_ws(x_t, c.P, c.A, M, K, 64, bias=b_t)
+    assert want == 16 * B * M * 4
+    assert torch.equal(y, hipabi.gemm_small_fused(x_t, c.P, c.A, M, K, 64, b_t, None))
+    l = hipabi.lib()
+    assert l.fp4_hip_gemm_small_ws_bytes(B, M, K, 128, hipabi.DT[dtype]) == 0
+    ws = torch.zeros(want, dtype=torch.uint8, device=dev())
+    out = torch.full((B, M), -7.0, dtype=dtype, device=dev())
+    rc = l.fp4_hip_gemm_small_ws(hipabi._ptr(x_t), hipabi._ptr(c.P), hipabi._ptr(c.A), hipabi._ptr(b_t), None, hipabi._ptr(out), B, M, K, 128,
+                                 hipabi.DT[dtype], hipabi.EPILOGUE_NONE, hipabi._ptr(ws), want, hipabi._stream())
+    assert rc == hipabi.ERR_UNSUPPORTED and "shape B=11 M=16 K=8192 blocksize=128" in hipabi.last_error()
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all()) and not bool(ws.any())
+
+
 def test_small_batch_random_shapes_against_float64():
     """200 seeded random cases through fp4_hip_gemm_small: 1..128 rows, M in 1..200, K = 64 * (1..40) - fewer quant blocks than K
     slices, ragged last steps, single-row weights, every workgroup shape of the one-pass kernels forced or chosen - against the

@@ -7,6 +7,7 @@
 //                           (v_mfma_f32_16x16x32): one-shot for any K % 512 == 0, persistent for K = 4096.
 #include <atomic>
 
+#include "fp4_call.h"
 #include "launchers.h"
 #include "mfma_common.h"
 
@@ -577,9 +578,21 @@ std::atomic<int> g_mfma_rowt{-1};     // force 1 or 2 row tiles per workgroup
 std::atomic<int> g_mfma_xstage{-1};   // 0 = B fragments straight from global even for batch <= 8
 std::atomic<int> g_mfma_persist{-1};  // 0 = never the persistent kernel, 1 = whenever it applies
 
+// the one-shot kernel for NBW blocks per wave and pass and RT row tiles: with the <= 4-row or <= 8-row x image where it is built
+template <int DT, int NBW, int RT>
+auto mfma_kernel(bool xs4, bool xs8) -> decltype(&gemm16_mfma_kernel<DT, NBW, RT, true>) {
+    if constexpr (NBW >= 4) {
+        if constexpr (RT == 1) {
+            if (xs4) return gemm16_mfma_kernel<DT, NBW, RT, true, 4>;
+        }
+        if (xs8) return gemm16_mfma_kernel<DT, NBW, RT, true, 8>;
+    }
+    return gemm16_mfma_kernel<DT, NBW, RT, true>;
+}
+
 template <int DT>
-int dispatch_mfma(const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, int B, int M,
-                  int K, int mode, hipStream_t stream) {
+int dispatch_mfma(const Fp4Call &c) {
+    const int B = (int)c.B, M = (int)c.M, K = (int)c.K;
     if (K % 512) return -1;
     const int units = K / 512;  // quant blocks per wave over the whole K
     const int v_rowt = g_mfma_rowt.load(std::memory_order_relaxed),
@@ -600,88 +613,43 @@ int dispatch_mfma(const void *x, const uint8_t *W, const float *absmax, const vo
         const int ntiles = (M + 15) / 16, resident = (B <= 4 ? 2 : 1) * device_cu_count();
         // measured (profiles/r01_f_small_batch_shapes.txt): never slower than the one-shot kernel, level with it while
         // every workgroup has a single tile, up to 1.6x faster on tall weights
-        {
-            const dim3 grid(ntiles < resident ? ntiles : resident);
-            if (B <= 4)
-                hipLaunchKernelGGL((gemm16_mfma_persist_kernel<DT, 4>), grid, dim3(512), 0, stream,
-                                   reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
-                                   reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, ntiles, mode);
-            else if (B <= 8)
-                hipLaunchKernelGGL((gemm16_mfma_persist_kernel<DT, 8>), grid, dim3(512), 0, stream,
-                                   reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
-                                   reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, ntiles, mode);
-            else
-                hipLaunchKernelGGL((gemm16_mfma_persist_kernel<DT, 0>), grid, dim3(512), 0, stream,
-                                   reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
-                                   reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, ntiles, mode);
-            return FP4_OK;
-        }
+        const auto kern = B <= 4 ? gemm16_mfma_persist_kernel<DT, 4> : (B <= 8 ? gemm16_mfma_persist_kernel<DT, 8> : gemm16_mfma_persist_kernel<DT, 0>);
+        return launch_gemm16(kern, dim3(ntiles < resident ? ntiles : resident), dim3(512), 0, c, ntiles);
     }
     const bool xs4 = v_xstage != 0 && B <= 4;
     const bool xs8 = v_xstage != 0 && !xs4 && B <= 8 && (int)blocks <= device_cu_count();
     // (round 3: the direct, un-staged 8-byte weight loads - a sweep switch that never won, profiles/r01_e_small_batch_valu_vs_mfma.txt -
     //  and the <= 4-row x image under two row tiles, which needs > 4 rows to be chosen, are no longer built)
-#define FP4_MF(NBW, RT)                                                                                               \
-    if constexpr ((NBW) >= 4) {                                                                                       \
-        if constexpr ((RT) == 1) {                                                                                    \
-            if (xs4) {                                                                                                \
-                hipLaunchKernelGGL((gemm16_mfma_kernel<DT, NBW, RT, true, 4>), dim3(blocks), dim3(512), 0, stream,    \
-                                   reinterpret_cast<const uint16_t *>(x), W, absmax,                                  \
-                                   reinterpret_cast<const uint16_t *>(bias), reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, mode); \
-                return FP4_OK;                                                                                        \
-            }                                                                                                         \
-        }                                                                                                             \
-        if (xs8) {                                                                                                    \
-            hipLaunchKernelGGL((gemm16_mfma_kernel<DT, NBW, RT, true, 8>), dim3(blocks), dim3(512), 0, stream,        \
-                               reinterpret_cast<const uint16_t *>(x), W, absmax,                                      \
-                               reinterpret_cast<const uint16_t *>(bias), reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, mode); \
-            return FP4_OK;                                                                                            \
-        }                                                                                                             \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((gemm16_mfma_kernel<DT, NBW, RT, true>), dim3(blocks), dim3(512), 0, stream,                   \
-                       reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),    \
-                       reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, mode);                                                   \
-    return FP4_OK
-#define FP4_MF_RT(NBW)          \
-    if (rowt == 2) {            \
-        FP4_MF(NBW, 2);         \
-    } else {                    \
-        FP4_MF(NBW, 1);         \
-    }
+#define FP4_MF(NBW) \
+    return launch_gemm16(rowt == 2 ? mfma_kernel<DT, NBW, 2>(xs4, xs8) : mfma_kernel<DT, NBW, 1>(xs4, xs8), dim3(blocks), dim3(512), 0, c)
     // At most 4 blocks per wave and pass, the next pass's loads in flight (8192 x 8192 x 4 rows: 12.4 -> 10.6 us, 28672 x 8192: 36 -> 33 us,
     // profiles/r01_f_small_batch_pass_ahead.txt).  Round 3: also where 8 blocks would be the whole K in one pass (K = 4096: 5.0 -> 4.6 us
     // at 4096 rows) - the 8-block instantiations (up to 208 VGPRs) are no longer built.
-    if (units % 4 == 0) { FP4_MF_RT(4) }
-    if (units % 2 == 0) { FP4_MF_RT(2) }
-    FP4_MF_RT(1)
-#undef FP4_MF_RT
+    if (units % 4 == 0) FP4_MF(4);
+    if (units % 2 == 0) FP4_MF(2);
+    FP4_MF(1);
 #undef FP4_MF
 }
 
 template <int DT, int KSPLIT, int G, int ITERS, int NB>
-int launch_small(const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, int B, int M,
-                 int K, int bs_shift, int mode, hipStream_t stream) {
+int launch_small(const Fp4Call &c) {
     constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
-    const unsigned blocks = (unsigned)((M + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL((gemm16_small_kernel<DT, KSPLIT, G, ITERS, NB>), dim3(blocks), dim3(256), 0, stream,
-                       reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias),
-                       reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, bs_shift, mode);
-    return FP4_OK;
+    return launch_gemm16(gemm16_small_kernel<DT, KSPLIT, G, ITERS, NB>, dim3((unsigned)((c.M + rows_per_block - 1) / rows_per_block)), dim3(256),
+                         0, c, c.bs_shift());
 }
 
 // returns -1 when the shape is outside what the register budget covers (caller falls back to dequant + GEMM)
 template <int DT>
-int dispatch_small(const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, int B, int M,
-                   int K, int bs_shift, int mode, hipStream_t stream) {
-    const int C = K >> 5;
+int dispatch_small(const Fp4Call &c) {
+    const int B = (int)c.B, C = (int)c.K >> 5;
     const int nb = B <= 2 ? 2 : (B <= 4 ? 4 : 8);
-    if (int64_t(M) * K >= (int64_t(1) << 32)) return -1;  // 32-bit buffer offsets
-#define FP4_SM(KS, GG, NBB) return launch_small<DT, KS, GG, 2, NBB>(x, W, absmax, bias, residual, out, B, M, K, bs_shift, mode, stream)
-#define FP4_SM_NB(KS, GG)                                                                                                   \
-    switch (nb) {                                                                                                           \
-        case 2: FP4_SM(KS, GG, 2);                                                                                          \
-        case 4: FP4_SM(KS, GG, 4);                                                                                          \
-        default: FP4_SM(KS, GG, 8);                                                                                         \
+    if (c.M * c.K >= (int64_t(1) << 32)) return -1;  // 32-bit buffer offsets
+#define FP4_SM(KS, GG, NBB) return launch_small<DT, KS, GG, 2, NBB>(c)
+#define FP4_SM_NB(KS, GG)            \
+    switch (nb) {                    \
+        case 2: FP4_SM(KS, GG, 2);   \
+        case 4: FP4_SM(KS, GG, 4);   \
+        default: FP4_SM(KS, GG, 8);  \
     }
     if (C <= 32) {
         FP4_SM_NB(1, 1)
@@ -717,38 +685,38 @@ void set_small_variant(int v) {
 
 namespace fp4 {
 namespace {
-int gemm_small_entry(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual, void *out,
-                     int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream) {
+int gemm_small_entry(const Fp4Call &c) {
+    const int64_t B = c.B, M = c.M, K = c.K;
+    const int blocksize = c.blocksize, dtype = c.dtype;
     if (B < 0 || B > 128 || M < 0 || K <= 0) {
         set_error("fp4_hip_gemm_small: B=%lld M=%lld K=%lld (need 0 <= B <= 128, M >= 0, K > 0)", (long long)B, (long long)M, (long long)K);
         return FP4_ERR_INVALID_ARGUMENT;
     }
-    if ((mode & kModeSiluMulPairs) && (M & 1)) {
+    if (c.gated() && (M & 1)) {
         set_error("fp4_hip_gemm_small_fused: the gate|up epilogue needs an even row count, got M=%lld", (long long)M);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     if (B == 0) return FP4_OK;  // an empty batch is no error (as M == 0 below, and as the NF4 entry points): nothing to launch
-    const int64_t M_out = (mode & kModeSiluMulPairs) ? M / 2 : M;
     if (dtype == FP4_DTYPE_F32) {
         // f32 activations (the reference's sanity harness; models run 16-bit): no matrix-core kernel and none needed - up to 8 rows run
         // as B launches of the f32 GEMV, each streaming the weight once (B x 9.45 MB against the 76 MB a dequantised 4096 x 4096 f32
         // weight costs to write and read back) and each bit-identical to the single-row call; bias and residual as the GEMV applies them
         // (in f32 "T(T(sum) + bias)" is the one f32 addition F.linear does).  More rows, or the gated epilogue: the caller's dequant + GEMM.
-        if (B > 8 || (mode & kModeSiluMulPairs)) {
+        if (B > 8 || c.gated()) {
             set_error("fp4_hip_gemm_small: f32 activations are covered up to 8 rows without the gate|up epilogue (got B=%lld); "
                       "use dequant + GEMM", (long long)B);
             return FP4_ERR_UNSUPPORTED;
         }
         if (M == 0) return FP4_OK;
-        if (!x || !out) {
+        if (!c.x || !c.out) {
             set_error("fp4_hip_gemm_small: null pointer");
             return FP4_ERR_INVALID_ARGUMENT;
         }
         for (int64_t b = 0; b < B; ++b) {
-            const int rc = fp4_hip_gemv_fused(static_cast<const float *>(x) + size_t(b) * size_t(K), packed, absmax, bias,
-                                              residual ? static_cast<const float *>(residual) + size_t(b) * size_t(M) : nullptr,
-                                              static_cast<float *>(out) + size_t(b) * size_t(M), M, K, blocksize, FP4_DTYPE_F32,
-                                              FP4_EPILOGUE_NONE, stream);
+            const int rc = fp4_hip_gemv_fused(static_cast<const float *>(c.x) + size_t(b) * size_t(K), c.W, c.absmax, c.bias,
+                                              c.residual ? static_cast<const float *>(c.residual) + size_t(b) * size_t(M) : nullptr,
+                                              static_cast<float *>(c.out) + size_t(b) * size_t(M), M, K, blocksize, FP4_DTYPE_F32,
+                                              FP4_EPILOGUE_NONE, c.stream);
             if (rc != FP4_OK) return rc;
         }
         return FP4_OK;
@@ -761,33 +729,21 @@ int gemm_small_entry(const void *x, const uint8_t *packed, const float *absmax, 
         // 17..64 rows: one pass over the weight with 2..4 column tiles per decoded fragment (gemm_wide_fp4.hip) where the shape
         // allows; otherwise, and above 64 rows, the rows are split evenly over several launches, each streaming the weight once -
         // still ahead of dequant + GEMM while launches x 9.45 MB < the 76 MB the dequantised weight costs to write and read back
-        const uintptr_t al = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
-        if (B <= 64 && M > 0 && x && packed && absmax && out && blocksize == 64 && (al & 15u) == 0 && M <= (int64_t(1) << 30) &&
-            K <= (int64_t(1) << 24) &&
-            gemm_wide_launch(dtype, x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, false, static_cast<hipStream_t>(stream)) == FP4_OK)
+        const uintptr_t al = reinterpret_cast<uintptr_t>(c.W) | reinterpret_cast<uintptr_t>(c.x);
+        if (B <= 64 && M > 0 && c.x && c.W && c.absmax && c.out && blocksize == 64 && (al & 15u) == 0 && M <= (int64_t(1) << 30) &&
+            K <= (int64_t(1) << 24) && gemm_wide_launch(c, false) == FP4_OK)
             return check_launch("fp4_hip_gemm_small");
-        const int64_t unit = B > 64 ? 64 : 16;
-        const int64_t chunks = (B + unit - 1) / unit, per = (B + chunks - 1) / chunks;
-        for (int64_t b0 = 0; b0 < B; b0 += per) {
-            const int64_t nb = B - b0 < per ? B - b0 : per;
-            const int rc = gemm_small_entry(static_cast<const uint8_t *>(x) + size_t(b0) * size_t(K) * 2, packed, absmax, bias,
-                                            residual ? static_cast<const uint8_t *>(residual) + size_t(b0) * size_t(M_out) * 2 : nullptr,
-                                            out ? static_cast<uint8_t *>(out) + size_t(b0) * size_t(M_out) * 2 : nullptr, nb, M, K,
-                                            blocksize, dtype, mode, stream);
-            if (rc != FP4_OK) return rc;
-        }
-        return FP4_OK;
+        return for_row_chunks(c, B > 64 ? 64 : 16, gemm_small_entry);  // a null out goes on as it is: the chunk reports it
     }
     if (M == 0) return FP4_OK;
-    if (!x || !packed || !absmax || !out) {
+    if (!c.x || !c.W || !c.absmax || !c.out) {
         set_error("fp4_hip_gemm_small: null pointer");
         return FP4_ERR_INVALID_ARGUMENT;
     }
-    const int bs_shift = ilog2_exact(blocksize);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
-    const bool ok = (dtype == FP4_DTYPE_F16 || dtype == FP4_DTYPE_BF16) && (K % 32) == 0 && bs_shift >= 5 &&
+    const uintptr_t align = reinterpret_cast<uintptr_t>(c.W) | reinterpret_cast<uintptr_t>(c.x);
+    const bool ok = (dtype == FP4_DTYPE_F16 || dtype == FP4_DTYPE_BF16) && (K % 32) == 0 && c.bs_shift() >= 5 &&
                     (K % blocksize) == 0 && (align & 15u) == 0 && M <= (int64_t(1) << 30) && K <= (int64_t(1) << 24);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto mfma = [&] { return with_dtype(dtype, [&](auto dt) { return dispatch_mfma<decltype(dt)::value>(c); }); };
     int rc = -1;
     // matrix-core kernel: blocksize 64, K % 512 == 0; wins from 2 rows up (4.96 vs 5.11 us at 2, 5.0 vs 11.3 us at 8), mandatory above 8
     const bool mfma_ok = ok && blocksize == 64 && (K % 512) == 0;
@@ -803,7 +759,7 @@ int gemm_small_entry(const void *x, const uint8_t *packed, const float *absmax, 
     // column tile (profiles/r02_wide_batch_17_to_128_rows.txt: 5120 x 13824 x 16 rows 49.2 -> 26.9 us, 13824 x 5120 21.7 -> 15.6 us,
     // 28672 x 8192 52.7 -> 38.8 us); up to 4 rows the old kernel holds where K / 512 is even.
     if (ok && blocksize == 64 && (K % 64) == 0 && g_small_wide.load(std::memory_order_relaxed))  // sweep hook
-        rc = gemm_wide_launch(dtype, x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, true, s);
+        rc = gemm_wide_launch(c, true);
     if (rc == -1 && mfma_ok && v_small < 0 && !short_few) {
         const int64_t units = K / 512;
         // (round 3, profiles/r03_small_batch_dispatch.txt: K / 512 = 2 mod 4 also below 5 rows on tall weights - 13824 x 5120 x 2..4 rows
@@ -812,22 +768,15 @@ int gemm_small_entry(const void *x, const uint8_t *packed, const float *absmax, 
         const int64_t cus = device_cu_count();
         if ((units & 1) || ((units % 4) != 0 && (B >= 5 || M >= 48 * cus)) || (M >= 96 * cus && K >= 8192 && B >= 5) ||
             (B >= 13 && K >= 12288 && M <= 16 * cus))
-            rc = gemm_wide_launch(dtype, x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, true, s);
+            rc = gemm_wide_launch(c, true);
     }
-    if (rc == -1 && mfma_ok && (want_mfma || B > 8))
-        rc = dtype == FP4_DTYPE_F16 ? dispatch_mfma<FP4_DTYPE_F16>(x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s)
-                                    : dispatch_mfma<FP4_DTYPE_BF16>(x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s);
-    if (rc == -1 && ok && B <= 8 && K <= 16384)
-        rc = dtype == FP4_DTYPE_F16
-                 ? dispatch_small<FP4_DTYPE_F16>(x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, bs_shift, mode, s)
-                 : dispatch_small<FP4_DTYPE_BF16>(x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, bs_shift, mode, s);
-    if (rc == -1 && mfma_ok)
-        rc = dtype == FP4_DTYPE_F16 ? dispatch_mfma<FP4_DTYPE_F16>(x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s)
-                                    : dispatch_mfma<FP4_DTYPE_BF16>(x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, s);
+    if (rc == -1 && mfma_ok && (want_mfma || B > 8)) rc = mfma();
+    if (rc == -1 && ok && B <= 8 && K <= 16384) rc = with_dtype(dtype, [&](auto dt) { return dispatch_small<decltype(dt)::value>(c); });
+    if (rc == -1 && mfma_ok) rc = mfma();
     // K % 512 != 0 beyond the VALU kernel's reach (e.g. Llama-2-7B's down projection, K = 11008): the one-pass kernels of
     // gemm_wide_fp4.hip take any K % 64 == 0 and 1..64 rows
     if (rc == -1 && ok && blocksize == 64 && (K % 64) == 0)
-        rc = gemm_wide_launch(dtype, x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, true, s);
+        rc = gemm_wide_launch(c, true);
     if (rc == -1) {
         set_error("fp4_hip_gemm_small: shape B=%lld M=%lld K=%lld blocksize=%d dtype=%d is not covered; use dequant + GEMM",
                   (long long)B, (long long)M, (long long)K, blocksize, dtype);
@@ -835,23 +784,33 @@ int gemm_small_entry(const void *x, const uint8_t *packed, const float *absmax, 
     }
     return check_launch("fp4_hip_gemm_small");
 }
+
+// fp4_hip_gemm_small_ws: the split-K path where the workspace, the shape and the blocksize are its own, else the call above
+int gemm_small_ws_entry(const Fp4Call &c) {
+    if (c.B > 64 && c.B <= 128 && c.workspace && c.x && c.out && c.M > 0 && c.K > 0 && (c.dtype == FP4_DTYPE_F16 || c.dtype == FP4_DTYPE_BF16))
+        return for_row_chunks(c, 64, gemm_small_ws_entry);  // two even chunks, one after the other through the same workspace
+    const uintptr_t al = reinterpret_cast<uintptr_t>(c.W) | reinterpret_cast<uintptr_t>(c.x);
+    if (c.workspace && c.x && c.W && c.absmax && c.out && (al & 15u) == 0 && c.B >= 33 && c.B <= 64 && c.M > 0 && c.M <= (int64_t(1) << 30) &&
+        c.K <= (int64_t(1) << 24) && !(c.gated() && (c.M & 1)) && gemm_splitk_launch(c) == FP4_OK)
+        return check_launch("fp4_hip_gemm_small_ws");
+    return gemm_small_entry(c);
+}
 }  // namespace
 }  // namespace fp4
 
 extern "C" int fp4_hip_gemm_small(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                                   int64_t B, int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
-    return fp4::gemm_small_entry(x, packed, absmax, bias, nullptr, out, B, M, K, blocksize, dtype, 0, stream);
+    return fp4::gemm_small_entry({.x = x, .W = packed, .absmax = absmax, .bias = bias, .out = out, .B = B, .M = M, .K = K,
+                                  .blocksize = blocksize, .dtype = dtype, .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int fp4_hip_gemm_small_fused(const void *x, const uint8_t *packed, const float *absmax, const void *bias,
                                         const void *residual, void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype,
                                         int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemm_small_fused: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemm_small_entry(x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype,
-                                 epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
+    const int mode = fp4::epilogue_mode("fp4_hip_gemm_small_fused", epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemm_small_entry({.x = x, .W = packed, .absmax = absmax, .bias = bias, .residual = residual, .out = out, .B = B, .M = M,
+                                  .K = K, .blocksize = blocksize, .dtype = dtype, .mode = mode, .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int64_t fp4_hip_gemm_small_ws_bytes(int64_t B, int64_t M, int64_t K, int blocksize, int dtype) {
@@ -862,28 +821,9 @@ extern "C" int64_t fp4_hip_gemm_small_ws_bytes(int64_t B, int64_t M, int64_t K, 
 extern "C" int fp4_hip_gemm_small_ws(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                      void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *workspace,
                                      int64_t workspace_bytes, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemm_small_ws: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    const int mode = epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0;
-    if (B > 64 && B <= 128 && workspace && x && out && M > 0 && K > 0 && (dtype == FP4_DTYPE_F16 || dtype == FP4_DTYPE_BF16)) {
-        const int64_t M_out = (mode & fp4::kModeSiluMulPairs) ? M / 2 : M, per = (B + 1) / 2;
-        for (int64_t b0 = 0; b0 < B; b0 += per) {
-            const int64_t nb = B - b0 < per ? B - b0 : per;
-            const int rc = fp4_hip_gemm_small_ws(static_cast<const uint8_t *>(x) + size_t(b0) * size_t(K) * 2, packed, absmax, bias,
-                                                 residual ? static_cast<const uint8_t *>(residual) + size_t(b0) * size_t(M_out) * 2 : nullptr,
-                                                 static_cast<uint8_t *>(out) + size_t(b0) * size_t(M_out) * 2, nb, M, K, blocksize, dtype,
-                                                 epilogue, workspace, workspace_bytes, stream);
-            if (rc != FP4_OK) return rc;
-        }
-        return FP4_OK;
-    }
-    const uintptr_t al = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
-    if (workspace && x && packed && absmax && out && (al & 15u) == 0 && B >= 33 && B <= 64 && M > 0 && M <= (int64_t(1) << 30) &&
-        K <= (int64_t(1) << 24) && !((mode & fp4::kModeSiluMulPairs) && (M & 1)) &&
-        fp4::gemm_splitk_launch(dtype, x, packed, absmax, bias, residual, out, (int)B, (int)M, (int)K, mode, workspace, workspace_bytes,
-                                static_cast<hipStream_t>(stream)) == FP4_OK)
-        return fp4::check_launch("fp4_hip_gemm_small_ws");
-    return fp4::gemm_small_entry(x, packed, absmax, bias, residual, out, B, M, K, blocksize, dtype, mode, stream);
+    const int mode = fp4::epilogue_mode("fp4_hip_gemm_small_ws", epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemm_small_ws_entry({.x = x, .W = packed, .absmax = absmax, .bias = bias, .residual = residual, .out = out, .B = B, .M = M,
+                                     .K = K, .blocksize = blocksize, .dtype = dtype, .mode = mode, .stream = static_cast<hipStream_t>(stream),
+                                     .workspace = workspace, .workspace_bytes = workspace_bytes});
 }

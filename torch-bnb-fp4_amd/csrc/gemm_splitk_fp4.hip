@@ -7,6 +7,7 @@
 // the first).  x traffic drops to (workgroups x rows x 1 KB), a few MB; the price is one float per (K slice, activation row, weight
 // row) through a workspace and a second, tiny launch that adds the slices in a fixed order and applies the epilogue - deterministic,
 // no atomics, no cross-workgroup synchronisation (stream order does it).
+#include "fp4_call.h"
 #include "launchers.h"
 #include "mfma_common.h"
 
@@ -161,31 +162,29 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
     }
 }
 
-template <int DT, int NT>
-void launch_xstat(const void *x, const uint8_t *W, const float *absmax, float *partial, int B, int M, int K, int rows_per_wg, int slices,
-                  hipStream_t stream) {
-    const dim3 grid((unsigned)slices, (unsigned)((M + rows_per_wg - 1) / rows_per_wg));
-    hipLaunchKernelGGL((gemm16_xstat_kernel<DT, NT>), grid, dim3(512), 0, stream, reinterpret_cast<const uint16_t *>(x), W, absmax, partial,
-                       B, M, K, rows_per_wg);
+// the launches of the two kernels here: each one's argument list, spelt here only; the partial sums live in the call's workspace
+template <typename Kern>
+void launch_xstat(Kern kern, dim3 grid, dim3 block, size_t lds, const Fp4Call &c, int rows_per_wg) {
+    hipLaunchKernelGGL(kern, grid, block, lds, c.stream, c.x16(), c.W, c.absmax, static_cast<float *>(c.workspace), (int)c.B, (int)c.M, (int)c.K,
+                       rows_per_wg);
+}
+template <typename Kern>
+void launch_reduce(Kern kern, dim3 grid, dim3 block, size_t lds, const Fp4Call &c, int slices) {
+    hipLaunchKernelGGL(kern, grid, block, lds, c.stream, static_cast<const float *>(c.workspace), c.bias16(), c.residual16(), c.out16(), (int)c.B,
+                       (int)c.M, slices, c.mode);
 }
 
 template <int DT>
-void launch_splitk(const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, float *ws,
-                   int B, int M, int K, int mode, int rows_per_wg, int slices, hipStream_t stream) {
-    const int nt = (B + 15) / 16;
-    if (nt == 1)
-        launch_xstat<DT, 1>(x, W, absmax, ws, B, M, K, rows_per_wg, slices, stream);
-    else if (nt == 2)
-        launch_xstat<DT, 2>(x, W, absmax, ws, B, M, K, rows_per_wg, slices, stream);
-    else if (nt == 3)
-        launch_xstat<DT, 3>(x, W, absmax, ws, B, M, K, rows_per_wg, slices, stream);
-    else
-        launch_xstat<DT, 4>(x, W, absmax, ws, B, M, K, rows_per_wg, slices, stream);
-    const int width = (mode & kModeSiluMulPairs) ? M / 2 : M;
-    const int64_t outs = (int64_t)B * width;
-    hipLaunchKernelGGL((splitk_reduce_kernel<DT>), dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, stream, ws,
-                       reinterpret_cast<const uint16_t *>(bias), reinterpret_cast<const uint16_t *>(residual),
-                       reinterpret_cast<uint16_t *>(out), B, M, slices, mode);
+void launch_splitk(const Fp4Call &c, int rows_per_wg, int slices) {
+    const dim3 grid((unsigned)slices, (unsigned)((c.M + rows_per_wg - 1) / rows_per_wg));
+    switch (((int)c.B + 15) / 16) {
+        case 1: launch_xstat(gemm16_xstat_kernel<DT, 1>, grid, dim3(512), 0, c, rows_per_wg); break;
+        case 2: launch_xstat(gemm16_xstat_kernel<DT, 2>, grid, dim3(512), 0, c, rows_per_wg); break;
+        case 3: launch_xstat(gemm16_xstat_kernel<DT, 3>, grid, dim3(512), 0, c, rows_per_wg); break;
+        default: launch_xstat(gemm16_xstat_kernel<DT, 4>, grid, dim3(512), 0, c, rows_per_wg);
+    }
+    const int64_t outs = c.B * c.M_out();
+    launch_reduce(splitk_reduce_kernel<DT>, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, c, slices);
 }
 
 }  // namespace
@@ -202,11 +201,13 @@ int64_t gemm_splitk_workspace_bytes(int64_t B, int64_t M, int64_t K, int blocksi
     return slices * B * M * 4;
 }
 
-// FP4_OK after both launches; -1 if the shape is not one for this path or the workspace is too small.
-int gemm_splitk_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                       int B, int M, int K, int mode, void *workspace, int64_t workspace_bytes, hipStream_t stream) {
-    const int64_t need = gemm_splitk_workspace_bytes(B, M, K, 64, dtype);
-    if (need == 0 || !workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u)) return -1;
+// FP4_OK after both launches; -1 if the shape is not one for this path (gemm16_xstat_kernel reads one scale per 64 weights: no other
+// blocksize, whatever workspace comes with it) or the workspace is too small.
+int gemm_splitk_launch(const Fp4Call &c) {
+    if (c.blocksize != 64) return -1;
+    const int64_t need = gemm_splitk_workspace_bytes(c.B, c.M, c.K, c.blocksize, c.dtype);
+    if (need == 0 || !c.workspace || c.workspace_bytes < need || (reinterpret_cast<uintptr_t>(c.workspace) & 15u)) return -1;
+    const int M = (int)c.M, K = (int)c.K;  // the caller has bounded them
     const int slices = (K / 64 + 7) / 8;
     // every wave gets the same number of 16-row tiles, and slices x row chunks is ONE round of workgroups (one per CU: the x slice's
     // fetch and the first barrier are paid once per workgroup)
@@ -214,11 +215,7 @@ int gemm_splitk_launch(int dtype, const void *x, const uint8_t *W, const float *
     int tpw = (int)((tiles + waves - 1) / waves);
     if (tpw < 1) tpw = 1;
     const int rows_per_wg = 128 * tpw;
-    float *ws = static_cast<float *>(workspace);
-    if (dtype == FP4_DTYPE_F16)
-        launch_splitk<FP4_DTYPE_F16>(x, W, absmax, bias, residual, out, ws, B, M, K, mode, rows_per_wg, slices, stream);
-    else
-        launch_splitk<FP4_DTYPE_BF16>(x, W, absmax, bias, residual, out, ws, B, M, K, mode, rows_per_wg, slices, stream);
+    with_dtype(c.dtype, [&](auto dt) { launch_splitk<decltype(dt)::value>(c, rows_per_wg, slices); });
     return FP4_OK;
 }
 

@@ -23,6 +23,7 @@
 //   * K-slice partials meet in LDS (the ring's storage, after the loop) and are summed in a fixed order: deterministic.
 #include <atomic>
 
+#include "fp4_call.h"
 #include "launchers.h"
 #include "mfma_common.h"
 
@@ -454,44 +455,29 @@ std::atomic<int> g_wide_cfg{-1};  // -1 heuristic; 0 = never (16-row launches); 
                                   // 5 = 16 rows, self-contained waves (up to 32 activation rows, else as 1)
 
 template <int DT, int NT>
-int dispatch_wide_cfg(int cfg, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                      int B, int M, int K, int mode, hipStream_t stream) {
-    const unsigned rows = (cfg == 1 || cfg == 5) ? 16u : (cfg == 2 ? 32u : (cfg == 3 ? 64u : 128u));
-    const dim3 grid(((unsigned)M + rows - 1) / rows);
-#define FP4_WIDE_ARGS reinterpret_cast<const uint16_t *>(x), W, absmax, reinterpret_cast<const uint16_t *>(bias), \
-                      reinterpret_cast<const uint16_t *>(residual), reinterpret_cast<uint16_t *>(out), B, M, K, mode
+int dispatch_wide_cfg(int cfg, const Fp4Call &c) {
+    const unsigned M = (unsigned)c.M, rows = (cfg == 1 || cfg == 5) ? 16u : (cfg == 2 ? 32u : (cfg == 3 ? 64u : 128u));
+    const dim3 grid((M + rows - 1) / rows);
     // 16 rows per workgroup: one or two column tiles (up to 32 activation rows) always take the barrier-free form - 5-17 % faster,
     // so the ring form is only built for three and four tiles (round 3); 128 rows per workgroup needs more than one column tile.
     if constexpr (NT <= 2) {
-        if (cfg == 5 || cfg == 1) {
-            hipLaunchKernelGGL((gemm16_wide_auto_kernel<DT, NT>), dim3(((unsigned)M + 15u) / 16u), dim3(512), 0, stream, FP4_WIDE_ARGS);
-            return FP4_OK;
-        }
+        if (cfg == 5 || cfg == 1) return launch_gemm16(gemm16_wide_auto_kernel<DT, NT>, dim3((M + 15u) / 16u), dim3(512), 0, c);
     } else {
-        if (cfg == 5 || cfg == 1) {
-            hipLaunchKernelGGL((gemm16_wide_ring8_kernel<DT, NT>), grid, dim3(640), 0, stream, FP4_WIDE_ARGS);
-            return FP4_OK;
-        }
+        if (cfg == 5 || cfg == 1) return launch_gemm16(gemm16_wide_ring8_kernel<DT, NT>, grid, dim3(640), 0, c);
     }
-    if (cfg == 2) {
-        hipLaunchKernelGGL((gemm16_wide_ring_kernel<DT, NT, 1>), grid, dim3(512), 0, stream, FP4_WIDE_ARGS);
-    } else if (cfg == 3 || NT == 1) {
-        hipLaunchKernelGGL((gemm16_wide_ring_kernel<DT, NT, 2>), dim3(((unsigned)M + 63u) / 64u), dim3(512), 0, stream, FP4_WIDE_ARGS);
-    } else {
-        if constexpr (NT >= 2) hipLaunchKernelGGL((gemm16_wide_ring_kernel<DT, NT, 4>), grid, dim3(512), 0, stream, FP4_WIDE_ARGS);
-    }
-#undef FP4_WIDE_ARGS
+    if (cfg == 2) return launch_gemm16(gemm16_wide_ring_kernel<DT, NT, 1>, grid, dim3(512), 0, c);
+    if (cfg == 3 || NT == 1) return launch_gemm16(gemm16_wide_ring_kernel<DT, NT, 2>, dim3((M + 63u) / 64u), dim3(512), 0, c);
+    if constexpr (NT >= 2) launch_gemm16(gemm16_wide_ring_kernel<DT, NT, 4>, grid, dim3(512), 0, c);
     return FP4_OK;
 }
 
 template <int DT>
-int dispatch_wide(int cfg, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, int B,
-                  int M, int K, int mode, hipStream_t stream) {
-    const int nt = (B + 15) / 16;
-    if (nt == 1) return dispatch_wide_cfg<DT, 1>(cfg, x, W, absmax, bias, residual, out, B, M, K, mode, stream);
-    if (nt == 2) return dispatch_wide_cfg<DT, 2>(cfg, x, W, absmax, bias, residual, out, B, M, K, mode, stream);
-    if (nt == 3) return dispatch_wide_cfg<DT, 3>(cfg, x, W, absmax, bias, residual, out, B, M, K, mode, stream);
-    return dispatch_wide_cfg<DT, 4>(cfg, x, W, absmax, bias, residual, out, B, M, K, mode, stream);
+int dispatch_wide(int cfg, const Fp4Call &c) {
+    const int nt = ((int)c.B + 15) / 16;
+    if (nt == 1) return dispatch_wide_cfg<DT, 1>(cfg, c);
+    if (nt == 2) return dispatch_wide_cfg<DT, 2>(cfg, c);
+    if (nt == 3) return dispatch_wide_cfg<DT, 3>(cfg, c);
+    return dispatch_wide_cfg<DT, 4>(cfg, c);
 }
 
 }  // namespace
@@ -501,8 +487,8 @@ void set_wide_variant(int v) { g_wide_cfg = v < 0 ? -1 : (v > 5 ? 5 : v); }
 // 17..64 activation rows (any_rows: 1..64 - the caller's other kernels do not cover the shape), 16-bit dtype, blocksize 64,
 // K % 64 == 0, 16-byte aligned operands.  Returns FP4_OK after the launch, or -1 when the shape is not covered / the path is switched
 // off (the caller then streams the weight once per 16 rows).
-int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                     int B, int M, int K, int mode, bool any_rows, hipStream_t stream) {
+int gemm_wide_launch(const Fp4Call &c, bool any_rows) {
+    const int B = (int)c.B, M = (int)c.M, K = (int)c.K;  // the caller has bounded them
     int cfg = g_wide_cfg.load(std::memory_order_relaxed);
     if (cfg == 0 || B < 1 || (B <= 16 && !any_rows) || B > 64 || (K % 64) != 0 || M < 1) return -1;
     if ((uint64_t)B * (uint64_t)K * 2u >= (uint64_t(1) << 32)) return -1;  // 32-bit x offsets
@@ -516,8 +502,7 @@ int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *ab
             cfg = M >= 96 * cus ? 4 : (M >= 48 * cus ? 3 : (M >= 24 * cus ? 2 : 1));
         if (cfg == 1 && B <= 32) cfg = 5;  // 16 rows per workgroup, one or two column tiles: the barrier-free form (5-17 % faster)
     }
-    return dtype == FP4_DTYPE_F16 ? dispatch_wide<FP4_DTYPE_F16>(cfg, x, W, absmax, bias, residual, out, B, M, K, mode, stream)
-                                  : dispatch_wide<FP4_DTYPE_BF16>(cfg, x, W, absmax, bias, residual, out, B, M, K, mode, stream);
+    return with_dtype(c.dtype, [&](auto dt) { return dispatch_wide<decltype(dt)::value>(cfg, c); });
 }
 
 }  // namespace fp4

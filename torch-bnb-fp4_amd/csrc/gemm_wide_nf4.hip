@@ -361,7 +361,7 @@ extern "C" int fp4_hip_gemm_wide_nf4(const void *x, const uint8_t *packed, const
 extern "C" int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                       void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemm_fused_nf4";
-    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    const int mode = fp4::epilogue_mode(name, epilogue);
     if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
     return fp4::gemm_wide_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .B = B,
                                            .M = M, .K = K, .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true,
@@ -372,7 +372,7 @@ extern "C" int fp4_hip_gemm_lora_nf4(const void *x, const uint8_t *packed, const
                                      const void *lora_B, const float *t, int64_t R, void *out, int64_t B, int64_t M, int64_t K,
                                      int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemm_lora_nf4";
-    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    const int mode = fp4::epilogue_mode(name, epilogue);
     if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
     return fp4::gemm_wide_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .B = B,
                                            .M = M, .K = K, .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true,
@@ -384,7 +384,7 @@ extern "C" int fp4_hip_gemm_lora_multi_nf4(const void *x, const uint8_t *packed,
                                            const void *B_stack, const int32_t *ids, int64_t n_adapters, const float *t, int64_t R, void *out,
                                            int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemm_lora_multi_nf4";
-    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    const int mode = fp4::epilogue_mode(name, epilogue);
     if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
     return fp4::gemm_wide_nf4_entry(
         name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .B = B, .M = M, .K = K,

@@ -30,7 +30,7 @@
 // (the 2..64-row small-batch kernels built on the same decode live in gemm_small_fp4.hip)
 #include <atomic>
 
-#include "gemv_common.h"
+#include "fp4_call.h"
 #include "launchers.h"
 
 #ifdef FP4_EXP_STAMPS
@@ -559,22 +559,24 @@ __global__ __launch_bounds__(256) void gemv32_regx_kernel(const float *__restric
     }
 }
 
-template <int KSPLIT, int G, int ITERS>
-int launch32_regx(const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, int M,
-                  int K, int bs_shift, hipStream_t stream) {
-    constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
-    const unsigned blocks = (unsigned)((M + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL((gemv32_regx_kernel<KSPLIT, G, ITERS>), dim3(blocks), dim3(256), 0, stream,
-                       reinterpret_cast<const float *>(x), W, absmax, reinterpret_cast<const float *>(bias),
-                       reinterpret_cast<const float *>(residual), reinterpret_cast<float *>(out), M, K, bs_shift);
+// the one launch of the f32 family (gemv32_kernel, gemv32_regx_kernel): their argument list, spelt here only
+template <typename Kern>
+int launch_gemv32(Kern kern, dim3 grid, dim3 block, size_t lds, const Fp4Call &c) {
+    hipLaunchKernelGGL(kern, grid, block, lds, c.stream, static_cast<const float *>(c.x), c.W, c.absmax, static_cast<const float *>(c.bias),
+                       static_cast<const float *>(c.residual), static_cast<float *>(c.out), (int)c.M, (int)c.K, c.bs_shift());
     return FP4_OK;
+}
+
+template <int KSPLIT, int G, int ITERS>
+int launch32_regx(const Fp4Call &c) {
+    constexpr int rows_per_block = 2 * (4 / KSPLIT) * ITERS;
+    return launch_gemv32(gemv32_regx_kernel<KSPLIT, G, ITERS>, dim3((unsigned)((c.M + rows_per_block - 1) / rows_per_block)), dim3(256), 0, c);
 }
 
 // returns -1 when K is too deep for a register-resident f32 x slice (K > 8192): use the LDS kernel
 // (round 3: the table-free decode - 10 % faster, but outside parity bar 2 in f32 - and 8 row pairs per group are no longer built)
-int dispatch32_regx(int iters, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                    int M, int K, int bs_shift, hipStream_t stream) {
-    const int C = K >> 5;
+int dispatch32_regx(int iters, const Fp4Call &c) {
+    const int M = (int)c.M, C = (int)c.K >> 5;
     const int ks = C <= 32 ? 1 : (C <= 64 ? 2 : 4);
     if (iters <= 0) {
         // the f32 x slice is 128 B per chunk per lane, re-read by every workgroup: amortise it over more rows than
@@ -583,11 +585,11 @@ int dispatch32_regx(int iters, const void *x, const uint8_t *W, const float *abs
         iters = 1;
         while (iters < 4 && M / (2 * (4 / ks) * iters * 2) >= 256) iters *= 2;
     }
-#define FP4_R32(KS, GG)                                                                                                   \
-    switch (iters) {                                                                                                      \
-        case 1: return launch32_regx<KS, GG, 1>(x, W, absmax, bias, residual, out, M, K, bs_shift, stream);        \
-        case 2: return launch32_regx<KS, GG, 2>(x, W, absmax, bias, residual, out, M, K, bs_shift, stream);        \
-        default: return launch32_regx<KS, GG, 4>(x, W, absmax, bias, residual, out, M, K, bs_shift, stream);       \
+#define FP4_R32(KS, GG)                              \
+    switch (iters) {                                 \
+        case 1: return launch32_regx<KS, GG, 1>(c);  \
+        case 2: return launch32_regx<KS, GG, 2>(c);  \
+        default: return launch32_regx<KS, GG, 4>(c); \
     }
     if (C <= 32) { FP4_R32(1, 1) }
     if (C <= 64) { FP4_R32(2, 1) }
@@ -654,38 +656,30 @@ int ensure_lds(Kern kern, size_t lds_bytes) {
     return FP4_OK;
 }
 
-// one 16-bit GEMV launch: operands, epilogue inputs and the mode flags of gemv_common.h
-struct GemvArgs {
-    const void *x;
-    const uint8_t *W;
-    const float *absmax;
-    const void *bias, *residual;
-    void *out;
-    int M, K, bs_shift, mode;
-    hipStream_t stream;
-};
-
-template <int DT, int ROWS, int WAVES, int UNROLL>
-int launch16(const GemvArgs &a) {
-    if (a.mode & kModeSiluMulPairs) return -2;  // a pair's rows sit in different waves here
-    auto kern = gemv16_kernel<DT, ROWS, WAVES, UNROLL>;
-    const int M = a.M, K = a.K;
-    const size_t lds = size_t(K) * 2;
-    if (int rc = ensure_lds(kern, lds)) return rc;
-    const int rows_per_block = ROWS * WAVES;
-    const unsigned blocks = (unsigned)((M + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVES * 64), lds, a.stream, reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax,
-                       reinterpret_cast<const uint16_t *>(a.bias), reinterpret_cast<const uint16_t *>(a.residual),
-                       reinterpret_cast<uint16_t *>(a.out), M, K, a.bs_shift, a.mode);
+// the one launch of the 16-bit family (gemv16_kernel, gemv16_regx_kernel): their argument list, spelt here only
+template <typename Kern>
+int launch_gemv16(Kern kern, dim3 grid, dim3 block, size_t lds, const Fp4Call &c) {
+    hipLaunchKernelGGL(kern, grid, block, lds, c.stream, c.x16(), c.W, c.absmax, c.bias16(), c.residual16(), c.out16(), (int)c.M, (int)c.K,
+                       c.bs_shift(), c.mode);
     return FP4_OK;
 }
 
+template <int DT, int ROWS, int WAVES, int UNROLL>
+int launch16(const Fp4Call &c) {
+    if (c.gated()) return -2;  // a pair's rows sit in different waves here
+    auto kern = gemv16_kernel<DT, ROWS, WAVES, UNROLL>;
+    const size_t lds = size_t(c.K) * 2;
+    if (int rc = ensure_lds(kern, lds)) return rc;
+    const int rows_per_block = ROWS * WAVES;
+    return launch_gemv16(kern, dim3((unsigned)((c.M + rows_per_block - 1) / rows_per_block)), dim3(WAVES * 64), lds, c);
+}
+
 template <int DT>
-int dispatch16(int variant, const GemvArgs &a) {
+int dispatch16(int variant, const Fp4Call &c) {
     switch (variant) {
 #define FP4_V(R, Wv, U)                  \
     case (R | (Wv << 8) | (U << 16)):    \
-        return launch16<DT, R, Wv, U>(a);
+        return launch16<DT, R, Wv, U>(c);
         // (1, 8, 2) is what K > 16384 falls back to; (1, 4, 2) is the north-star mapping at the reference's 4 rows per block.
         // Round 3 removed (1,4,1) (2,4,2) (2,8,2) (1,16,2): sweep-only, behind the register-x geometry at every measured shape
         // (profiles/r01_b_exp_gemv_geometries.txt, profiles/r03_kernel_inventory.txt)
@@ -700,22 +694,18 @@ int dispatch16(int variant, const GemvArgs &a) {
 constexpr int kRegxFlag = 1 << 24;
 
 template <int DT, int KSPLIT, int G, int ITERS, int WAVES = 4>
-int launch_regx(const GemvArgs &a) {
+int launch_regx(const Fp4Call &c) {
     constexpr int rows_per_block = 2 * (WAVES / KSPLIT) * ITERS;
-    const unsigned blocks = (unsigned)((a.M + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL((gemv16_regx_kernel<DT, KSPLIT, G, ITERS, WAVES>), dim3(blocks), dim3(WAVES * 64), 0, a.stream,
-                       reinterpret_cast<const uint16_t *>(a.x), a.W, a.absmax, reinterpret_cast<const uint16_t *>(a.bias),
-                       reinterpret_cast<const uint16_t *>(a.residual), reinterpret_cast<uint16_t *>(a.out), a.M, a.K, a.bs_shift,
-                       a.mode);
-    return FP4_OK;
+    return launch_gemv16(gemv16_regx_kernel<DT, KSPLIT, G, ITERS, WAVES>, dim3((unsigned)((c.M + rows_per_block - 1) / rows_per_block)),
+                         dim3(WAVES * 64), 0, c);
 }
 
 // K decides the band split and the x-slice depth; ITERS (row pairs per group) is the tunable.  `ks_override` selects the
 // 5 / 6 / 7 / 8-band geometries for the row lengths they were built for; G follows from ceil(C / (32 * KSPLIT)).
 template <int DT>
-int dispatch_regx(int iters, int ks_override, const GemvArgs &a) {
-    const int C = a.K >> 5;
-    if (int64_t(a.M) * a.K >= (int64_t(1) << 32)) return -1;  // 32-bit buffer offsets; the LDS geometry addresses with 64 bits
+int dispatch_regx(int iters, int ks_override, const Fp4Call &c) {
+    const int C = (int)c.K >> 5;
+    if (c.M * c.K >= (int64_t(1) << 32)) return -1;  // 32-bit buffer offsets; the LDS geometry addresses with 64 bits
     // K = 7 * 1024 * {1, 2, 4} (7168, 14336, 28672 - the Llama-3 / Mistral intermediate sizes): seven waves split the row into
     // seven bands, so no lane of a 32-chunk band is idle (4 bands leave an eighth of the deepest slice dead at 14336) and
     // 28672 still fits the register-resident x slice
@@ -723,19 +713,19 @@ int dispatch_regx(int iters, int ks_override, const GemvArgs &a) {
     // profiles/r01_f_gemv_seven_bands.txt, profiles/r02_gemv_regx_sweep.txt): 7168 -> 2 row pairs, 14336 -> 4, 28672 -> 2.
     if (ks_override == 7 && C % 224 == 0 && (C / 224 == 1 || C / 224 == 2 || C / 224 == 4)) {
         const int g7 = C / 224;
-        if (g7 == 1) return launch_regx<DT, 7, 1, 2, 7>(a);
-        if (g7 == 2) return launch_regx<DT, 7, 2, 4, 7>(a);
-        return launch_regx<DT, 7, 4, 2, 7>(a);
+        if (g7 == 1) return launch_regx<DT, 7, 1, 2, 7>(c);
+        if (g7 == 2) return launch_regx<DT, 7, 2, 4, 7>(c);
+        return launch_regx<DT, 7, 4, 2, 7>(c);
     }
     // five / six bands for rows of exactly 5 or 6 (x 1, 2) band widths: K = 5120 / 10240 (Llama-2-13B hidden size) and 6144 / 12288
     if ((ks_override == 5 && C % 160 == 0 && C / 160 <= 2) || (ks_override == 6 && C == 192)) {
         const int gg = C / (32 * ks_override);
         if (iters > 4) iters = 4;
-#define FP4_RXN(KS, GG)                                                                                               \
-    switch (iters) {                                                                                                  \
-        case 1: return launch_regx<DT, KS, GG, 1, KS>(a);      \
-        case 2: return launch_regx<DT, KS, GG, 2, KS>(a);      \
-        default: return launch_regx<DT, KS, GG, 4, KS>(a);     \
+#define FP4_RXN(KS, GG)                                   \
+    switch (iters) {                                      \
+        case 1: return launch_regx<DT, KS, GG, 1, KS>(c); \
+        case 2: return launch_regx<DT, KS, GG, 2, KS>(c); \
+        default: return launch_regx<DT, KS, GG, 4, KS>(c);\
     }
         if (ks_override == 5 && gg == 1) { FP4_RXN(5, 1) }
         if (ks_override == 5 && gg == 2) { FP4_RXN(5, 2) }
@@ -743,8 +733,8 @@ int dispatch_regx(int iters, int ks_override, const GemvArgs &a) {
 #undef FP4_RXN
     }
     if (ks_override == 8 && C == 256) {  // K = 8192 split 8 ways over 8 waves (the heuristic's choice from 4096 rows up)
-        if (iters >= 4) return launch_regx<DT, 8, 1, 4, 8>(a);
-        return launch_regx<DT, 8, 1, 2, 8>(a);
+        if (iters >= 4) return launch_regx<DT, 8, 1, 4, 8>(c);
+        return launch_regx<DT, 8, 1, 2, 8>(c);
     }
     const int ks = C <= 32 ? 1 : (C <= 64 ? 2 : 4);
     const int need = (C + 32 * ks - 1) / (32 * ks);
@@ -755,23 +745,17 @@ int dispatch_regx(int iters, int ks_override, const GemvArgs &a) {
     if (g >= 3 && iters > 2) iters = 2;
     if (iters == 3) iters = 2;
     if (iters < 1) iters = 1;
-#define FP4_RX(KS, GG, IT) return launch_regx<DT, KS, GG, IT>(a)
     // only the (KSPLIT, G, ITERS) triples the heuristic can reach are instantiated: the split follows K, G = 1, 2 -> 1, 2, 4 row pairs;
     // G >= 3 -> 1, 2 (round 3 removed 8 row pairs and the forced splits with deep slices: sweep-only, never ahead)
-#define FP4_RX_IT(KS, GG)                                    \
-    if (ks == KS && g == GG) {                               \
-        switch (iters) {                                     \
-            case 1: FP4_RX(KS, GG, 1);                       \
-            case 2: FP4_RX(KS, GG, 2);                       \
-            case 4:                                          \
-                if constexpr ((GG) <= 2) { FP4_RX(KS, GG, 4); } \
-                break;                                       \
-            default: break;                                  \
-        }                                                    \
+#define FP4_RX_IT(KS, GG)                                             \
+    if (ks == KS && g == GG) {                                        \
+        if (iters == 1) return launch_regx<DT, KS, GG, 1>(c);         \
+        if (iters == 2) return launch_regx<DT, KS, GG, 2>(c);         \
+        if constexpr ((GG) <= 2)                                      \
+            if (iters == 4) return launch_regx<DT, KS, GG, 4>(c);     \
     }
     FP4_RX_IT(1, 1) FP4_RX_IT(2, 1) FP4_RX_IT(4, 1) FP4_RX_IT(4, 2) FP4_RX_IT(4, 3) FP4_RX_IT(4, 4)
 #undef FP4_RX_IT
-#undef FP4_RX
     set_error("fp4_hip_gemv: unknown regx geometry (iters %d, ksplit %d, g %d)", iters, ks, g);
     return FP4_ERR_INVALID_ARGUMENT;
 }
@@ -812,11 +796,9 @@ int default_variant16(int M, int K) {
 }
 
 template <int DT>
-int run_generic(const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out, int64_t M,
-                int64_t K, int blocksize, int mode, hipStream_t stream, int table = FP4_TABLE_CODEBOOK) {
-    const CodeTable tbl = make_table(table);
-    hipLaunchKernelGGL((gemv_generic_kernel<DT>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, stream, x, W, absmax, bias,
-                       residual, out, (int)M, K, blocksize, tbl, mode);
+int run_generic(const Fp4Call &c, int table) {
+    hipLaunchKernelGGL((gemv_generic_kernel<DT>), dim3((unsigned)((c.M + 3) / 4)), dim3(256), 0, c.stream, c.x, c.W, c.absmax, c.bias,
+                       c.residual, c.out, (int)c.M, c.K, c.blocksize, make_table(table), c.mode);
     return FP4_OK;
 }
 
@@ -824,22 +806,15 @@ int run_generic(const void *x, const uint8_t *W, const float *absmax, const void
 
 void set_gemv_variant(int v) { g_gemv_variant.store(v, std::memory_order_relaxed); }
 
-// The generic kernel with another code table (the NF4 GEMV's path for irregular shapes, gemv_nf4.hip).
-int gemv_generic_table(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int64_t M, int64_t K,
-                       int blocksize, int dtype, int table, hipStream_t stream) {
-    switch (dtype) {
-        case FP4_DTYPE_F16: return run_generic<FP4_DTYPE_F16>(x, W, absmax, bias, nullptr, out, M, K, blocksize, 0, stream, table);
-        case FP4_DTYPE_BF16: return run_generic<FP4_DTYPE_BF16>(x, W, absmax, bias, nullptr, out, M, K, blocksize, 0, stream, table);
-        default: return run_generic<FP4_DTYPE_F32>(x, W, absmax, bias, nullptr, out, M, K, blocksize, 0, stream, table);
-    }
+// The generic kernel with `table` as its code: the FP4 GEMV's irregular shapes below, and with another table the NF4 GEMV's (gemv_nf4.hip).
+int gemv_generic_table(const Fp4Call &c, int table) {
+    return with_dtype<true>(c.dtype, [&](auto dt) { return run_generic<decltype(dt)::value>(c, table); });
 }
 
-}  // namespace fp4
-
-namespace fp4 {
 namespace {
-int gemv_entry(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual, void *out,
-               int64_t M, int64_t K, int blocksize, int dtype, int mode, void *stream) {
+int gemv_entry(const Fp4Call &c) {
+    const int64_t M = c.M, K = c.K;
+    const int blocksize = c.blocksize, dtype = c.dtype;
     if (M < 0 || K < 0 || (K & 1) || blocksize < 2 || (blocksize & 1)) {
         set_error("fp4_hip_gemv: M=%lld K=%lld blocksize=%d (need M,K >= 0, even K, even blocksize >= 2)", (long long)M,
                   (long long)K, blocksize);
@@ -850,12 +825,12 @@ int gemv_entry(const void *x, const uint8_t *packed, const float *absmax, const 
         set_error("fp4_hip_gemv: unsupported dtype %d", dtype);
         return FP4_ERR_UNSUPPORTED;
     }
-    if ((mode & kModeSiluMulPairs) && (M & 1)) {
+    if (c.gated() && (M & 1)) {
         set_error("fp4_hip_gemv_fused: the gate|up epilogue needs an even row count, got M=%lld", (long long)M);
         return FP4_ERR_INVALID_ARGUMENT;
     }
     if (M == 0) return FP4_OK;
-    if (!out || (K > 0 && (!x || !packed || !absmax))) {
+    if (!c.out || (K > 0 && (!c.x || !c.W || !c.absmax))) {
         set_error("fp4_hip_gemv: null pointer");
         return FP4_ERR_INVALID_ARGUMENT;
     }
@@ -863,52 +838,35 @@ int gemv_entry(const void *x, const uint8_t *packed, const float *absmax, const 
         set_error("fp4_hip_gemv: M=%lld K=%lld too large", (long long)M, (long long)K);
         return FP4_ERR_UNSUPPORTED;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int bs_shift = ilog2_exact(blocksize);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(x);
+    const uintptr_t align = reinterpret_cast<uintptr_t>(c.W) | reinterpret_cast<uintptr_t>(c.x);
     const size_t esz = dtype == FP4_DTYPE_F32 ? 4 : 2;
-    const bool fast = K > 0 && (K % 32) == 0 && bs_shift >= 5 && (K % blocksize) == 0 && (align & 15u) == 0 &&
+    const bool fast = K > 0 && (K % 32) == 0 && c.bs_shift() >= 5 && (K % blocksize) == 0 && (align & 15u) == 0 &&
                       size_t(K) * esz <= size_t(kMaxLdsBytes);
     int rc = FP4_OK;
     const int gv = g_gemv_variant.load(std::memory_order_relaxed);  // one snapshot per call
     if (fast && dtype != FP4_DTYPE_F32) {
-        const GemvArgs a{x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, mode, s};
         int variant = gv >= 0 ? gv : default_variant16((int)M, (int)K);
         rc = -1;
         if (variant & kRegxFlag) {
             const int iters = variant & 0xFF, ks_override = (variant >> 8) & 0xF;
-            rc = dtype == FP4_DTYPE_F16 ? dispatch_regx<FP4_DTYPE_F16>(iters, ks_override, a)
-                                        : dispatch_regx<FP4_DTYPE_BF16>(iters, ks_override, a);
+            rc = with_dtype(dtype, [&](auto dt) { return dispatch_regx<decltype(dt)::value>(iters, ks_override, c); });
             if (rc == -1) variant = 1 | (8 << 8) | (2 << 16);  // K too large for register-resident x
         }
-        if (rc == -1) rc = dtype == FP4_DTYPE_F16 ? dispatch16<FP4_DTYPE_F16>(variant, a) : dispatch16<FP4_DTYPE_BF16>(variant, a);
-    } else if (mode & kModeSiluMulPairs) {
+        if (rc == -1) rc = with_dtype(dtype, [&](auto dt) { return dispatch16<decltype(dt)::value>(variant, c); });
+    } else if (c.gated()) {
         rc = -2;  // f32 activations / irregular shapes: only the register-x geometry pairs rows up
     } else if (fast && gv != 0 &&
                // the bit-faithful CODE_PARAM f32 table (the all-f32 reference kernel is accurate to ~1e-7, so the table's 1e-6
                // deviations from k/12 are visible at f32)
-               dispatch32_regx(gv < 0 ? 0 : (gv & 0xFF), x, packed, absmax, bias, residual, out, (int)M, (int)K, bs_shift, s) == FP4_OK) {
+               dispatch32_regx(gv < 0 ? 0 : (gv & 0xFF), c) == FP4_OK) {
         rc = FP4_OK;  // f32 activations, register-x geometry (variant 0 forces the LDS kernel below, for sweeps)
     } else if (fast) {
         auto kern = gemv32_kernel<1, 4>;
         const size_t lds = size_t(K) * 4;
         rc = ensure_lds(kern, lds);
-        if (rc == FP4_OK)
-            hipLaunchKernelGGL(kern, dim3((unsigned)((M + 3) / 4)), dim3(256), lds, s, reinterpret_cast<const float *>(x),
-                               packed, absmax, reinterpret_cast<const float *>(bias), reinterpret_cast<const float *>(residual),
-                               reinterpret_cast<float *>(out), (int)M, (int)K, bs_shift);
+        if (rc == FP4_OK) launch_gemv32(kern, dim3((unsigned)((M + 3) / 4)), dim3(256), lds, c);
     } else {
-        switch (dtype) {
-            case FP4_DTYPE_F16:
-                rc = run_generic<FP4_DTYPE_F16>(x, packed, absmax, bias, residual, out, M, K, blocksize, mode, s);
-                break;
-            case FP4_DTYPE_BF16:
-                rc = run_generic<FP4_DTYPE_BF16>(x, packed, absmax, bias, residual, out, M, K, blocksize, mode, s);
-                break;
-            default:
-                rc = run_generic<FP4_DTYPE_F32>(x, packed, absmax, bias, residual, out, M, K, blocksize, mode, s);
-                break;
-        }
+        rc = gemv_generic_table(c, FP4_TABLE_CODEBOOK);
     }
     if (rc == -2) {
         set_error("fp4_hip_gemv_fused: the gate|up epilogue is not available for M=%lld K=%lld blocksize=%d dtype=%d "
@@ -924,20 +882,20 @@ int gemv_entry(const void *x, const uint8_t *packed, const float *absmax, const 
 
 extern "C" int fp4_hip_gemv(const void *x, const uint8_t *packed, const float *absmax, const void *bias, void *out,
                             int64_t M, int64_t K, int blocksize, int dtype, void *stream) {
-    return fp4::gemv_entry(x, packed, absmax, bias, nullptr, out, M, K, blocksize, dtype, 0, stream);
+    return fp4::gemv_entry({.x = x, .W = packed, .absmax = absmax, .bias = bias, .out = out, .M = M, .K = K, .blocksize = blocksize,
+                            .dtype = dtype, .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int fp4_hip_gemv_fused(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                   void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        fp4::set_error("fp4_hip_gemv_fused: unknown epilogue %d", epilogue);
-        return FP4_ERR_INVALID_ARGUMENT;
-    }
-    return fp4::gemv_entry(x, packed, absmax, bias, residual, out, M, K, blocksize, dtype,
-                           epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? fp4::kModeSiluMulPairs : 0, stream);
+    const int mode = fp4::epilogue_mode("fp4_hip_gemv_fused", epilogue);
+    if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
+    return fp4::gemv_entry({.x = x, .W = packed, .absmax = absmax, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
+                            .blocksize = blocksize, .dtype = dtype, .mode = mode, .stream = static_cast<hipStream_t>(stream)});
 }
 
 extern "C" int fp4_hip_gemv_partial(const void *x, const uint8_t *packed, const float *absmax, float *out_f32, int64_t M,
                                     int64_t K, int blocksize, int x_dtype, void *stream) {
-    return fp4::gemv_entry(x, packed, absmax, nullptr, nullptr, out_f32, M, K, blocksize, x_dtype, fp4::kModeOutF32, stream);
+    return fp4::gemv_entry({.x = x, .W = packed, .absmax = absmax, .out = out_f32, .M = M, .K = K, .blocksize = blocksize,
+                            .dtype = x_dtype, .mode = fp4::kModeOutF32, .stream = static_cast<hipStream_t>(stream)});
 }

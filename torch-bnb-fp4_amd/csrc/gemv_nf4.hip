@@ -406,7 +406,8 @@ int gemv_nf4_entry(const char *name, const Nf4Call &c) {
     if (fast)
         dispatch_nf4(g_gemv_nf4_variant.load(std::memory_order_relaxed) == 1, c);
     else  // the plain form only
-        gemv_generic_table(c.x, c.W, static_cast<const float *>(c.scales), c.bias, c.out, M, K, blocksize, dtype, FP4_TABLE_NF4, c.stream);
+        gemv_generic_table({.x = c.x, .W = c.W, .absmax = static_cast<const float *>(c.scales), .bias = c.bias, .out = c.out, .M = M, .K = K,
+                            .blocksize = blocksize, .dtype = dtype, .stream = c.stream}, FP4_TABLE_NF4);
     return check_launch(name);
 }
 
@@ -425,7 +426,7 @@ extern "C" int fp4_hip_gemv_nf4(const void *x, const uint8_t *packed, const floa
 extern "C" int fp4_hip_gemv_fused_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
                                       void *out, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemv_fused_nf4";
-    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    const int mode = fp4::epilogue_mode(name, epilogue);
     if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
     return fp4::gemv_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
                                       .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true,
@@ -436,7 +437,7 @@ extern "C" int fp4_hip_gemv_lora_nf4(const void *x, const uint8_t *packed, const
                                      const void *lora_B, const float *t, int64_t R, void *out, int64_t M, int64_t K, int blocksize,
                                      int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemv_lora_nf4";
-    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    const int mode = fp4::epilogue_mode(name, epilogue);
     if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
     return fp4::gemv_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
                                       .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true, .stream = static_cast<hipStream_t>(stream),
@@ -447,7 +448,7 @@ extern "C" int fp4_hip_gemv_lora_multi_nf4(const void *x, const uint8_t *packed,
                                            const void *B_stack, const int32_t *ids, int64_t n_adapters, const float *t, int64_t R, void *out,
                                            int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream) {
     const char *name = "fp4_hip_gemv_lora_multi_nf4";
-    const int mode = fp4::nf4_epilogue_mode(name, epilogue);
+    const int mode = fp4::epilogue_mode(name, epilogue);
     if (mode < 0) return FP4_ERR_INVALID_ARGUMENT;
     return fp4::gemv_nf4_entry(name, {.x = x, .W = packed, .scales = absmax, .bias = bias, .residual = residual, .out = out, .M = M, .K = K,
                                       .blocksize = blocksize, .dtype = dtype, .mode = mode, .fused = true, .stream = static_cast<hipStream_t>(stream),

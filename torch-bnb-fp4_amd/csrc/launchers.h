@@ -13,14 +13,12 @@ struct Nf4Call;  // nf4_call.h
 void gemm_small_nf4_launch(const Nf4Call &call);
 
 // gemv_fp4.hip, for the plain NF4 GEMV's irregular shapes (gemv_nf4.hip): the generic kernel with `table` as its code
-int gemv_generic_table(const void *x, const uint8_t *W, const float *absmax, const void *bias, void *out, int64_t M, int64_t K,
-                       int blocksize, int dtype, int table, hipStream_t stream);
+struct Fp4Call;  // fp4_call.h
+int gemv_generic_table(const Fp4Call &call, int table);
 
 // gemm_wide_fp4.hip, gemm_splitk_fp4.hip, for gemm_small_fp4.hip: FP4_OK after the launch, -1 where the shape is not theirs
-int gemm_wide_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                     int B, int M, int K, int mode, bool any_rows, hipStream_t stream);
-int gemm_splitk_launch(int dtype, const void *x, const uint8_t *W, const float *absmax, const void *bias, const void *residual, void *out,
-                       int B, int M, int K, int mode, void *workspace, int64_t workspace_bytes, hipStream_t stream);
+int gemm_wide_launch(const Fp4Call &call, bool any_rows);
+int gemm_splitk_launch(const Fp4Call &call);
 int64_t gemm_splitk_workspace_bytes(int64_t B, int64_t M, int64_t K, int blocksize, int dtype);
 
 // sweep hooks behind fp4_hip_set_variant (capi.hip), each defined beside the kernels it steers

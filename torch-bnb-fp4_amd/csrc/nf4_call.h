@@ -12,9 +12,7 @@
 // part in the new extern "C" functions.  The entry functions change only where the form needs a check of its own.
 #pragma once
 
-#include <type_traits>
-
-#include "gemv_common.h"
+#include "fp4_call.h"  // with_dtype, epilogue_mode: shared with the FP4 half
 #include "lora_nf4.h"
 #include "nested_absmax.h"
 
@@ -74,25 +72,6 @@ inline void with_nf4_form(const Nf4Call &c, F &&f) {
         c.fused ? f(Nf4Form<kNf4Fused>{}) : f(Nf4Form<0>{});
 }
 
-// runtime dtype (validated: fp16 or bf16, with WITH_F32 also f32) -> template argument: f(std::integral_constant<int, FP4_DTYPE_*>{})
-template <bool WITH_F32 = false, typename F>
-inline void with_dtype(int dtype, F &&f) {
-    if (dtype == FP4_DTYPE_F16) return f(std::integral_constant<int, FP4_DTYPE_F16>{});
-    if constexpr (WITH_F32) {
-        if (dtype == FP4_DTYPE_F32) return f(std::integral_constant<int, FP4_DTYPE_F32>{});
-    }
-    f(std::integral_constant<int, FP4_DTYPE_BF16>{});
-}
-
-// `epilogue` of the C ABI -> the kernels' `mode`, or -1 with the message set (the caller returns FP4_ERR_INVALID_ARGUMENT)
-inline int nf4_epilogue_mode(const char *name, int epilogue) {
-    if (epilogue != FP4_EPILOGUE_NONE && epilogue != FP4_EPILOGUE_SILU_MUL_PAIRS) {
-        set_error("%s: unknown epilogue %d", name, epilogue);
-        return -1;
-    }
-    return epilogue == FP4_EPILOGUE_SILU_MUL_PAIRS ? kModeSiluMulPairs : 0;
-}
-
 // The adapter's own check, after the operands': FP4_OK (also without an adapter), or the status to return with the message set
 inline int nf4_check_adapter(const char *name, const Nf4Call &c) {
     const Nf4Call::Adapter &a = c.adapter;
@@ -133,7 +112,7 @@ inline int nf4_check_args(const char *name, const Nf4Call &c, int max_rows, int 
 // c.mode), then the statistics.  FP4_OK, or the status to return with the message set.  `kind` is what reads the groups ("GEMV",
 // "GEMM"), `plain_op` the entry point to run on the expanded statistics instead.
 inline int nested_check_args(const char *name, const char *kind, const char *plain_op, int epilogue, int nested_blocksize, Nf4Call &c) {
-    if ((c.mode = nf4_epilogue_mode(name, epilogue)) < 0) return FP4_ERR_INVALID_ARGUMENT;
+    if ((c.mode = epilogue_mode(name, epilogue)) < 0) return FP4_ERR_INVALID_ARGUMENT;
     if (nested_blocksize <= 0) {
         set_error("%s: nested_blocksize=%d (need a positive group size)", name, nested_blocksize);
         return FP4_ERR_INVALID_ARGUMENT;
