@@ -8,7 +8,9 @@ import torch
 import fp4_constructed as C
 from oracle import fp4_oracle as o
 
-SHAPES = [(257, 64, 64), (257, 512, 64), (33, 4096, 64), (257, 1472, 64), (9, 32768, 64), (37, 96, 32), (17, 8256, 64)]
+SHAPES = [(257, 64, 64), (257, 512, 64), (33, 4096, 64), (257, 1472, 64), (9, 32768, 64), (37, 96, 32), (17, 8256, 64),
+          # the VALU small-batch kernel's families at other block sizes (test_gpu_fp4_constructed.VALU_BLOCKSIZES, M = its M_PLACE)
+          (257, 96, 32), (257, 256, 128), (257, 512, 256), (257, 4096, 4096)]
 DT16 = ["bfloat16", "float16"]
 
 
@@ -37,6 +39,24 @@ def test_the_weight_runs_through_every_byte_and_the_scales_differ_between_neighb
     assert (am[1:] != am[:-1]).all() and (am[:, 1:] != am[:, :-1]).all()
     assert C.one_hot_positions(4096)[:64] == list(range(64)) and {2047, 2048, 4031, 4032, 4094, 4095} <= set(C.one_hot_positions(4096))
     assert C.one_hot_positions(64) == list(range(64))
+
+
+@pytest.mark.parametrize("K,bs", [(96, 32), (256, 128), (512, 256), (4096, 4096)])
+def test_a_wrong_scale_index_shows_as_a_wrong_power_of_two(K, bs):
+    """The runtime-blocksize families: every block of a row is reached by a one-hot position, and the scale an index off by one would
+    read - the next block's, the next row's, the flat neighbour across a row end - is another power of two."""
+    M = 257
+    am = C.placement_scales(M, K, bs).reshape(M, K // bs)
+    assert {k // bs for k in C.one_hot_positions(K)} == set(range(K // bs))
+    assert (am[1:] != am[:-1]).all() and (am[:, 1:] != am[:, :-1]).all()
+    flat = am.reshape(-1)
+    assert (flat[1:] != flat[:-1]).all()
+    assert (np.log2(am) == np.round(np.log2(am))).all()
+    # a shift off by one (blocks twice or half as long) reads another scale wherever the index changes
+    nb = K // bs
+    if nb > 1:
+        j = np.arange(nb)
+        assert (am[:, j // 2] != am[:, j])[:, 1:].all()
 
 
 @pytest.mark.parametrize("M,K,bs", SHAPES)

@@ -150,7 +150,7 @@ def test_placement_gemv_partial(K, dtype):
     gemv_one_hot("gemv_partial default", M_PLACE, K, dtype, None, partial=True)
 
 
-def batch_one_hot(family, M, K, B, dtype, call):
+def batch_one_hot(family, M, K, B, dtype, call, bs=BS):
     """B one-hot rows per launch over the same positions; then the first launch again with x at a 16-byte offset inside a larger
     buffer, which must give the same bits."""
     pos, val = C.one_hot_batches(K, B)
@@ -159,7 +159,7 @@ def batch_one_hot(family, M, K, B, dtype, call):
     OUT = sentinel_filled((L, pad16(B * M)), dtype)
     for l in range(L):
         call(x[l], OUT[l, :B * M].view(B, M))
-    exact = C.closed_form(M, K, pos, val)
+    exact = C.closed_form(M, K, pos, val, bs)
     y = OUT[:, :B * M].reshape(L, B, M)
     got = report("placement", f"{family} B{B} M{M} K{K}", dtype, y, exact, np.abs(exact))
     assert (got[exact == 0] == 0).all()
@@ -171,12 +171,12 @@ def batch_one_hot(family, M, K, B, dtype, call):
     assert torch.equal(again, y[0])
 
 
-def small_call(M, K, **variants):
-    P, A = placement_weight(M, K)
+def small_call(M, K, bs=BS, **variants):
+    P, A = placement_weight(M, K, bs)
 
     def call(x, out):
         with forced(**variants):
-            hipabi.gemm_small(x, P, A, M, K, BS, out=out)
+            hipabi.gemm_small(x, P, A, M, K, bs, out=out)
     return call
 
 
@@ -196,6 +196,20 @@ def test_placement_small_batch(family, variant, M, K, rows, dtype):
     fragments straight from global (bit 9), and K % 512 != 0 in the default dispatch (one-pass kernels with a ragged last step)."""
     for B in rows:
         batch_one_hot(f"small {family}", M, K, B, dtype, small_call(M, K, gemm_small=variant))
+
+
+VALU_BLOCKSIZES = [(96, 32), (256, 128), (512, 256), (4096, 4096)]  # (K, blocksize): 3 scales a row .. 1; four chunks a scale .. 128
+
+
+@pytest.mark.parametrize("dtype", DT16, ids=lambda d: NPDT[d])
+def test_placement_small_batch_valu_kernel_at_other_blocksizes(dtype):
+    """gemm16_small_kernel (variant 0 forced) takes the blocksize at run time and reads its scale through a buffer descriptor at
+    chunk >> (log2(blocksize) - 5); everything above runs it at 64.  The placement scales of neighbouring blocks and of neighbouring rows
+    differ by a power of two, so a wrong shift or a wrong descriptor size shows as a wrong power of two (or as the 0 of a load the
+    descriptor clamped).  This is the kernel a layer of such a blocksize reaches under small_batch_fused."""
+    for K, bs in VALU_BLOCKSIZES:
+        for B in (2, 5, 8):
+            batch_one_hot(f"small valu bs{bs}", M_PLACE, K, B, dtype, small_call(M_PLACE, K, bs, gemm_small=0), bs)
 
 
 @pytest.mark.parametrize("dtype", DT16, ids=lambda d: NPDT[d])

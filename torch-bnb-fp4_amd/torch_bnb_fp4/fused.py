@@ -33,7 +33,7 @@ from torch import nn
 
 from ._ext import ext
 from .nn import QuantState, fp4_code, nf4_code
-from .quant_data import QuantData
+from .quant_data import QuantData, aligned16, small_fp4_covers
 
 EPILOGUE_NONE = 0
 EPILOGUE_SILU_MUL_PAIRS = 1
@@ -170,9 +170,12 @@ class FusedFP4Linear(nn.Module):
     _batched_op = "gemm_small_fp4_fused"
 
     def _batched_covers(self, rows: int, K: int, dtype: torch.dtype) -> bool:
-        qd = self.quant_data
-        return (2 <= rows <= 128 and dtype in (torch.float16, torch.bfloat16)
-                and ((qd.blocksize == 64 and K % 64 == 0) or (rows <= 8 and K % qd.blocksize == 0 and K % 32 == 0 and K <= 4096)))
+        return small_fp4_covers(rows, K, self.quant_data.blocksize, dtype)
+
+    def _gemv_wants_alignment(self) -> bool:
+        """Whether the GEMV op refuses an activation off a 16-byte boundary (then it gets a copy).  ``fp4_hip_gemv_fused`` refuses it for
+        gate|up only: with the plain epilogue it runs its generic kernel on any address, and keeps doing so."""
+        return self.epilogue == EPILOGUE_SILU_MUL_PAIRS
 
     def _residual_in_kernel(self, rows: int, K: int) -> bool:
         """Whether the batched op adds the residual itself; where it does not, torch adds it to the op's output - T(t + r) either way."""
@@ -191,7 +194,11 @@ class FusedFP4Linear(nn.Module):
         self._fix_compute_dtype(x)
         if (self._fused_ok and x.numel() == K and K == self.in_features and x.ndim in (2, 3) and K % qd.blocksize == 0
                 and x.dtype == qd.o_type):
-            if not x.is_contiguous():
+            # an address belongs to the call: where the op would refuse it the call is made coverable, so that the refusals caught
+            # below, which switch a route off for the life of the layer, are about the shape alone
+            if self._gemv_wants_alignment():
+                x = aligned16(x)
+            elif not x.is_contiguous():
                 x = x.contiguous()
             try:
                 return getattr(ext, self._gemv_op)(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual, self.epilogue)
@@ -203,7 +210,7 @@ class FusedFP4Linear(nn.Module):
         if self._small_ok and K == self.in_features and x.dtype == qd.o_type and self._batched_covers(rows, K, x.dtype):
             in_kernel = residual is not None and self._residual_in_kernel(rows, K)
             try:  # batched decode: the same epilogues on the small-batch kernels
-                y = getattr(ext, self._batched_op)(x.contiguous(), qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias,
+                y = getattr(ext, self._batched_op)(aligned16(x), qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias,
                                                    residual if in_kernel else None, self.epilogue)
                 return y if in_kernel or residual is None else y + residual
             except RuntimeError as exc:
@@ -239,6 +246,9 @@ class FusedNF4Linear(FusedFP4Linear):
 
     def _batched_covers(self, rows: int, K: int, dtype: torch.dtype) -> bool:
         return 2 <= rows <= 64 and dtype in (torch.float16, torch.bfloat16) and self.quant_data.blocksize == 64 and K % 64 == 0
+
+    def _gemv_wants_alignment(self) -> bool:
+        return True  # fp4_hip_gemv_fused_nf4 has no generic kernel behind it: either epilogue refuses an address off 16 bytes
 
     def _residual_in_kernel(self, rows: int, K: int) -> bool:
         # the one cell in which the fused residual add measured no gain (profiles/nf4_fused_epilogues.json): more than 32 rows against
@@ -417,7 +427,7 @@ class LoRANF4Linear(LoRAAdapterMixin, FusedNF4Linear):
                     and K % 64 == 0)
             if (one or many) and lora_fused_ahead(rows, int(qd.M), K, int(self.lora_A.shape[0])):
                 A, B = self._adapter(x.dtype)
-                x = x.contiguous()
+                x = aligned16(x)  # lora_down and both adapter ops read x in 16-byte pieces
                 try:
                     t = ext.lora_down(x, A, self.lora_scale)
                 except RuntimeError as exc:
@@ -636,7 +646,7 @@ class MultiLoRANF4Linear(FusedNF4Linear):
                     and K % 64 == 0)
             if (one or many) and lora_fused_ahead(rows, int(qd.M), K, self.rank):
                 A, B = self._stacks(x.dtype)
-                x = x.contiguous()
+                x = aligned16(x)  # lora_down_multi and both adapter ops read x in 16-byte pieces
                 try:
                     t = ext.lora_down_multi(x, A, self.lora_scale_stack, ids)
                 except RuntimeError as exc:

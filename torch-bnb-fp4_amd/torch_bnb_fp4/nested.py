@@ -29,6 +29,7 @@ from torch import nn
 from ._ext import ext
 from .dtypes import ScalarType
 from .fused import LoRAAdapterMixin
+from .quant_data import aligned16
 
 NESTED_BLOCKSIZE = 256  # what every bitsandbytes file holds, and what the resident GEMV reads
 
@@ -163,16 +164,16 @@ class NestedNF4Linear(nn.Module):
             return torch.empty(x.shape[:-1] + (M,), dtype=x.dtype, device=x.device)
         bias = self._bias_for(x)
         if x.numel() == K and x.dim() in (2, 3) and x.dtype in (torch.float16, torch.bfloat16, torch.float32):
-            xc = x if x.is_contiguous() else x.contiguous()
-            if xc.data_ptr() % 16 == 0:
-                return ext.gemv_nf4_nested(xc, self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset,
-                                           self.nested_blocksize, self.blocksize, self._shape_list, bias,
-                                           None if residual is None else residual.contiguous(), 0)
+            # the GEMV reads x in 16-byte pieces: an activation off that boundary is copied once (an address belongs to the call)
+            return ext.gemv_nf4_nested(aligned16(x), self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset,
+                                       self.nested_blocksize, self.blocksize, self._shape_list, bias,
+                                       None if residual is None else residual.contiguous(), 0)
         rows = x.numel() // K
         if self._batched_ok and self._batched_routed(rows, K, x.dtype):
             in_kernel = residual is not None and self._residual_in_kernel(rows, K)
             try:
-                y = ext.gemm_nf4_nested(x.contiguous(), self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset,
+                # the call is made coverable, so that a refusal caught below is about the shape, which belongs to the layer
+                y = ext.gemm_nf4_nested(aligned16(x), self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset,
                                         self.nested_blocksize, self.blocksize, self._shape_list, bias,
                                         residual.contiguous() if in_kernel else None, 0)
                 return y if in_kernel or residual is None else y + residual
@@ -260,9 +261,9 @@ class LoRANestedNF4Linear(LoRAAdapterMixin, NestedNF4Linear):
             one = (rows == 1 and x.dim() in (2, 3) and self._gemv_lora_ok
                    and x.dtype in (torch.float16, torch.bfloat16, torch.float32))
             many = self._gemm_lora_ok and self._batched_covers(rows, K, x.dtype)
-            xc = x.contiguous()
-            if (one or many) and xc.data_ptr() % 16 == 0 and lora_fused_ahead(rows, M, K, int(self.lora_A.shape[0])):
+            if (one or many) and lora_fused_ahead(rows, M, K, int(self.lora_A.shape[0])):
                 A, B = self._adapter(x.dtype)
+                xc = aligned16(x)  # lora_down and both adapter ops read x in 16-byte pieces
                 try:
                     t = ext.lora_down(xc, A, self.lora_scale)
                 except RuntimeError as exc:

@@ -41,6 +41,24 @@ from .functional import dequantize_fp4_codebook_invoke_qtype, dequantize_fp4_qty
 from .nn import check_quant_type, expand_quant_state
 
 
+def aligned16(x: torch.Tensor) -> torch.Tensor:
+    """``x`` contiguous with its first element on a 16-byte boundary: ``x`` itself where it is there already (every fresh allocation
+    is), one copy otherwise.  The batched, epilogue and adapter ops load the activation in 16-byte pieces and refuse any other address;
+    an address belongs to the call, not to the layer, so the layers make the call coverable instead of changing route.  Under graph
+    capture the copy is an allocation from the caching allocator and one more captured kernel, like the split-K workspace."""
+    x = x.contiguous()
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
+def small_fp4_covers(rows: int, K: int, blocksize: int, dtype: torch.dtype) -> bool:
+    """The 16-bit cells of ``fp4_hip_gemm_small``: 2..128 rows against a blocksize-64 weight with K % 64 == 0 (the matrix-core and
+    one-pass kernels), and up to 8 rows on the VALU kernel, which takes any power-of-two blocksize from 32 that divides K, K % 32 == 0,
+    K <= 4096.  Any other blocksize (dequant takes every even one) stays on dequant + GEMM."""
+    return (2 <= rows <= 128 and dtype in (torch.float16, torch.bfloat16)
+            and ((blocksize == 64 and K % 64 == 0)
+                 or (rows <= 8 and blocksize >= 32 and blocksize & (blocksize - 1) == 0 and K % blocksize == 0 and K % 32 == 0 and K <= 4096)))
+
+
 class QuantData:
     def __init__(self, A: torch.Tensor, state, shape: Tuple[int, int], original_lin=None,
                  bias: Optional[torch.Tensor] = None, use_codebook_dequant: Optional[bool] = True,
@@ -185,14 +203,15 @@ class QuantData:
         # everything that is not a 2-D / 3-D single token with K % blocksize == 0 (:593-594, :614-617)
         rows = total // K
         if self.small_batch_fused and not self.nf4 and 2 <= rows <= 128 and (
-                (A.dtype in (torch.float16, torch.bfloat16)
-                 and ((self.blocksize == 64 and K % 64 == 0) or (rows <= 8 and K % self.blocksize == 0 and K % 32 == 0 and K <= 4096)))
+                small_fp4_covers(rows, K, self.blocksize, A.dtype)
                 or (A.dtype == torch.float32 and rows <= 8 and K % self.blocksize == 0)):  # f32: one f32 GEMV per row, up to 8 rows
-            return ext.gemm_small_fp4(A.contiguous(), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
+            # (the f32 GEMV takes any address itself; the 16-bit kernels take the aligned copy)
+            return ext.gemm_small_fp4(A.contiguous() if A.dtype == torch.float32 else aligned16(A), self.A.t(), self.absmax, self.blocksize,
+                                      self._shape_list, self.bias)
         if self.small_batch_fused_nf4 and self.nf4 and 2 <= rows <= 16 and self.blocksize == 64 and K % 512 == 0 and (
                 A.dtype in (torch.float16, torch.bfloat16)):
-            return ext.gemm_small_nf4(A.contiguous(), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
+            return ext.gemm_small_nf4(aligned16(A), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
         if self.wide_batch_fused_nf4 and self.nf4 and self.blocksize == 64 and K % 64 == 0 and (
                 17 <= rows <= 64 or (2 <= rows <= 16 and K % 512 != 0)) and A.dtype in (torch.float16, torch.bfloat16):
-            return ext.gemm_wide_nf4(A.contiguous(), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
+            return ext.gemm_wide_nf4(aligned16(A), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
         return self.qlinear(A)
