@@ -399,3 +399,45 @@ def test_hypothesis_draws(B, M, u, dtype, with_bias, shift):
         exact_d = exact_d + bias.double()
     y = gemm(x, packed, absmax, M, K, bias=bias)
     check_bar(y, exact_d.reshape(-1), scale_d.reshape(-1), dtype, (B, M, K, with_bias))
+
+
+# ---- 9. the single-round rule of the x image -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("extra", [0, 16], ids=["16cus", "16cus+16"])
+def test_the_8_row_x_image_switches_off_past_one_round_of_workgroups(extra):
+    """dispatch_nf4_mfma_shape stages x for 5..8 rows only while the grid is a single round (B <= 8 && blocks <= cus): M = 16 cus is
+    the last shape with the image, 16 cus + 16 the first without, and no other small-batch shape here is taller than 4096.  5 and 8
+    rows, both dtypes, through fp4_hip_gemm_small_nf4 and through fp4_hip_gemm_fused_nf4: the plain result at this file's bar against
+    the restatement (and the same bits from both entry points); the gate|up epilogue within 1 ulp of torch's silu(g) * u on that
+    result, >= 99.8 % identical (the batched rule of tests/test_gpu_nf4_fused.py)."""
+    l = _lib()
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    l.fp4_hip_gemm_fused_nf4.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp]
+    l.fp4_hip_gemm_fused_nf4.restype = i32
+    M, K = 16 * torch.cuda.get_device_properties(dev()).multi_processor_count + extra, 2048
+    packed_d, absmax_d = _random_nf4(M * K, 31 * M + K)
+    g = torch.Generator().manual_seed(K + M)
+    x32 = torch.randn(8, K, generator=g)
+    b32 = torch.randn(M, generator=g) * 0.1
+    for dtype in DTYPES:
+        x, bias = x32.to(dtype).to(dev()), b32.to(dtype).to(dev())
+        exact_d, scale_d = device_products(packed_d, absmax_d, M, K, BS, list(x))
+        tie_to_restatement(packed_d, absmax_d, M, K, BS, [x[0], x[7]], exact_d[[0, 7]], np.random.default_rng(M), n_rows=14)
+        with_bias = exact_d + bias.double()
+        for B in (5, 8):
+            xb = x[:B].contiguous()
+            y = gemm(xb, packed_d, absmax_d, M, K)
+            check_bar(y, exact_d[:B].reshape(-1), scale_d[:B].reshape(-1), dtype, (M, K, B, "plain"))
+            yb = gemm(xb, packed_d, absmax_d, M, K, bias=bias)
+            check_bar(yb, with_bias[:B].reshape(-1), scale_d[:B].reshape(-1), dtype, (M, K, B, "bias"))
+            outs = {}
+            for epi in (hipabi.EPILOGUE_NONE, hipabi.EPILOGUE_SILU_MUL_PAIRS):
+                out = torch.empty(B, M // 2 if epi else M, dtype=dtype, device=dev())
+                rc = l.fp4_hip_gemm_fused_nf4(hipabi._ptr(xb), hipabi._ptr(packed_d), hipabi._ptr(absmax_d), hipabi._ptr(bias), None,
+                                              hipabi._ptr(out), B, M, K, BS, hipabi.DT[dtype], epi, hipabi._stream())
+                assert rc == hipabi.OK, (rc, hipabi.last_error())
+                outs[epi] = out
+            assert torch.equal(bits_t(outs[hipabi.EPILOGUE_NONE]), bits_t(yb))
+            ref = torch.nn.functional.silu(yb[:, 0::2]) * yb[:, 1::2]
+            line = lambda t: torch.where((bits_t(t).int() & 0xFFFF) >= 0x8000, 0x8000 - (bits_t(t).int() & 0xFFFF), bits_t(t).int() & 0xFFFF)
+            d = (line(outs[hipabi.EPILOGUE_SILU_MUL_PAIRS]) - line(ref)).abs()
+            assert int(d.max()) <= 1 and float((d == 0).float().mean()) >= 0.998, (M, B, dtype, int(d.max()))
