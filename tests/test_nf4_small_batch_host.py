@@ -217,12 +217,19 @@ def test_the_new_source_is_built_and_its_kernels_are_tied_to_it():
     files = source_digest.sources_of("gemm_nf4_mfma_kernel<2, 4, 4>")
     assert files and any(f.endswith("gemm_small_nf4.hip") for f in files)
     assert not any(f.endswith("gemm_small_fp4.hip") for f in files)
-    assert any(f.endswith("gemm_small_fp4.hip") for f in source_digest.sources_of("gemm16_mfma_kernel<2, 4, 1, true, 4>"))
+    assert any(f.endswith("gemm_small_fp4.hip") for f in source_digest.sources_of("gemm16_mfma_kernel<2, 4, 1, 4>"))
     # the shared headers: rebuilt on an edit, and among the sources of the matrix-core kernels that include them - and of no other
     assert {"mfma_common.h", "nf4_mfma.h", "launchers.h"} <= set(build.HIP_HEADERS)
     names = lambda kernel: {os.path.basename(f) for f in source_digest.sources_of(kernel)}
     assert {"mfma_common.h", "nf4_mfma.h"} <= names("gemm_nf4_mfma_kernel<2, 4, 4>")
-    for fp4_kernel in ("gemm16_mfma_kernel<2, 4, 1, true, 4>", "gemm16_small_kernel<2, 4>"):
+    for fp4_kernel in ("gemm16_mfma_kernel<2, 4, 1, 4>", "gemm16_small_kernel<2, 4>"):
         assert "mfma_common.h" in names(fp4_kernel) and "nf4_mfma.h" not in names(fp4_kernel)
     for other in ("gemv16_regx_kernel<2, 4>", "gemv_nf4_kernel<2, 4>", "dequant_tiles_kernel<2>", "quantize_nf4_kernel<2>", "lora_down_kernel<2>"):
         assert not {"mfma_common.h", "nf4_mfma.h"} & names(other), other
+    # the wave-private LDS images: the header of the three translation units that stage through them, and of no other
+    assert "wave_image.h" in build.HIP_HEADERS
+    for image_kernel in ("gemm_nf4_mfma_kernel<2, 4, 4>", "gemm_wide_nf4_kernel<2, 4, 1, 4>", "gemm16_mfma_kernel<2, 4, 1, 4>"):
+        assert "wave_image.h" in names(image_kernel), image_kernel
+    for other in ("gemv16_regx_kernel<2, 4>", "gemv_nf4_kernel<2, 4>", "dequant_tiles_kernel<2>", "quantize_nf4_kernel<2>", "lora_down_kernel<2>",
+                  "gemm16_wide_ring_kernel<2, 4>"):
+        assert "wave_image.h" not in names(other), other

@@ -1,6 +1,6 @@
 """Are two `hipcc --cuda-device-only -S` outputs of one source the same kernels, whatever ORDER they were emitted in?
 
-    python tools/asm_same_kernels.py PARENT.s TREE.s        exit status 0: yes
+    python tools/asm_same_kernels.py PARENT.s TREE.s [--rename REGEX REPLACEMENT]        exit status 0: yes
 
 A host-side edit that changes the order in which kernel templates are first referenced changes the order in which the compiler
 emits them, and with it the ordinal inside every local label (.LBB<n>_<m>, .Lfunc_end<n>): a plain diff then shows most of the
@@ -8,13 +8,22 @@ file although no instruction moved.  This splits both files at the kernels' `.se
 in local labels (and in the comments that quote them), squeezes the blanks that pad those comments, and compares the kernels by
 symbol; the metadata entries (one per kernel) are compared as a set, and everything outside kernels line by line, where only the
 compilation-unit id (__hip_cuid_) may differ.  Printed: the kernel counts, how many kernels differ in text, how many positions
-hold another kernel than in the first file, and the differing lines outside kernels."""
+hold another kernel than in the first file, and the differing lines outside kernels.
+
+--rename REGEX REPLACEMENT (re.sub, so \\1 names a group) is applied to the whole text of the FIRST file before it is parsed: an edit that
+drops or adds a template parameter changes the mangled names and nothing else, and the parent's symbols - in labels, directives,
+comments and metadata alike - are rewritten to the tree's mangling so that the kernels pair up.  The dropped `bool STAGE` of
+gemm16_mfma_kernel:   --rename '(gemm16_mfma_kernelILi[0-9]*ELi[0-9]*ELi[0-9]*E)Lb1E' '\\1'"""
+import argparse
 import re
 import sys
 
 
-def parse(path):
-    lines = open(path).read().split("\n")
+def parse(path, rename=None):
+    text = open(path).read()
+    if rename:
+        text = re.sub(rename[0], rename[1], text)
+    lines = text.split("\n")
     meta_a, meta_b = lines.index("\t.amdgpu_metadata"), lines.index("\t.end_amdgpu_metadata")
     body, meta = lines[:meta_a], lines[meta_a:meta_b + 1]
     begins = [i for i, l in enumerate(body) if "; -- Begin function" in l]
@@ -42,8 +51,8 @@ def parse(path):
     return kernels, order, sorted("\n".join(e) for e in entries), outside
 
 
-def main(a_path, b_path):
-    (ka, oa, ma, xa), (kb, ob, mb, xb) = parse(a_path), parse(b_path)
+def main(a_path, b_path, rename=None):
+    (ka, oa, ma, xa), (kb, ob, mb, xb) = parse(a_path, rename), parse(b_path)
     differing = sorted(k for k in ka if k in kb and ka[k] != kb[k])
     moved = sum(1 for x, y in zip(oa, ob) if x != y)
     outside = [(x, y) for x, y in zip(xa, xb) if x != y and "__hip_cuid_" not in x] + [None] * abs(len(xa) - len(xb))
@@ -57,4 +66,9 @@ def main(a_path, b_path):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("first")
+    ap.add_argument("second")
+    ap.add_argument("--rename", nargs=2, metavar=("REGEX", "REPLACEMENT"), help="re.sub applied to the whole text of the first file")
+    args = ap.parse_args()
+    sys.exit(main(args.first, args.second, args.rename))

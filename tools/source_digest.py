@@ -15,9 +15,10 @@ LORA = os.path.join(CSRC, "lora_nf4.h")  # the adapter term of the NF4 decode ke
 MFMA = os.path.join(CSRC, "mfma_common.h")  # the matrix-core kernels' shared device helpers
 FP4_CALL = os.path.join(CSRC, "fp4_call.h")  # the call descriptor and the launch functions of the decode entry points (host side)
 NF4_MFMA = os.path.join(CSRC, "nf4_mfma.h")  # the NF4 hi / lo decode of the two NF4 matrix-core kernels
+IMAGE = os.path.join(CSRC, "wave_image.h")  # the wave-private LDS weight and x images of the 16-row-tile matrix-core kernels
 KERNEL_SOURCES = {
-    "gemm_wide_nf4": [os.path.join(CSRC, "gemm_wide_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, NF4_MFMA, LORA, FP4_CALL] + COMMON,
-    "gemm_nf4": [os.path.join(CSRC, "gemm_small_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, NF4_MFMA, LORA, FP4_CALL] + COMMON,
+    "gemm_wide_nf4": [os.path.join(CSRC, "gemm_wide_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, IMAGE, NF4_MFMA, LORA, FP4_CALL] + COMMON,
+    "gemm_nf4": [os.path.join(CSRC, "gemm_small_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, IMAGE, NF4_MFMA, LORA, FP4_CALL] + COMMON,
     "gemv_nf4": [os.path.join(CSRC, "gemv_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA, FP4_CALL] + COMMON,
     "lora_down": [os.path.join(CSRC, "lora_nf4.hip"), os.path.join(CSRC, "gemv_common.h"), LORA] + COMMON,
     "quantize_nf4": [os.path.join(CSRC, "quantize_nf4.hip")] + COMMON,
@@ -28,7 +29,7 @@ KERNEL_SOURCES = {
     "gemm16_wide": [os.path.join(CSRC, "gemm_wide_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, FP4_CALL] + COMMON,
     "gemm16_xstat": [os.path.join(CSRC, "gemm_splitk_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, FP4_CALL] + COMMON,
     "splitk_reduce": [os.path.join(CSRC, "gemm_splitk_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, FP4_CALL] + COMMON,
-    "gemm16_": [os.path.join(CSRC, "gemm_small_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, FP4_CALL] + COMMON,
+    "gemm16_": [os.path.join(CSRC, "gemm_small_fp4.hip"), os.path.join(CSRC, "gemv_common.h"), MFMA, IMAGE, FP4_CALL] + COMMON,
 }
 
 

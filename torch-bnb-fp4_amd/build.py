@@ -27,7 +27,7 @@ OBJ_DIR = os.path.join(REPO, "build_tmp", "obj")
 
 HIP_SOURCES = ["capi.hip", "dequant_fp4.hip", "gemv_fp4.hip", "gemm_small_fp4.hip", "gemm_wide_fp4.hip", "gemm_splitk_fp4.hip", "quantize_fp4.hip", "allreduce_oneshot.hip",
                "gemv_nf4.hip", "quantize_nf4.hip", "gemm_small_nf4.hip", "gemm_wide_nf4.hip", "lora_nf4.hip", "nested_absmax.hip"]
-HIP_HEADERS = ["fp4_common.h", "gemv_common.h", "mfma_common.h", "nf4_mfma.h", "nf4_call.h", "fp4_call.h", "launchers.h", "lora_nf4.h", "nested_absmax.h",
+HIP_HEADERS = ["fp4_common.h", "gemv_common.h", "mfma_common.h", "wave_image.h", "nf4_mfma.h", "nf4_call.h", "fp4_call.h", "launchers.h", "lora_nf4.h", "nested_absmax.h",
                os.path.join(INCLUDE, "torch_bnb_fp4_hip.h")]
 ARCH = "gfx950"
 # Kernel arguments are preloaded into SGPRs at wave launch instead of being fetched with s_load at the top of the

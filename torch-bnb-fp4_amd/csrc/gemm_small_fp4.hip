@@ -10,6 +10,7 @@
 #include "fp4_call.h"
 #include "launchers.h"
 #include "mfma_common.h"
+#include "wave_image.h"
 
 namespace fp4 {
 
@@ -177,34 +178,20 @@ __device__ __forceinline__ u32x4 pair_up8(u32x4 w) {
     return o;
 }
 
-template <int DT, int NBW, int ROWT, bool STAGE, int XS = 0>
+template <int DT, int NBW, int ROWT, int XS = 0>
 __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__restrict__ x, const uint8_t *__restrict__ W,
                                                           const float *__restrict__ absmax,
                                                           const uint16_t *__restrict__ bias, const uint16_t *residual, uint16_t *out,
                                                           int B, int M, int K, int mode) {
     // ROWT 16-row tiles per workgroup share one B fragment (x slice): x is re-read by every workgroup, so taller
     // workgroups cut that L2 traffic (B*K*2 bytes each) at the price of fewer workgroups
-    // (STAGE = false - direct 8-byte fragment loads - lost every sweep and is no longer instantiated since round 3; the branch stays as
-    //  the record of the alternative.)
-    // STAGE: the A-fragment layout wants 8 bytes per lane from 16 different rows (32-byte segments per row per
-    // instruction); instead each wave pulls its 16 x (32*NBW)-byte region with row-contiguous 16-byte loads and
-    // re-reads it from a wave-private LDS image (no workgroup barrier).  Each image row is followed by that row's NBW
-    // block scales: the accumulator layout needs the scales of 4 rows x NBW blocks per lane, the same values in 16 lanes,
-    // so they are fetched once per wave (one 4- or 8-byte load per lane) and re-read from LDS as broadcasts instead of
-    // 8 x 16-byte global loads per lane and tile.  Row stride 32*NBW + 32 bytes: the 8-byte fragment reads of 16 rows
-    // x 4 k-groups fall on distinct banks per half-wave.
-    // XS > 0 (batch <= XS, XS in {4, 8}): the B fragment wants 32 bytes per lane from 16 activation rows, of which only
-    // `batch` are real - loaded straight from global every 16-row workgroup would pull 16 / batch times its share of x
-    // through the texture path (4x the weight stream at batch 4).  Instead the wave copies the XS x (64*NBW) activations of
-    // its K slice into a wave-private LDS image with row-contiguous 16-byte loads and reads the fragments from there
-    // (lanes of the unused columns read a real row: broadcast, results never stored).
-    constexpr int kStageStride = 32 * NBW + 32;
-    constexpr int kXStride = 128 * NBW + 16;
-    constexpr int kWImageBytes = STAGE ? 8 * ROWT * 16 * kStageStride : 0;
-    constexpr int kXImageBytes = 8 * XS * kXStride;
-    constexpr int kImageBytes = kWImageBytes + kXImageBytes;
+    // Weights and scales go through a wave-private LDS image, one per row tile; for batch <= XS (XS in {4, 8}) so does the wave's
+    // slice of x: both layouts, and why, in wave_image.h.
+    using WImg = WeightImage<NBW>;
+    using XImg = XImage<NBW, XS>;
+    constexpr int kWImageBytes = 8 * ROWT * WImg::kBytes;
+    constexpr int kImageBytes = kWImageBytes + 8 * XImg::kBytes;
     constexpr int kPartBytes = 8 * ROWT * 256 * 4;
-    static_assert(XS == 0 || (STAGE && (XS * NBW) % 8 == 0 && (XS & (XS - 1)) == 0), "x staging: whole 16-byte units per lane");
     // the cross-wave partial sums reuse the images' storage after the K loop (one barrier in between): LDS per workgroup
     // decides how many of these 8-wave workgroups a CU holds
     __shared__ __attribute__((aligned(16))) uint8_t s_raw[kImageBytes > kPartBytes ? kImageBytes : kPartBytes];
@@ -219,15 +206,7 @@ __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__rest
     const int nblk = K >> 6;
     const int passes = nblk / (8 * NBW);
     const int64_t n_b = r < B ? r : B - 1;  // clamped rows / batch entries are computed, never stored
-    int64_t row_a[ROWT], row_d[ROWT][4];
-#pragma unroll
-    for (int rt = 0; rt < ROWT; ++rt) {
-        row_a[rt] = row0 + 16 * rt + r < M ? row0 + 16 * rt + r : M - 1;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) row_d[rt][g] = row0 + 16 * rt + kb * 4 + g < M ? row0 + 16 * rt + kb * 4 + g : M - 1;
-    }
     const u32x4 *x4 = reinterpret_cast<const u32x4 *>(x);
-    const u32x2 *W2 = reinterpret_cast<const u32x2 *>(W);
 
     f32x4 acc[ROWT];
 #pragma unroll
@@ -236,22 +215,20 @@ __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__rest
     // scales, for XS > 0 the x slice - are loaded one pass AHEAD: the registers of pass p + 1 are requested as soon as pass p's
     // have been written to the LDS images and fly while pass p is decoded and multiplied.  With 8 blocks per pass the extra live
     // registers would cost the second workgroup per CU (128 -> 140..164 VGPRs), so there each pass loads its own.
-    constexpr bool kPassAhead = STAGE && NBW <= 4;
-    constexpr int kXUnits = XS ? XS * NBW / 8 : 1;  // 16-byte units of the x image per lane
-    constexpr int kLanesPerRow = 2 * NBW, kRowsPerInstr = 64 / kLanesPerRow, kInstr = (16 + kRowsPerInstr - 1) / kRowsPerInstr;
+    constexpr bool kPassAhead = NBW <= 4;
     // 16 rows x NBW scales over 64 lanes (with NBW < 4 the upper lanes repeat rows: same address, same value)
     constexpr int kScalesPerLane = NBW > 4 ? NBW / 4 : 1;
     constexpr int kLanesPerScaleRow = NBW / kScalesPerLane;
     const int srow = (lane / kLanesPerScaleRow) & 15, sj0 = (lane % kLanesPerScaleRow) * kScalesPerLane;
-    u32x4 xstage[kXUnits];
-    u32x4 wstage[ROWT][kInstr];
+    u32x4 xstage[XImg::kUnits];
+    u32x4 wstage[ROWT][WImg::kInstr];
     float amstage[ROWT][kScalesPerLane];
     auto issue_staged = [&](int pass) {  // x first (L2), then the weight stream (HBM), then the scales; all branch-free
         const int b0 = (pass * 8 + wave) * NBW;
         if constexpr (XS > 0) {
 #pragma unroll
-            for (int i = 0; i < kXUnits; ++i) {
-                const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
+            for (int i = 0; i < XImg::kUnits; ++i) {
+                const int n = XImg::unit_row(i, lane), c16 = XImg::unit_col(i, lane);
                 const int64_t nn = n < B ? n : B - 1;
                 xstage[i] = x4[((nn * K + 64 * b0) >> 3) + c16];
             }
@@ -259,12 +236,7 @@ __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__rest
 #pragma unroll
         for (int rt = 0; rt < ROWT; ++rt)
 #pragma unroll
-            for (int i = 0; i < kInstr; ++i) {
-                const int rr = i * kRowsPerInstr + lane / kLanesPerRow;  // row of the tile this lane fetches
-                const int64_t row = row0 + 16 * rt + (rr & 15) < M ? row0 + 16 * rt + (rr & 15) : M - 1;
-                wstage[rt][i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(W) + ((row * K) >> 5) + 2 * b0 +
-                                                           (lane % kLanesPerRow));
-            }
+            for (int i = 0; i < WImg::kInstr; ++i) wstage[rt][i] = __builtin_nontemporal_load(WImg::fetch_unit(W, i, lane, row0 + 16 * rt, M, K, b0));
 #pragma unroll
         for (int rt = 0; rt < ROWT; ++rt) {
             const int64_t row = row0 + 16 * rt + srow < M ? row0 + 16 * rt + srow : M - 1;
@@ -276,7 +248,7 @@ __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__rest
     if constexpr (kPassAhead) issue_staged(0);
     for (int p = 0; p < passes; ++p) {
         const int b0 = (p * 8 + wave) * NBW;
-        if constexpr (STAGE && !kPassAhead) issue_staged(p);
+        if constexpr (!kPassAhead) issue_staged(p);
         u32x4 xr[XS ? 1 : NBW][2];
         if constexpr (XS == 0) {
 #pragma unroll
@@ -288,75 +260,46 @@ __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__rest
         }
         u32x2 wq[ROWT][NBW];
         float am[ROWT][4][NBW];
-        if constexpr (!STAGE) {
+        if (p > 0) __builtin_amdgcn_wave_barrier();  // the previous pass's reads are done before the image is rewritten
 #pragma unroll
-            for (int rt = 0; rt < ROWT; ++rt)
+        for (int rt = 0; rt < ROWT; ++rt) {
+            uint8_t *img = WImg::template at<ROWT>(s_w, wave, rt);
 #pragma unroll
-                for (int j = 0; j < NBW; ++j)
-                    wq[rt][j] = __builtin_nontemporal_load(W2 + ((row_a[rt] * K) >> 4) + 4 * (b0 + j) + kb);
-#pragma unroll
-            for (int rt = 0; rt < ROWT; ++rt) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float *src = absmax + row_d[rt][g] * nblk + b0;
-                    if constexpr (NBW % 4 == 0) {
-#pragma unroll
-                        for (int j = 0; j < NBW; j += 4) {
-                            const f32x4 v = *reinterpret_cast<const f32x4 *>(src + j);
-                            am[rt][g][j] = v.x, am[rt][g][j + 1] = v.y, am[rt][g][j + 2] = v.z, am[rt][g][j + 3] = v.w;
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < NBW; ++j) am[rt][g][j] = src[j];
-                    }
-                }
+            for (int i = 0; i < WImg::kInstr; ++i) {
+                const int rr = WImg::fetch_row(i, lane);
+                if (WImg::inside(rr)) *WImg::unit(img, rr, lane) = wstage[rt][i];
             }
+            float *tail = WImg::scales(img, srow) + sj0;
+#pragma unroll
+            for (int i = 0; i < kScalesPerLane; ++i) tail[i] = amstage[rt][i];
         }
-        if constexpr (STAGE) {
-            if (p > 0) __builtin_amdgcn_wave_barrier();  // the previous pass's reads are done before the image is rewritten
+        if constexpr (XS > 0) {
+            uint8_t *ximg = XImg::at(s_x, wave);
 #pragma unroll
-            for (int rt = 0; rt < ROWT; ++rt) {
-                uint8_t *img = s_w + (wave * ROWT + rt) * 16 * kStageStride;
+            for (int i = 0; i < XImg::kUnits; ++i)
+                *XImg::unit(ximg, XImg::unit_row(i, lane), XImg::unit_col(i, lane)) = pair_up8(xstage[i]);  // once, not per tile
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if constexpr (kPassAhead)
+            if (p + 1 < passes) issue_staged(p + 1);  // uniform
 #pragma unroll
-                for (int i = 0; i < kInstr; ++i) {
-                    const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
-                    if (rr < 16) *reinterpret_cast<u32x4 *>(img + rr * kStageStride + 16 * (lane % kLanesPerRow)) = wstage[rt][i];
-                }
-                float *tail = reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW) + sj0;
+        for (int rt = 0; rt < ROWT; ++rt) {
+            uint8_t *img = WImg::template at<ROWT>(s_w, wave, rt);
+            WImg::read_frags(img, r, kb, wq[rt]);
 #pragma unroll
-                for (int i = 0; i < kScalesPerLane; ++i) tail[i] = amstage[rt][i];
-            }
-            if constexpr (XS > 0) {
-                uint8_t *ximg = s_x + wave * XS * kXStride;
+            for (int g = 0; g < 4; ++g) {
+                const float *src = WImg::scales(img, kb * 4 + g);
+                if constexpr (NBW % 4 == 0) {
 #pragma unroll
-                for (int i = 0; i < kXUnits; ++i) {
-                    const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
-                    *reinterpret_cast<u32x4 *>(ximg + n * kXStride + 16 * c16) = pair_up8(xstage[i]);  // once, not per tile
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if constexpr (kPassAhead)
-                if (p + 1 < passes) issue_staged(p + 1);  // uniform
-#pragma unroll
-            for (int rt = 0; rt < ROWT; ++rt) {
-                const uint8_t *img = s_w + (wave * ROWT + rt) * 16 * kStageStride;
-#pragma unroll
-                for (int j = 0; j < NBW; ++j) wq[rt][j] = *reinterpret_cast<const u32x2 *>(img + r * kStageStride + 32 * j + 8 * kb);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const uint8_t *src = img + (kb * 4 + g) * kStageStride + 32 * NBW;
-                    if constexpr (NBW % 4 == 0) {
-#pragma unroll
-                        for (int j = 0; j < NBW; j += 4) {
-                            const f32x4 v = reinterpret_cast<const f32x4 *>(src)[j >> 2];
-                            am[rt][g][j] = v.x, am[rt][g][j + 1] = v.y, am[rt][g][j + 2] = v.z, am[rt][g][j + 3] = v.w;
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < NBW; ++j) am[rt][g][j] = reinterpret_cast<const float *>(src)[j];
+                    for (int j = 0; j < NBW; j += 4) {
+                        const f32x4 v = reinterpret_cast<const f32x4 *>(src)[j >> 2];
+                        am[rt][g][j] = v.x, am[rt][g][j + 1] = v.y, am[rt][g][j + 2] = v.z, am[rt][g][j + 3] = v.w;
                     }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < NBW; ++j) am[rt][g][j] = src[j];
                 }
             }
         }
@@ -366,7 +309,7 @@ __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__rest
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 if constexpr (XS > 0)
-                    bfrag[t] = *reinterpret_cast<const u32x4 *>(s_x + wave * XS * kXStride + (r & (XS - 1)) * kXStride + 128 * j + 32 * kb + 16 * t);
+                    bfrag[t] = *XImg::frag(XImg::at(s_x, wave), r, j, kb, t);
                 else
                     bfrag[t] = pair_up8(xr[j][t]);
             }
@@ -387,7 +330,7 @@ __global__ __launch_bounds__(512) void gemm16_mfma_kernel(const uint16_t *__rest
             }
         }
     }
-    if constexpr (STAGE) __syncthreads();  // every wave is done with its image before the partials overwrite the storage
+    __syncthreads();  // every wave is done with its image before the partials overwrite the storage
 #pragma unroll
     for (int rt = 0; rt < ROWT; ++rt) *reinterpret_cast<f32x4 *>(&s_part[wave][rt][lane * 4]) = acc[rt];
     __syncthreads();
@@ -424,10 +367,10 @@ __global__ __launch_bounds__(512) void gemm16_mfma_persist_kernel(const uint16_t
                                                                   const uint16_t *__restrict__ bias, const uint16_t *residual,
                                                                   uint16_t *out, int B, int M, int K, int ntiles, int mode) {
     constexpr int NBW = 8;
-    constexpr int kStageStride = 32 * NBW + 32, kXStride = 128 * NBW + 16;
-    constexpr int kXUnits = XS ? XS * NBW / 8 : 1;
-    __shared__ __attribute__((aligned(16))) uint8_t s_w[8 * 16 * kStageStride];
-    __shared__ __attribute__((aligned(16))) uint8_t s_x[XS ? 8 * XS * kXStride : 16];
+    using WImg = WeightImage<NBW>;  // both images: wave_image.h
+    using XImg = XImage<NBW, XS>;
+    __shared__ __attribute__((aligned(16))) uint8_t s_w[8 * WImg::kBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t s_x[XS ? 8 * XImg::kBytes : 16];
     // Above 4 rows one workgroup owns the CU anyway (LDS), so the cross-wave partials are double-buffered there: tile t writes buffer
     // t & 1, its reducers read it behind the tile's one barrier, tile t + 2 overwrites it only behind tile t + 1's barrier - one
     // workgroup barrier per tile instead of two.  Up to 4 rows a second buffer would cost the second workgroup per CU.
@@ -439,8 +382,8 @@ __global__ __launch_bounds__(512) void gemm16_mfma_persist_kernel(const uint16_t
     const int b0 = wave * NBW;
     int par = 0;
     const u32x4 *x4 = reinterpret_cast<const u32x4 *>(x);
-    uint8_t *img = s_w + wave * 16 * kStageStride;
-    uint8_t *ximg = s_x + wave * XS * kXStride;
+    uint8_t *img = WImg::at(s_w, wave);
+    uint8_t *ximg = XImg::at(s_x, wave);
 
     // x slice of this wave, once: up to 8 rows as a paired-up LDS image; above that (XS == 0) the 16 B fragments of the slice
     // stay in registers for every tile (64 VGPRs: one workgroup per CU, but no x traffic at all after the first tile)
@@ -454,33 +397,26 @@ __global__ __launch_bounds__(512) void gemm16_mfma_persist_kernel(const uint16_t
             bregs[j][1] = pair_up8(x4[(e >> 3) + 1]);
         }
     } else {
-        u32x4 xstage[kXUnits];
+        u32x4 xstage[XImg::kUnits];
 #pragma unroll
-        for (int i = 0; i < kXUnits; ++i) {
-            const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
+        for (int i = 0; i < XImg::kUnits; ++i) {
+            const int n = XImg::unit_row(i, lane), c16 = XImg::unit_col(i, lane);
             const int64_t nn = n < B ? n : B - 1;
             xstage[i] = x4[((nn * K + 64 * b0) >> 3) + c16];
         }
 #pragma unroll
-        for (int i = 0; i < kXUnits; ++i) {
-            const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
-            *reinterpret_cast<u32x4 *>(ximg + n * kXStride + 16 * c16) = pair_up8(xstage[i]);
-        }
+        for (int i = 0; i < XImg::kUnits; ++i)
+            *XImg::unit(ximg, XImg::unit_row(i, lane), XImg::unit_col(i, lane)) = pair_up8(xstage[i]);
     }
 
-    constexpr int kLanesPerRow = 2 * NBW, kRowsPerInstr = 64 / kLanesPerRow, kInstr = 16 / kRowsPerInstr;  // 16, 4, 4
     constexpr int kScalesPerLane = NBW / 4;
     const int srow = lane >> 2, sj0 = (lane & 3) * kScalesPerLane;
-    u32x4 wstage[kInstr];
+    u32x4 wstage[WImg::kInstr];  // 4: 16 lanes per row, 4 rows per instruction
     float amstage[kScalesPerLane];
     auto issue = [&](int tile) {  // branch-free: rows past M are clamped (computed, never stored)
         const int row0 = tile * 16;
 #pragma unroll
-        for (int i = 0; i < kInstr; ++i) {
-            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
-            const int64_t row = row0 + rr < M ? row0 + rr : M - 1;
-            wstage[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(W) + ((row * K) >> 5) + 2 * b0 + (lane % kLanesPerRow));
-        }
+        for (int i = 0; i < WImg::kInstr; ++i) wstage[i] = __builtin_nontemporal_load(WImg::fetch_unit(W, i, lane, row0, M, K, b0));
         const int64_t row = row0 + srow < M ? row0 + srow : M - 1;
         const float *src = absmax + row * nblk + b0 + sj0;
 #pragma unroll
@@ -492,15 +428,10 @@ __global__ __launch_bounds__(512) void gemm16_mfma_persist_kernel(const uint16_t
     while (true) {
         __builtin_amdgcn_wave_barrier();  // this wave's reads of the previous tile's image are done
 #pragma unroll
-        for (int i = 0; i < kInstr; ++i) {
-            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
-            *reinterpret_cast<u32x4 *>(img + rr * kStageStride + 16 * (lane % kLanesPerRow)) = wstage[i];
-        }
-        {
-            float *tail = reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW) + sj0;
+        for (int i = 0; i < WImg::kInstr; ++i) *WImg::unit(img, WImg::fetch_row(i, lane), lane) = wstage[i];
+        float *tail = WImg::scales(img, srow) + sj0;
 #pragma unroll
-            for (int i = 0; i < kScalesPerLane; ++i) tail[i] = amstage[i];
-        }
+        for (int i = 0; i < kScalesPerLane; ++i) tail[i] = amstage[i];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -511,11 +442,10 @@ __global__ __launch_bounds__(512) void gemm16_mfma_persist_kernel(const uint16_t
 
         u32x2 wq[NBW];
         float am[4][NBW];
-#pragma unroll
-        for (int j = 0; j < NBW; ++j) wq[j] = *reinterpret_cast<const u32x2 *>(img + r * kStageStride + 32 * j + 8 * kb);
+        WImg::read_frags(img, r, kb, wq);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const f32x4 *src = reinterpret_cast<const f32x4 *>(img + (kb * 4 + g) * kStageStride + 32 * NBW);
+            const f32x4 *src = reinterpret_cast<const f32x4 *>(WImg::scales(img, kb * 4 + g));
 #pragma unroll
             for (int j = 0; j < NBW; j += 4) {
                 const f32x4 v = src[j >> 2];
@@ -532,7 +462,7 @@ __global__ __launch_bounds__(512) void gemm16_mfma_persist_kernel(const uint16_t
                 if constexpr (XS == 0)
                     bfrag = bregs[j][t];
                 else
-                    bfrag = *reinterpret_cast<const u32x4 *>(ximg + (r & (XS - 1)) * kXStride + 128 * j + 32 * kb + 16 * t);
+                    bfrag = *XImg::frag(ximg, r, j, kb, t);
                 uint32_t P[4];
                 decode8<DT>(t == 0 ? wq[j].x : wq[j].y, P);
                 const u32x4 afrag = {P[0], P[1], P[2], P[3]};
@@ -580,14 +510,14 @@ std::atomic<int> g_mfma_persist{-1};  // 0 = never the persistent kernel, 1 = wh
 
 // the one-shot kernel for NBW blocks per wave and pass and RT row tiles: with the <= 4-row or <= 8-row x image where it is built
 template <int DT, int NBW, int RT>
-auto mfma_kernel(bool xs4, bool xs8) -> decltype(&gemm16_mfma_kernel<DT, NBW, RT, true>) {
+auto mfma_kernel(bool xs4, bool xs8) -> decltype(&gemm16_mfma_kernel<DT, NBW, RT>) {
     if constexpr (NBW >= 4) {
         if constexpr (RT == 1) {
-            if (xs4) return gemm16_mfma_kernel<DT, NBW, RT, true, 4>;
+            if (xs4) return gemm16_mfma_kernel<DT, NBW, RT, 4>;
         }
-        if (xs8) return gemm16_mfma_kernel<DT, NBW, RT, true, 8>;
+        if (xs8) return gemm16_mfma_kernel<DT, NBW, RT, 8>;
     }
-    return gemm16_mfma_kernel<DT, NBW, RT, true>;
+    return gemm16_mfma_kernel<DT, NBW, RT>;
 }
 
 template <int DT>

@@ -1,9 +1,9 @@
 // Small-batch NF4 product for gfx950 (MI355X): 1..16 activation rows against one NF4 weight on the matrix cores,
 //     out[b][r] = T( sum_k x[b][k] * code[nib(r,k)] * absmax[(r*K+k)/64] + bias[r] )
-// The tile scheme is gemm16_mfma_kernel's (gemm_small_fp4.hip; the staging is written out in both kernels - sharing it between the
-// FP4 and the NF4 kernel is a change of its own, not made here): 8-wave workgroup per 16-row tile of W, the waves split K,
-// row-contiguous 16-byte weight loads staged through a wave-private LDS image, scales re-read from it as broadcasts, loads one pass
-// ahead, v_mfma_f32_16x16x32_{bf16,f16} with one instruction never straddling two scales, partial tiles meeting in LDS.
+// The tile scheme is gemm16_mfma_kernel's (gemm_small_fp4.hip): 8-wave workgroup per 16-row tile of W, the waves split K,
+// row-contiguous 16-byte weight loads staged through a wave-private LDS image (wave_image.h: one definition of the weight and the x
+// image for the FP4 and the NF4 kernels), scales re-read from it as broadcasts, loads one pass ahead,
+// v_mfma_f32_16x16x32_{bf16,f16} with one instruction never straddling two scales, partial tiles meeting in LDS.
 //
 // What differs is the decode: every weight goes to the matrix cores twice, as hi = T(code) and lo = T(code - hi) from one 256-entry
 // LDS table indexed by the packed byte.  nf4_mfma.h has the decode, the reason for it and fp16's 2^24 rule; here the weight is the
@@ -34,6 +34,7 @@
 #include "launchers.h"
 #include "nested_absmax.h"
 #include "nf4_mfma.h"
+#include "wave_image.h"
 
 namespace fp4 {
 
@@ -42,8 +43,7 @@ namespace {
 // Workgroup = 8 waves = one 16-row tile of W; wave w owns quant blocks (p*8 + w)*NBW.. of pass p.  Lane (r = l & 15, kb = l >> 4)
 // supplies, per 64-weight block, the 8 packed bytes [8kb, 8kb + 8) of row r: k-sets {16kb + 8t + j}, t = 0, 1, each fed as hi and as
 // lo - four matrix instructions per block and tile.  The B operand is x[n = l & 15][64b + 16kb + 8t + j], from a wave-private LDS
-// image for <= XS rows (XS in {4, 8}), else straight from L2.  Weight image row stride 32*NBW + 32 bytes (the row's NBW scales
-// follow its bytes), x image row stride 128*NBW + 16, as in the FP4 kernel.
+// image for <= XS rows (XS in {4, 8}), else straight from L2.  Both images are wave_image.h's, as in the FP4 kernel.
 // FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
 // MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R] and lora_ids[n] names activation row n's adapter; a row
@@ -60,13 +60,11 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     static_assert(!LORA || FUSED, "the adapter term comes with the fused epilogues");
     static_assert(!MULTI || LORA, "the adapter stack comes with the adapter term");
     static_assert(!NESTED || (FUSED && !MULTI), "nested absmax comes with the fused epilogues and without the adapter stack");
-    constexpr int kStageStride = 32 * NBW + 32;
-    constexpr int kXStride = 128 * NBW + 16;
-    constexpr int kWImageBytes = 8 * 16 * kStageStride;
-    constexpr int kXImageBytes = 8 * XS * kXStride;
-    constexpr int kImageBytes = kWImageBytes + kXImageBytes;
+    using WImg = WeightImage<NBW>;
+    using XImg = XImage<NBW, XS>;
+    constexpr int kWImageBytes = 8 * WImg::kBytes;
+    constexpr int kImageBytes = kWImageBytes + 8 * XImg::kBytes;
     constexpr int kPartBytes = 8 * 256 * 4;
-    static_assert(XS == 0 || ((XS * NBW) % 8 == 0 && (XS & (XS - 1)) == 0), "x staging: whole 16-byte units per lane");
     // the cross-wave partial sums reuse the images' storage after the K loop; the code table has storage of its own
     __shared__ __attribute__((aligned(16))) uint8_t s_raw[kImageBytes > kPartBytes ? kImageBytes : kPartBytes];
     __shared__ __attribute__((aligned(16))) u32x2 s_code[256];
@@ -84,30 +82,24 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
     const int64_t n_b = r < B ? r : B - 1;  // clamped rows / batch entries are computed, never stored
     const u32x4 *x4 = reinterpret_cast<const u32x4 *>(x);
 
-    constexpr int kXUnits = XS ? XS * NBW / 8 : 1;  // 16-byte units of the x image per lane
-    constexpr int kLanesPerRow = 2 * NBW, kRowsPerInstr = 64 / kLanesPerRow, kInstr = (16 + kRowsPerInstr - 1) / kRowsPerInstr;
     // 16 rows x NBW scales over 64 lanes (with NBW < 4 the upper lanes repeat rows: same address, same value)
     const int srow = (lane / NBW) & 15, sj0 = lane % NBW;
-    u32x4 xstage[kXUnits];
-    u32x4 wstage[kInstr];
+    u32x4 xstage[XImg::kUnits];
+    u32x4 wstage[WImg::kInstr];
     float amstage;
     [[maybe_unused]] uint32_t aqstage;  // NESTED: the block's code; amstage holds its group's scale
     auto issue_staged = [&](int pass) {  // x first (L2), then the weight stream (HBM), then the scales; all branch-free
         const int b0 = (pass * 8 + wave) * NBW;
         if constexpr (XS > 0) {
 #pragma unroll
-            for (int i = 0; i < kXUnits; ++i) {
-                const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
+            for (int i = 0; i < XImg::kUnits; ++i) {
+                const int n = XImg::unit_row(i, lane), c16 = XImg::unit_col(i, lane);
                 const int64_t nn = n < B ? n : B - 1;
                 xstage[i] = x4[((nn * K + 64 * b0) >> 3) + c16];
             }
         }
 #pragma unroll
-        for (int i = 0; i < kInstr; ++i) {
-            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;  // row of the tile this lane fetches
-            const int64_t row = row0 + (rr & 15) < M ? row0 + (rr & 15) : M - 1;
-            wstage[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(W) + ((row * K) >> 5) + 2 * b0 + (lane % kLanesPerRow));
-        }
+        for (int i = 0; i < WImg::kInstr; ++i) wstage[i] = __builtin_nontemporal_load(WImg::fetch_unit(W, i, lane, row0, M, K, b0));
         const int64_t row = row0 + srow < M ? row0 + srow : M - 1;
         if constexpr (NESTED) {
             const int64_t blk = row * nblk + b0 + sj0;
@@ -140,23 +132,20 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
             }
         }
         if (p > 0) __builtin_amdgcn_wave_barrier();  // the previous pass's reads are done before the image is rewritten
-        uint8_t *img = s_w + wave * 16 * kStageStride;
+        uint8_t *img = WImg::at(s_w, wave);
 #pragma unroll
-        for (int i = 0; i < kInstr; ++i) {
-            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
-            if (rr < 16) *reinterpret_cast<u32x4 *>(img + rr * kStageStride + 16 * (lane % kLanesPerRow)) = wstage[i];
+        for (int i = 0; i < WImg::kInstr; ++i) {
+            const int rr = WImg::fetch_row(i, lane);
+            if (WImg::inside(rr)) *WImg::unit(img, rr, lane) = wstage[i];
         }
         if constexpr (NESTED)
-            reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW)[sj0] = unnest_scale(s_ncode[aqstage], amstage, nested_offset);
+            WImg::scales(img, srow)[sj0] = unnest_scale(s_ncode[aqstage], amstage, nested_offset);
         else
-            reinterpret_cast<float *>(img + srow * kStageStride + 32 * NBW)[sj0] = amstage;
+            WImg::scales(img, srow)[sj0] = amstage;
         if constexpr (XS > 0) {
-            uint8_t *ximg = s_x + wave * XS * kXStride;
 #pragma unroll
-            for (int i = 0; i < kXUnits; ++i) {
-                const int u = i * 64 + lane, n = u / (8 * NBW), c16 = u % (8 * NBW);
-                *reinterpret_cast<u32x4 *>(ximg + n * kXStride + 16 * c16) = xstage[i];  // natural k order
-            }
+            for (int i = 0; i < XImg::kUnits; ++i)
+                *XImg::unit(XImg::at(s_x, wave), XImg::unit_row(i, lane), XImg::unit_col(i, lane)) = xstage[i];  // natural k order
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -165,11 +154,10 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
 
         u32x2 wq[NBW];
         float am[4][NBW];
-#pragma unroll
-        for (int j = 0; j < NBW; ++j) wq[j] = *reinterpret_cast<const u32x2 *>(img + r * kStageStride + 32 * j + 8 * kb);
+        WImg::read_frags(img, r, kb, wq);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const uint8_t *src = img + (kb * 4 + g) * kStageStride + 32 * NBW;
+            const float *src = WImg::scales(img, kb * 4 + g);
             if constexpr (NBW % 4 == 0) {
 #pragma unroll
                 for (int j = 0; j < NBW; j += 4) {
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
                 }
             } else {
 #pragma unroll
-                for (int j = 0; j < NBW; ++j) am[g][j] = reinterpret_cast<const float *>(src)[j];
+                for (int j = 0; j < NBW; ++j) am[g][j] = src[j];
             }
         }
 #pragma unroll
@@ -188,7 +176,7 @@ __global__ __launch_bounds__(512) void gemm_nf4_mfma_kernel(const uint16_t *__re
             for (int t = 0; t < 2; ++t) {
                 u32x4 bfrag;
                 if constexpr (XS > 0)
-                    bfrag = *reinterpret_cast<const u32x4 *>(s_x + wave * XS * kXStride + (r & (XS - 1)) * kXStride + 128 * j + 32 * kb + 16 * t);
+                    bfrag = *XImg::frag(XImg::at(s_x, wave), r, j, kb, t);
                 else
                     bfrag = xr[j][t];
                 const uint32_t q = t == 0 ? wq[j].x : wq[j].y;

@@ -49,6 +49,7 @@
 #include "launchers.h"
 #include "nested_absmax.h"
 #include "nf4_mfma.h"
+#include "wave_image.h"
 
 namespace fp4 {
 
@@ -57,7 +58,7 @@ namespace {
 // Lane (r = l & 15, kb = l >> 4).  Instruction t = 0, 1 of a block takes k = 32t .. 32t + 31 in natural order: the B operand is the
 // packed dword [16t + 4kb, 16t + 4kb + 4) of weight row r (k = 32t + 8kb + j), the A operand x[16nt + r][64b + 32t + 8kb + j], so
 // one x load instruction reads 64 contiguous bytes per activation row.  D: lane holds out[16nt + 4kb + reg][row0 + 16rt + r].
-// Weight image (per wave): 16 * RT rows of stride 32 * NBW + 32 bytes, the row's NBW scales behind its bytes.
+// Weight image (per wave): WeightImage<NBW, 16 * RT> of wave_image.h, the RT row tiles fetched and addressed as one image.
 // FUSED = false: `residual` and `mode` are ignored.  FUSED = true: store_small's residual add, or with kModeSiluMulPairs (M even) the
 // gate|up product into out[B][M / 2].  `residual` may alias `out` (each element is read, then written, by one thread).
 // MULTI = true (with LORA): lora_B is a stack of n_adapters arrays T[M][R] and lora_ids[n] names activation row n's adapter; a row
@@ -75,8 +76,8 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
     static_assert(!MULTI || LORA, "the adapter stack comes with the adapter term");
     static_assert(!NESTED || (FUSED && !MULTI), "nested absmax comes with the fused epilogues and without the adapter stack");
     constexpr int kRows = 16 * RT;
-    constexpr int kStageStride = 32 * NBW + 32;
-    constexpr int kImageBytes = 8 * kRows * kStageStride;
+    using WImg = WeightImage<NBW, kRows>;
+    constexpr int kImageBytes = 8 * WImg::kBytes;
     constexpr int kTiles = RT * NT;
     constexpr int kPartBytes = 4 * kTiles * 256 * 4;  // four slots: see the reduction below
     // the cross-wave partial sums reuse the images' storage after the K loop; the code table has storage of its own
@@ -94,20 +95,15 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
     const int passes = (nunits + 7) >> 3;
     const u32x4 *x4 = reinterpret_cast<const u32x4 *>(x);
 
-    constexpr int kLanesPerRow = 2 * NBW, kRowsPerInstr = 64 / kLanesPerRow, kInstr = (kRows + kRowsPerInstr - 1) / kRowsPerInstr;
     constexpr int kScaleInstr = (kRows * NBW + 63) / 64;  // with fewer than 64 scales the upper lanes repeat rows: same address, same value
-    u32x4 wstage[kInstr];
+    u32x4 wstage[WImg::kInstr];
     float amstage[kScaleInstr];
     [[maybe_unused]] uint32_t aqstage[NESTED ? kScaleInstr : 1];  // NESTED: the block's code; amstage holds its group's scale
     auto issue_staged = [&](int pass) {  // the weight stream (HBM), then the scales; branch-free, a unit past the end is clamped
         const int u = pass * 8 + wave;
         const int b0 = (u < nunits ? u : nunits - 1) * NBW;
 #pragma unroll
-        for (int i = 0; i < kInstr; ++i) {
-            const int rr = (i * kRowsPerInstr + lane / kLanesPerRow) % kRows;  // row of the workgroup's tiles this lane fetches
-            const int64_t row = row0 + rr < M ? row0 + rr : int64_t(M) - 1;
-            wstage[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(W) + ((row * K) >> 5) + 2 * b0 + (lane % kLanesPerRow));
-        }
+        for (int i = 0; i < WImg::kInstr; ++i) wstage[i] = __builtin_nontemporal_load(WImg::fetch_unit(W, i, lane, row0, M, K, b0));
 #pragma unroll
         for (int i = 0; i < kScaleInstr; ++i) {
             const int idx = i * 64 + lane, rr = (idx / NBW) % kRows;
@@ -145,7 +141,7 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
     }
     __syncthreads();
     const uint8_t *code = reinterpret_cast<const uint8_t *>(s_code);
-    uint8_t *img = s_raw + wave * kRows * kStageStride;
+    uint8_t *img = WImg::at(s_raw, wave);
 
     f32x4 acc[RT][NT];
 #pragma unroll
@@ -161,17 +157,17 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
         load_x(xcur, b0);
         if (p > 0) __builtin_amdgcn_wave_barrier();  // the previous pass's reads are done before the image is rewritten
 #pragma unroll
-        for (int i = 0; i < kInstr; ++i) {
-            const int rr = i * kRowsPerInstr + lane / kLanesPerRow;
-            if (rr < kRows) *reinterpret_cast<u32x4 *>(img + rr * kStageStride + 16 * (lane % kLanesPerRow)) = wstage[i];
+        for (int i = 0; i < WImg::kInstr; ++i) {
+            const int rr = WImg::fetch_row(i, lane);
+            if (WImg::inside(rr)) *WImg::unit(img, rr, lane) = wstage[i];
         }
 #pragma unroll
         for (int i = 0; i < kScaleInstr; ++i) {
             const int idx = i * 64 + lane, rr = (idx / NBW) % kRows;
             if constexpr (NESTED)
-                reinterpret_cast<float *>(img + rr * kStageStride + 32 * NBW)[idx % NBW] = unnest_scale(s_ncode[aqstage[i]], amstage[i], nested_offset);
+                WImg::scales(img, rr)[idx % NBW] = unnest_scale(s_ncode[aqstage[i]], amstage[i], nested_offset);
             else
-                reinterpret_cast<float *>(img + rr * kStageStride + 32 * NBW)[idx % NBW] = amstage[i];
+                WImg::scales(img, rr)[idx % NBW] = amstage[i];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -185,10 +181,9 @@ __global__ __launch_bounds__(512) void gemm_wide_nf4_kernel(const uint16_t *__re
             if (j + 1 < NBW) load_x(xnext, b0 + j + 1);
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-                const uint8_t *wrow = img + (16 * rt + r) * kStageStride;
-                const uint32_t wq[2] = {*reinterpret_cast<const uint32_t *>(wrow + 32 * j + 4 * kb),
-                                        *reinterpret_cast<const uint32_t *>(wrow + 32 * j + 16 + 4 * kb)};
-                const float am = reinterpret_cast<const float *>(wrow + 32 * NBW)[j];
+                uint8_t *wrow = WImg::row(img, 16 * rt + r);
+                const uint32_t wq[2] = {*WImg::frag4(wrow, j, kb, 0), *WImg::frag4(wrow, j, kb, 1)};
+                const float am = WImg::row_scales(wrow)[j];
                 f32x4 tile[NT], tile_lo[NT];
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) tile[nt] = tile_lo[nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
