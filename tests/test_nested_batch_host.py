@@ -118,11 +118,12 @@ class RouteExt(NestedExt):
     def __init__(self, real):
         super().__init__(real)
         self.refuse = set()
+        self.refuse_text = {}  # op -> the words of its refusal, where "not covered" is not what the case is about
 
     def _answer(self, name, A, Bshape, residual=None):
         self.calls.append((name, A.numel() // A.shape[-1], residual is not None))
         if name in self.refuse:
-            raise RuntimeError(f"{name}: B=.. is not covered (..)")
+            raise RuntimeError(self.refuse_text.get(name, f"{name}: B=.. is not covered (..)"))
         return torch.zeros(A.shape[:-1] + (Bshape[0],), dtype=A.dtype)
 
     def qlinear_nf4_nested(self, A, B, q, nested, code, offset, g, M, K, bs, bias):
@@ -138,7 +139,7 @@ class RouteExt(NestedExt):
     def lora_down(self, x, A, scale):
         self.calls.append(("lora_down", x.numel() // x.shape[-1], False))
         if "lora_down" in self.refuse:
-            raise RuntimeError("lora_down: R=.. is not covered")
+            raise RuntimeError(self.refuse_text.get("lora_down", "lora_down: R=.. is not covered"))
         return torch.zeros(x.numel() // x.shape[-1], A.shape[0])
 
     def gemv_nf4_lora_nested(self, A, B, q, nested, code, offset, g, bs, Bshape, bias, residual, epi, lB, t):
@@ -268,6 +269,113 @@ def test_lora_nested_linear_routing(route):
     assert [c[0] for c in route.calls] == ["gemv_nf4_nested"] and not wide._lora_ok
     with pytest.raises(ValueError, match="adapter shapes"):
         pkg.LoRANestedNF4Linear.from_nested(_layer(), A, B[:40], 2.0)
+
+
+LADDER_EVENTS = ["one row", "2..64 rows", "65 rows", "not ahead", "down refuses", "gemv refuses", "batched refuses", "other error in down",
+                 "other error in up", "residual cell", "misaligned x"]
+
+
+@pytest.mark.parametrize("event", LADDER_EVENTS)
+def test_every_event_of_the_adapter_ladder(route, monkeypatch, event):
+    """Each event of LoRANestedNF4Linear's forward ladder: the extension calls it makes (op, rows, whether it was handed the
+    residual), the route flags afterwards and the output bits.  The double answers zeros, so a fused route gives zeros - plus the
+    residual where torch adds it - and the fallback gives the adapter term restated here: (x A^T * s) B^T in f32, one cast, then
+    the residual."""
+    M, K, bf16 = 48, 512, torch.bfloat16
+    rnd = lambda *shape, dtype=bf16: torch.randn(*shape, generator=torch.Generator().manual_seed(sum(shape))).to(dtype)  # noqa: E731
+    flags = lambda l: (l._lora_ok, l._gemv_lora_ok, l._gemm_lora_ok, l._batched_ok)  # noqa: E731
+    fresh = lambda M=M, K=K: pkg.LoRANestedNF4Linear.from_nested(_layer(M, K), *_adapter(M, K, 5, 3), 2.0)  # noqa: E731
+    gemv, gemm = "gemv_nf4_lora_nested", "gemm_nf4_lora_nested"
+
+    def call(layer, x, r=None):
+        route.calls.clear()
+        y = layer(x, r)
+        return y, list(route.calls)
+
+    def fallback_bits(layer, x, r):
+        A, B = layer.lora_A.to(x.dtype), layer.lora_B.to(x.dtype)
+        y = (torch.zeros(x.shape[0], layer.out_features) + (x.float() @ A.float().t() * layer.lora_scale) @ B.float().t()).to(x.dtype)
+        return y if r is None else y + r
+
+    if event == "one row":  # f32 as well: the resident GEMV takes it, and the layer has no compute dtype of its own
+        layer = fresh()
+        for dtype in (bf16, torch.float16, torch.float32):
+            x, r = rnd(1, K, dtype=dtype), rnd(1, M, dtype=dtype)
+            y, calls = call(layer, x, r)
+            assert calls == [("lora_down", 1, False), (gemv, 1, True)] and flags(layer) == (True,) * 4
+            assert y.dtype == dtype and torch.equal(y, torch.zeros(1, M, dtype=dtype))
+    elif event == "2..64 rows":
+        layer = fresh()
+        for rows in (2, 64):
+            y, calls = call(layer, rnd(rows, K), rnd(rows, M))
+            assert calls == [("lora_down", rows, False), (gemm, rows, True)] and flags(layer) == (True,) * 4
+            assert torch.equal(y, torch.zeros(rows, M, dtype=bf16))
+        y, calls = call(layer, rnd(4, K, dtype=torch.float32))  # several rows of f32 are outside the matrix-core kernels
+        assert calls == [("qlinear_nf4_nested", 4, False)] and flags(layer) == (True,) * 4
+    elif event == "65 rows":
+        layer = fresh()
+        x, r = rnd(65, K), rnd(65, M)
+        y, calls = call(layer, x, r)
+        assert calls == [("qlinear_nf4_nested", 65, False)] and flags(layer) == (True,) * 4 and torch.equal(y, fallback_bits(layer, x, r))
+    elif event == "not ahead":  # no down call at all: the base on the layer's own path, the adapter in torch
+        monkeypatch.setattr(fused_mod, "lora_fused_ahead", lambda rows, M, K, rank: False)
+        layer = fresh()
+        for rows, base in ((1, "gemv_nf4_nested"), (4, "qlinear_nf4_nested")):
+            x, r = rnd(rows, K), rnd(rows, M)
+            y, calls = call(layer, x, r)
+            assert calls == [(base, rows, False)] and flags(layer) == (True,) * 4 and torch.equal(y, fallback_bits(layer, x, r))
+    elif event == "down refuses":  # "not covered" clears _lora_ok alone; the next call makes no down call
+        route.refuse.add("lora_down")
+        layer = fresh()
+        x, r = rnd(4, K), rnd(4, M)
+        y, calls = call(layer, x, r)
+        assert calls == [("lora_down", 4, False), ("qlinear_nf4_nested", 4, False)] and flags(layer) == (False, True, True, True)
+        assert torch.equal(y, fallback_bits(layer, x, r))
+        assert call(layer, rnd(1, K))[1] == [("gemv_nf4_nested", 1, False)] and flags(layer) == (False, True, True, True)
+    elif event in ("gemv refuses", "batched refuses"):  # either wording clears the flag of the op that refused, and only that one
+        op, rows, base, other, other_rows, left = ((gemv, 1, "gemv_nf4_nested", gemm, 4, (True, False, True, True)) if event == "gemv refuses" else
+                                                   (gemm, 4, "qlinear_nf4_nested", gemv, 1, (True, True, False, True)))
+        route.refuse.add(op)
+        for text in ("the fused epilogue is not available for M=48 K=512", "M=48 K=512 blocksize=64 dtype=2 is not covered"):
+            route.refuse_text[op] = f"fp4_hip_{op}: {text}"
+            layer = fresh()
+            x, r = rnd(rows, K), rnd(rows, M)
+            y, calls = call(layer, x, r)
+            assert calls == [("lora_down", rows, False), (op, rows, True), (base, rows, False)] and flags(layer) == left
+            assert torch.equal(y, fallback_bits(layer, x, r)), text
+            assert call(layer, x, r)[1] == [(base, rows, False)]  # not tried again
+            y, calls = call(layer, rnd(other_rows, K), rnd(other_rows, M))  # the other route still runs
+            assert calls == [("lora_down", other_rows, False), (other, other_rows, True)] and flags(layer) == left
+    elif event in ("other error in down", "other error in up"):  # any other RuntimeError propagates with every flag untouched
+        for op, row_counts in ((("lora_down", (1, 4)),) if event == "other error in down" else ((gemv, (1,)), (gemm, (4,)))):
+            route.refuse.add(op)
+            route.refuse_text[op] = "hipErrorLaunchFailure"
+            layer = fresh()
+            for rows in row_counts:
+                route.calls.clear()
+                with pytest.raises(RuntimeError, match="LaunchFailure"):
+                    layer(rnd(rows, K), rnd(rows, M))
+                assert [c[0] for c in route.calls] == (["lora_down"] if op == "lora_down" else ["lora_down", op]) and flags(layer) == (True,) * 4
+    elif event == "residual cell":  # 33 rows, K = 8192: the op gets None and torch adds the residual; at 32 rows it goes to the op
+        layer = fresh(8, 8192)
+        for rows, in_kernel in ((33, False), (32, True)):
+            r = rnd(rows, 8)
+            y, calls = call(layer, rnd(rows, 8192), r)
+            assert calls == [("lora_down", rows, False), (gemm, rows, in_kernel)] and flags(layer) == (True,) * 4
+            assert torch.equal(y, torch.zeros(rows, 8, dtype=bf16) if in_kernel else r), rows
+    elif event == "misaligned x":  # an address belongs to the call: one copy, no refusal, flags intact
+        from fake_ext import Strict
+
+        for mod in (nested_mod, fused_mod):
+            monkeypatch.setattr(mod, "ext", Strict(route))
+        layer = fresh()
+        for rows in (1, 4):
+            x = rnd(rows * K + 8)[1:1 + rows * K].view(rows, K)
+            assert x.data_ptr() % 16 != 0
+            y, calls = call(layer, x, rnd(rows, M))
+            assert calls == [("lora_down", rows, False), (gemv if rows == 1 else gemm, rows, True)] and flags(layer) == (True,) * 4
+    else:
+        raise AssertionError(event)
 
 
 class _MLP(nn.Module):

@@ -111,6 +111,7 @@ class LoraExt(FusedNf4Ext):
 
     def _lora(self, A, B, absmax, blocksize, Bshape, bias, residual, epilogue, lora_B, t, gemv):
         M, K = Bshape
+        self.residual_seen = residual is not None  # whether the last adapter op was handed the residual
         assert lora_B.dtype == A.dtype and tuple(lora_B.shape) == (M, t.shape[1]) and t.dtype == torch.float32 and t.shape[1] % 8 == 0
         name = {torch.float16: "float16", torch.bfloat16: "bfloat16", torch.float32: "float32"}[A.dtype]
         w = R.dequantize_f32(B.numpy().ravel(), absmax.numpy(), blocksize, M * K).reshape(M, K).astype(np.float64)
@@ -302,6 +303,147 @@ def test_refusals_flip_the_flags_and_the_fallback_answers(fx):
     third = pkg.LoRANF4Linear.from_linear(g, *_adapter(M, K, 8, 1), 2.0)
     with pytest.raises(RuntimeError, match="LaunchFailure"):
         third(x1)
+
+
+# ---- every event of the adapter forward ladder ---------------------------------------------------------------------------------------------
+class Ladder:
+    """One kind of adapter layer for :func:`run_ladder_event`: how to build it, what its three ops and their ``refuse_*`` switches on
+    the double are called, and its two routes restated - the fused one from the double's numpy restatement called directly, the
+    fallback as base + delta in f32, one cast, the epilogue and the residual in torch.  test_nf4_multi_lora_host.py subclasses it."""
+
+    down, gemv, gemm = "lora_down", "gemv_nf4_lora", "gemm_nf4_lora"
+    refuse = {"down": "refuse_down", "gemv": "refuse_gemv_lora", "gemm": "refuse_gemm_lora"}
+
+    def __init__(self, fx):
+        self.fx = fx
+
+    def layer(self, M=32, K=128, gated=False):
+        if gated:
+            return pkg.LoRANF4Linear.gate_up(_nf4_layer(M, K, 1), _nf4_layer(M, K, 2), (*_adapter(M, K, 4, 1), 2.0), (*_adapter(M, K, 6, 2), 0.5))
+        return pkg.LoRANF4Linear.from_linear(_nf4_layer(M, K, 1), *_adapter(M, K, 5, 3), 2.0)
+
+    def select(self, rows):
+        pass
+
+    def fused_bits(self, layer, x, residual, gemv):
+        qd = layer.quant_data
+        t = self.fx.lora_down(x.contiguous(), layer.lora_A, layer.lora_scale)
+        return self.fx._lora(x.contiguous(), qd._B_t, qd.absmax, 64, [qd.M, qd.N], qd.bias, residual, layer.epilogue, layer.lora_B, t, gemv)
+
+    def delta(self, layer, x):
+        return (x.float() @ layer.lora_A.float().t() * layer.lora_scale) @ layer.lora_B.float().t()
+
+    def fallback_bits(self, layer, x, residual):
+        twin = pkg.FusedNF4Linear(layer.quant_data, layer.epilogue)  # the base alone, on the routes the layer has left
+        twin._fused_ok, twin._small_ok = layer._fused_ok, layer._small_ok
+        base = twin.quant_data.forward(x) if layer.epilogue == GATED else twin(x)
+        y = (base.float() + self.delta(layer, x)).to(x.dtype)
+        if layer.epilogue == GATED:
+            y = torch.nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
+        return y if residual is None else y + residual
+
+
+LADDER_EVENTS = ["one row", "2..64 rows", "65 rows", "not ahead", "down refuses", "gemv refuses", "batched refuses", "other error in down",
+                 "other error in up", "residual cell", "misaligned x"]
+
+
+def run_ladder_event(c, monkeypatch, event):
+    """Each event of the adapter layers' forward ladder: the extension calls it makes, the route flags afterwards and the output bits."""
+    fx = c.fx
+    bf16 = torch.bfloat16
+    rnd = lambda *shape: torch.randn(*shape, generator=torch.Generator().manual_seed(sum(shape))).to(bf16)  # noqa: E731
+    flags = lambda layer: (layer._lora_ok, layer._fused_ok, layer._small_ok)  # noqa: E731
+
+    def call(layer, x, r=None):
+        c.select(x.numel() // x.shape[-1])
+        fx.calls.clear()
+        y = layer(x, r)
+        return y, list(fx.calls)
+
+    if event in ("one row", "2..64 rows"):
+        for gated in (False, True):
+            layer = c.layer(gated=gated)
+            for rows in ((1,) if event == "one row" else (2, 64)):
+                x, r = rnd(rows, 128), rnd(rows, 32)
+                y, calls = call(layer, x, r)
+                assert calls == [c.down, c.gemv if rows == 1 else c.gemm] and flags(layer) == (True, True, True) and fx.residual_seen
+                assert torch.equal(y, c.fused_bits(layer, x, r, rows == 1)), (gated, rows)
+    elif event == "65 rows":
+        for gated in (False, True):
+            layer = c.layer(gated=gated)
+            x, r = rnd(65, 128), rnd(65, 32)
+            y, calls = call(layer, x, r)
+            assert calls == ["qlinear_nf4_bias"] and flags(layer) == (True, True, True)
+            assert torch.equal(y, c.fallback_bits(layer, x, r)), gated
+    elif event == "not ahead":  # no down call at all: the base on its own fused route, the adapter in torch
+        monkeypatch.setattr(fused_mod, "lora_fused_ahead", lambda rows, M, K, rank: False)
+        for gated, want in ((False, {1: ["gemv_nf4_fused"], 4: ["gemm_nf4_fused"]}), (True, {1: ["gemv_nf4_bias"], 4: ["qlinear_nf4_bias"]})):
+            layer = c.layer(gated=gated)
+            for rows in (1, 4):
+                x, r = rnd(rows, 128), rnd(rows, 32)
+                y, calls = call(layer, x, r)
+                assert calls == want[rows] and flags(layer) == (True, True, True)
+                assert torch.equal(y, c.fallback_bits(layer, x, r)), (gated, rows)
+    elif event == "down refuses":  # "not covered" clears _lora_ok alone; the next call makes no down call
+        setattr(fx, c.refuse["down"], "fp4_hip_lora_down: Bt=4 R=8 K=128 is not covered")
+        layer = c.layer()
+        x, r = rnd(4, 128), rnd(4, 32)
+        y, calls = call(layer, x, r)
+        assert calls == [c.down, "gemm_nf4_fused"] and flags(layer) == (False, True, True)
+        assert torch.equal(y, c.fallback_bits(layer, x, r))
+        y, calls = call(layer, rnd(1, 128))
+        assert calls == ["gemv_nf4_fused"] and flags(layer) == (False, True, True)
+    elif event in ("gemv refuses", "batched refuses"):  # either wording clears the flag of the op that refused, and only that one
+        which, rows, other_rows = ("gemv", 1, 4) if event == "gemv refuses" else ("gemm", 4, 1)
+        for text in ("the fused epilogue is not available for M=32 K=128", "M=32 K=128 blocksize=64 dtype=2 is not covered"):
+            setattr(fx, c.refuse[which], f"fp4_hip_{which}_lora_nf4: {text}")
+            layer = c.layer()
+            x, r = rnd(rows, 128), rnd(rows, 32)
+            y, calls = call(layer, x, r)
+            left = (True, False, True) if which == "gemv" else (True, True, False)
+            assert calls == [c.down, getattr(c, which), "gemv_nf4_bias" if which == "gemv" else "qlinear_nf4_bias"] and flags(layer) == left
+            assert torch.equal(y, c.fallback_bits(layer, x, r)), text
+            assert call(layer, x, r)[1] == ["gemv_nf4_bias" if which == "gemv" else "qlinear_nf4_bias"]  # not tried again
+            x, r = rnd(other_rows, 128), rnd(other_rows, 32)
+            y, calls = call(layer, x, r)  # the other route still runs
+            assert calls == [c.down, c.gemm if which == "gemv" else c.gemv] and flags(layer) == left
+            assert torch.equal(y, c.fused_bits(layer, x, r, which == "gemm"))
+    elif event in ("other error in down", "other error in up"):  # any other RuntimeError propagates with every flag untouched
+        for which in (("down",) if event == "other error in down" else ("gemv", "gemm")):
+            setattr(fx, c.refuse[which], "hipErrorLaunchFailure")
+            layer = c.layer()
+            for rows in ((1, 4) if which == "down" else (1,) if which == "gemv" else (4,)):
+                c.select(rows)
+                fx.calls.clear()
+                with pytest.raises(RuntimeError, match="LaunchFailure"):
+                    layer(rnd(rows, 128), rnd(rows, 32))
+                assert fx.calls == ([c.down] if which == "down" else [c.down, getattr(c, which)]) and flags(layer) == (True, True, True)
+    elif event == "residual cell":  # 33 rows, K = 8192, plain epilogue: the op gets None and torch adds; 32 rows and gate|up: in the op
+        for gated, rows, in_kernel in ((False, 33, False), (False, 32, True), (True, 33, True)):
+            layer = c.layer(8, 8192, gated)
+            x, r = rnd(rows, 8192), rnd(rows, 8)
+            y, calls = call(layer, x, r)
+            assert calls == [c.down, c.gemm] and fx.residual_seen is in_kernel and flags(layer) == (True, True, True)
+            want = c.fused_bits(layer, x, r, False) if in_kernel else c.fused_bits(layer, x, None, False) + r
+            assert torch.equal(y, want), (gated, rows)
+    elif event == "misaligned x":  # an address belongs to the call: one copy, no refusal, flags intact
+        from fake_ext import Strict
+
+        monkeypatch.setattr(fused_mod, "ext", Strict(fx))
+        layer = c.layer()
+        for rows in (1, 4):
+            x = rnd(rows * 128 + 8)[1:1 + rows * 128].view(rows, 128)
+            assert x.data_ptr() % 16 != 0
+            y, calls = call(layer, x, rnd(rows, 32))
+            assert calls == [c.down, c.gemv if rows == 1 else c.gemm] and flags(layer) == (True, True, True)
+            assert torch.equal(y, c.fused_bits(layer, x.clone(), rnd(rows, 32), rows == 1))
+    else:
+        raise AssertionError(event)
+
+
+@pytest.mark.parametrize("event", LADDER_EVENTS)
+def test_every_event_of_the_adapter_ladder(fx, monkeypatch, event):
+    run_ladder_event(Ladder(fx), monkeypatch, event)
 
 
 # ---- surgery -----------------------------------------------------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ import nf4_multi_lora_cases as MC
 import nf4_ref as R
 import torch_bnb_fp4 as pkg
 from test_nf4_fused_host import _nf4_layer, _fp4_layer
-from test_nf4_lora_host import LoraExt, _adapter, _dense, _peft_state, _toy
+from test_nf4_lora_host import LADDER_EVENTS, Ladder, LoraExt, _adapter, _dense, _peft_state, _toy, run_ladder_event
 from torch_bnb_fp4 import functional as F_mod, fused as fused_mod, quant_data as qd_mod
 
 NONE, GATED = 0, 1
@@ -342,6 +342,52 @@ def test_refusals_flip_the_flags_and_the_fallback_answers(fx):
     _, _, third = _layer(M, K, (8, 8), sel)
     with pytest.raises(RuntimeError, match="LaunchFailure"):
         third(x4)
+
+
+# ---- every event of the adapter forward ladder ---------------------------------------------------------------------------------------------
+class MultiLadder(Ladder):
+    """test_nf4_lora_host.Ladder for a stack of two adapters and ids that mix both with rows of the bare base model."""
+
+    down, gemv, gemm = "lora_down_multi", "gemv_nf4_lora_multi", "gemm_nf4_lora_multi"
+    refuse = {"down": "refuse_down_multi", "gemv": "refuse_gemv_multi", "gemm": "refuse_gemm_multi"}
+
+    def __init__(self, fx):
+        super().__init__(fx)
+        self.sel = pkg.AdapterSelection(capacity=128)
+
+    def layer(self, M=32, K=128, gated=False):
+        if gated:
+            pairs = [((*_adapter(M, K, 4, 1), 2.0), (*_adapter(M, K, 6, 2), 0.5)), ((*_adapter(M, K, 2, 3), 1.0), (*_adapter(M, K, 1, 4), 3.0))]
+            return pkg.MultiLoRANF4Linear.gate_up_from_fused(pkg.FusedNF4Linear.gate_up(_nf4_layer(M, K, 1), _nf4_layer(M, K, 2)), pairs, self.sel)
+        return pkg.MultiLoRANF4Linear.from_linear(_nf4_layer(M, K, 1), [(*_adapter(M, K, 5, 3), 2.0), (*_adapter(M, K, 12, 4), 0.5)], self.sel)
+
+    def select(self, rows):
+        self.sel.set([(1, -1, 0, 2)[b % 4] for b in range(rows)])
+
+    def fused_bits(self, layer, x, residual, gemv):
+        qd, ids = layer.quant_data, self.sel.ids
+        t = self.fx.lora_down_multi(x.contiguous(), layer.lora_A_stack, layer.lora_scale_stack, ids)
+        return self.fx._multi(x.contiguous(), qd._B_t, qd.absmax, 64, [qd.M, qd.N], qd.bias, residual, layer.epilogue, layer.lora_B_stack, ids, t, gemv)
+
+    def delta(self, layer, x):
+        terms = [(self.sel.ids == a).to(torch.float32).unsqueeze(1)
+                 * ((x.float() @ layer.lora_A_stack[a].float().t() * layer.lora_scale_stack[a]) @ layer.lora_B_stack[a].float().t())
+                 for a in range(layer.n_adapters)]
+        return terms[0] + terms[1]
+
+
+@pytest.mark.parametrize("event", LADDER_EVENTS + ["id count"])
+def test_every_event_of_the_adapter_ladder(fx, monkeypatch, event):
+    c = MultiLadder(fx)
+    if event != "id count":
+        return run_ladder_event(c, monkeypatch, event)
+    layer = c.layer()
+    for have, rows in ((3, 1), (1, 4), (64, 65)):  # raised ahead of every route, the fallback's included; nothing is called or cleared
+        c.sel.set([0] * have)
+        fx.calls.clear()
+        with pytest.raises(ValueError, match="one id per row"):
+            layer(torch.zeros(rows, 128, dtype=torch.bfloat16))
+        assert fx.calls == [] and (layer._lora_ok, layer._fused_ok, layer._small_ok) == (True, True, True)
 
 
 # ---- surgery -----------------------------------------------------------------------------------------------------------------------------

@@ -48,3 +48,19 @@ with torch.inference_mode():
     bench("ext.gemv_nf4_fused (raw extension op)", lambda: pkg.ext.gemv_nf4_fused(x, nf4_B, nf4_absmax, 64, [M, K], None, None, 0))
     bench("ext.gemm_nf4_fused 4 rows (raw extension op)", lambda: pkg.ext.gemm_nf4_fused(xb, nf4_B, nf4_absmax, 64, [M, K], None, None, 0))
     bench("ext.gemm_small_fp4 4 rows (raw extension op)", lambda: pkg.ext.gemm_small_fp4(xb, qd._B_t, qd.absmax, 64, qd._shape_list, None))
+    # the adapter layers: one forward ladder (torch_bnb_fp4/fused.py) above two launches each, rank 16
+    from torch_bnb_fp4.nested import nest_absmax  # noqa: E402
+
+    rank = 16
+    adapter = lambda seed: (torch.randn(rank, K, device=dev, dtype=torch.bfloat16, generator=torch.Generator(dev).manual_seed(seed)) / K**0.5,  # noqa: E731
+                            torch.randn(M, rank, device=dev, dtype=torch.bfloat16, generator=torch.Generator(dev).manual_seed(seed + 1)) * 0.05, 2.0)
+    fused = pkg.FusedNF4Linear.from_packed(nf4_packed, nf4_absmax, (M, K), 64, dtype=torch.bfloat16)
+    selection = pkg.AdapterSelection(device=dev)
+    resident = pkg.NestedNF4Linear(nf4_packed, *nest_absmax(nf4_absmax), (M, K), 64, None, torch.bfloat16)
+    layers = {"LoRANF4Linear": pkg.LoRANF4Linear.from_fused(fused, *adapter(1)),
+              "MultiLoRANF4Linear, 2 adapters": pkg.MultiLoRANF4Linear.from_fused(fused, [adapter(1), adapter(3)], selection),
+              "LoRANestedNF4Linear": pkg.LoRANestedNF4Linear.from_nested(resident, *adapter(1))}
+    for rows, xr in ((1, x), (4, xb)):
+        selection.set([0, 1, -1, 0][:rows])
+        for name, layer in layers.items():
+            bench(f"{name} {rows} row{'s' if rows > 1 else ''}", lambda: layer(xr))

@@ -21,7 +21,14 @@ the fused kernels do not cover, run the unfused sequence through :class:`QuantDa
 :class:`LoRANF4Linear` is a :class:`FusedNF4Linear` with a LoRA adapter beside the 4-bit weight (QLoRA serving: the adapter cannot
 be merged into NF4 without re-quantising): ``y = W x + B (s * A x)`` as two launches, the down projection ``t = s * A x`` in f32
 (``fp4_hip_lora_down``) and the same fused kernels with ``B t`` added to their f32 row sums before the rounding
-(``fp4_hip_gemv_lora_nf4`` / ``fp4_hip_gemm_lora_nf4``).
+(``fp4_hip_gemv_lora_nf4`` / ``fp4_hip_gemm_lora_nf4``).  :class:`MultiLoRANF4Linear` holds a stack of adapters and picks one per
+activation row on the device (:class:`AdapterSelection`).
+
+The adapter layers - these two and :class:`~torch_bnb_fp4.nested.LoRANestedNF4Linear` - share :class:`LoRAAdapterMixin`: one holder
+(validation, padding, the buffers under each class's own state-dict keys, the per-dtype cast cache) and one forward ladder
+(``_adapter_forward``: :func:`lora_fused_ahead`, the down op, the measured residual exception, the one-row or batched op, the flags a
+refusal clears, the torch fallback).  Each layer's ``forward`` keeps its own guards and names its ops, flags and operands; the routing
+rules of the NF4 ops themselves are ``nf4_batched_covers``, ``nf4_small_cell`` and ``nf4_residual_in_kernel`` in ``quant_data.py``.
 """
 from __future__ import annotations
 
@@ -33,10 +40,17 @@ from torch import nn
 
 from ._ext import ext
 from .nn import QuantState, fp4_code, nf4_code
-from .quant_data import QuantData, aligned16, small_fp4_covers
+from .quant_data import QuantData, aligned16, nf4_batched_covers, nf4_residual_in_kernel, small_fp4_covers
 
 EPILOGUE_NONE = 0
 EPILOGUE_SILU_MUL_PAIRS = 1
+
+
+def epilogue_in_torch(y: torch.Tensor, epilogue: int, residual: Optional[torch.Tensor]) -> torch.Tensor:
+    """The epilogue as torch ops over a rounded ``W x + bias``: silu(gate) * up on interleaved gate | up columns, then the residual."""
+    if epilogue == EPILOGUE_SILU_MUL_PAIRS:
+        y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
+    return y if residual is None else y + residual
 
 
 def interleave_rows(a: Tuple[torch.Tensor, torch.Tensor], b: Tuple[torch.Tensor, torch.Tensor], shape: Sequence[int], blocksize: int
@@ -160,10 +174,17 @@ class FusedFP4Linear(nn.Module):
 
     # -- forward -----------------------------------------------------------------------------------------------------
     def _unfused(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
-        y = self.quant_data.forward(x)
-        if self.epilogue == EPILOGUE_SILU_MUL_PAIRS:
-            y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
-        return y if residual is None else y + residual
+        return epilogue_in_torch(self.quant_data.forward(x), self.epilogue, residual)
+
+    # what a subclass that adds a term of its own ahead of the epilogue (an adapter) asks of this layer
+    def _before_epilogue(self, x: torch.Tensor) -> torch.Tensor:
+        """``W x + bias`` rounded to the activation dtype, on this class's own routes where the epilogue is the plain one."""
+        return self.quant_data.forward(x) if self.epilogue == EPILOGUE_SILU_MUL_PAIRS else FusedFP4Linear.forward(self, x)
+
+    def _kernel_operands(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> tuple:
+        """The operands of a fused op between the activation and an adapter's own."""
+        qd = self.quant_data
+        return qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual, self.epilogue
 
     # forward()'s ladder is this class's alone; a subclass over another code names its two ops and says what its batched op covers
     _gemv_op = "gemv_fp4_fused"
@@ -245,15 +266,13 @@ class FusedNF4Linear(FusedFP4Linear):
     _batched_op = "gemm_nf4_fused"
 
     def _batched_covers(self, rows: int, K: int, dtype: torch.dtype) -> bool:
-        return 2 <= rows <= 64 and dtype in (torch.float16, torch.bfloat16) and self.quant_data.blocksize == 64 and K % 64 == 0
+        return nf4_batched_covers(rows, K, self.quant_data.blocksize, dtype)
 
     def _gemv_wants_alignment(self) -> bool:
         return True  # fp4_hip_gemv_fused_nf4 has no generic kernel behind it: either epilogue refuses an address off 16 bytes
 
     def _residual_in_kernel(self, rows: int, K: int) -> bool:
-        # the one cell in which the fused residual add measured no gain (profiles/nf4_fused_epilogues.json): more than 32 rows against
-        # rows of 8192 and more weights with the plain epilogue - there the add stays torch's
-        return not (self.epilogue == EPILOGUE_NONE and rows > 32 and K >= 8192)
+        return nf4_residual_in_kernel(rows, K, self.epilogue)  # all but the one measured cell, where the add stays torch's
 
 
 LORA_RANK_MULTIPLE = 8  # the kernels read B and t in 16-byte units
@@ -280,16 +299,26 @@ def lora_fused_ahead(rows: int, M: int, K: int, rank: int) -> bool:
     return M * rows * rank <= limit
 
 
-def pad_adapter(lora_A: torch.Tensor, lora_B: torch.Tensor, scale: torch.Tensor):
-    """Zero rows of A, zero columns of B and zero factors up to the next multiple of 8 of the rank.  Exact: a padded row of A gives
-    t = 0 and a padded column of B multiplies it by 0."""
-    r = lora_A.shape[0]
-    pad = -r % LORA_RANK_MULTIPLE
+def pad_adapter_to(lora_A: torch.Tensor, lora_B: torch.Tensor, scale: torch.Tensor, rank: int):
+    """Zero rows of A, zero columns of B and zero factors up to a given rank.  Exact: a padded row of A gives t = 0 and a padded
+    column of B multiplies it by 0."""
+    pad = rank - lora_A.shape[0]
+    if pad < 0:
+        raise ValueError(f"cannot pad an adapter of rank {lora_A.shape[0]} to {rank}")
     if pad:
         lora_A = torch.cat([lora_A, lora_A.new_zeros(pad, lora_A.shape[1])], 0)
         lora_B = torch.cat([lora_B, lora_B.new_zeros(lora_B.shape[0], pad)], 1)
         scale = torch.cat([scale, scale.new_zeros(pad)], 0)
     return lora_A.contiguous(), lora_B.contiguous(), scale.contiguous()
+
+
+def padded_rank(rank: int) -> int:
+    return rank + -rank % LORA_RANK_MULTIPLE
+
+
+def pad_adapter(lora_A: torch.Tensor, lora_B: torch.Tensor, scale: torch.Tensor):
+    """:func:`pad_adapter_to` the next multiple of 8 of the rank."""
+    return pad_adapter_to(lora_A, lora_B, scale, padded_rank(lora_A.shape[0]))
 
 
 def stack_gate_up_adapters(gate_adapter, up_adapter):
@@ -314,40 +343,101 @@ def lora_scaling(r: int, lora_alpha: float, use_rslora: bool = False) -> float:
 
 
 class LoRAAdapterMixin:
-    """One LoRA adapter held beside a 4-bit weight, shared by :class:`LoRANF4Linear` and
-    :class:`~torch_bnb_fp4.nested.LoRANestedNF4Linear`: the buffers ``lora_A`` / ``lora_B`` / ``lora_scale`` padded to a multiple of 8
-    (:func:`pad_adapter`), ``rank``, ``_lora_ok`` and the per-dtype casts."""
+    """What :class:`LoRANF4Linear`, :class:`MultiLoRANF4Linear` and :class:`~torch_bnb_fp4.nested.LoRANestedNF4Linear` share: the
+    adapter - or stack of adapters - held beside a 4-bit weight, and the one forward ladder over it.
 
-    def _init_adapter(self, lora_A: torch.Tensor, lora_B: torch.Tensor, scale, M: int, K: int, dev) -> None:
+    Holder.  :meth:`_checked_adapter` validates one ``(A, B, scale)``; :meth:`_hold` registers the padded tensors under the class's
+    three buffer names (``_adapter_buffers``: they are state-dict keys), sets ``_lora_ok`` and starts the per-dtype cast cache.
+
+    Ladder (:meth:`_adapter_forward`).  A layer's ``forward`` keeps its own guards, decides ``one`` / ``many`` and hands over.  What
+    is the layer's own it names as data - ``_lora_ops`` (the down op, the one-row op, the batched op) and ``_lora_route_flags`` (the
+    flags the last two clear) - or answers as a method of the class this is mixed into: ``_kernel_operands(x, residual)``,
+    ``_residual_in_kernel(rows, K)``, ``_before_epilogue(x)`` and ``epilogue``.  The ladder never asks which layer it serves."""
+
+    _adapter_buffers = ("lora_A", "lora_B", "lora_scale")
+
+    # -- holder ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _checked_adapter(lora_A: torch.Tensor, lora_B: torch.Tensor, scale, M: int, K: int, dev):
+        """One ``(A [r, K], B [M, r], scale)`` checked against a ``[M, K]`` weight and moved to ``dev``, the scale as float32 ``[r]``."""
         if lora_A.ndim != 2 or lora_B.ndim != 2 or lora_A.shape[1] != K or lora_B.shape != (M, lora_A.shape[0]):
             raise ValueError(f"adapter shapes {tuple(lora_A.shape)} / {tuple(lora_B.shape)} do not fit a [{M}, {K}] weight (need A [r, K] "
                              "and B [M, r])")
-        self.rank = int(lora_A.shape[0])
+        r = int(lora_A.shape[0])
         if not torch.is_tensor(scale):
-            scale = torch.full((self.rank,), float(scale))
-        if scale.numel() != self.rank:
-            raise ValueError(f"scale must be one factor or one per adapter row ({self.rank}), got {scale.numel()}")
-        A, B, sc = pad_adapter(lora_A.detach().to(dev), lora_B.detach().to(dev), scale.detach().reshape(-1).to(device=dev, dtype=torch.float32))
-        self.register_buffer("lora_A", A, persistent=True)
-        self.register_buffer("lora_B", B, persistent=True)
-        self.register_buffer("lora_scale", sc, persistent=True)
-        self._lora_ok = A.shape[0] <= LORA_MAX_RANK  # cleared as well when lora_down reports a shape as not covered
+            scale = torch.full((r,), float(scale))
+        if scale.numel() != r:
+            raise ValueError(f"scale must be one factor or one per adapter row ({r}), got {scale.numel()}")
+        return lora_A.detach().to(dev), lora_B.detach().to(dev), scale.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+
+    def _hold(self, A: torch.Tensor, B: torch.Tensor, scale: torch.Tensor, M: int, K: int) -> None:
+        """Register a padded adapter ``(A [R, K], B [M, R], scale [R])``, or a stack of them with the adapter index in front."""
+        for name, tensor in zip(self._adapter_buffers, (A, B, scale)):
+            self.register_buffer(name, tensor, persistent=True)
+        self._lora_cell = (M, K, int(A.shape[-2]))  # what lora_fused_ahead is asked about, beside the rows
+        self._lora_ok = A.shape[-2] <= LORA_MAX_RANK  # cleared as well when the down op reports a shape as not covered
         self._cast = {}  # activation dtype -> (A, B) in that dtype
+
+    def _init_adapter(self, lora_A: torch.Tensor, lora_B: torch.Tensor, scale, M: int, K: int, dev) -> None:
+        A, B, scale = self._checked_adapter(lora_A, lora_B, scale, M, K, dev)
+        self.rank = int(A.shape[0])
+        self._hold(*pad_adapter(A, B, scale), M, K)
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)  # device moves only
+        for name in self._adapter_buffers:
+            self._buffers[name] = self._buffers[name].to(self.qweight.device)
+        self._cast = {}
+        return self
 
     def _adapter(self, dtype: torch.dtype):
         # the adapter follows the activation dtype, as the bias does; the buffers stay as attached and every cast starts from them,
         # so a layer that meets two activation dtypes rounds the adapter once for each, never twice in a row
-        if self.lora_A.dtype == dtype:
-            return self.lora_A, self.lora_B
+        A, B = self._buffers[self._adapter_buffers[0]], self._buffers[self._adapter_buffers[1]]
+        if A.dtype == dtype:
+            return A, B
         cast = self._cast.get(dtype)
-        if cast is None or cast[0].device != self.lora_A.device:
-            cast = self._cast[dtype] = (self.lora_A.to(dtype), self.lora_B.to(dtype))
+        if cast is None or cast[0].device != A.device:
+            cast = self._cast[dtype] = (A.to(dtype), B.to(dtype))
         return cast
 
+    # -- forward -----------------------------------------------------------------------------------------------------
     def _adapter_delta(self, x: torch.Tensor) -> torch.Tensor:
         """The adapter term in torch, in f32: ``(x.float() @ A.float().T * scale) @ B.float().T``."""
         A, B = self._adapter(x.dtype)
-        return (x.float() @ A.float().t() * self.lora_scale) @ B.float().t()
+        return (x.float() @ A.float().t() * self._buffers[self._adapter_buffers[2]]) @ B.float().t()
+
+    def _adapter_in_torch(self, x: torch.Tensor, residual: Optional[torch.Tensor], *selection) -> torch.Tensor:
+        """The fallback: the base through the layer's own routes, base + delta in f32, one cast, then the epilogue in torch."""
+        y = (self._before_epilogue(x).float() + self._adapter_delta(x, *selection)).to(x.dtype)
+        return epilogue_in_torch(y, self.epilogue, residual)
+
+    def _adapter_forward(self, x: torch.Tensor, residual: Optional[torch.Tensor], rows: int, one: bool, many: bool, selection=()
+                         ) -> torch.Tensor:
+        """The ladder.  ``one`` / ``many``: whether the layer's one-row, respectively batched, adapter op may take this input.
+        ``selection``: the call's operands that follow the adapter's in all three ops (a stack's ids)."""
+        M, K, rank = self._lora_cell
+        if (one or many) and lora_fused_ahead(rows, M, K, rank):
+            down, gemv, batched = self._lora_ops
+            A, B = self._adapter(x.dtype)
+            xa = aligned16(x)  # the down op and both adapter ops read x in 16-byte pieces
+            try:
+                t = getattr(ext, down)(xa, A, self._buffers[self._adapter_buffers[2]], *selection)
+            except RuntimeError as exc:
+                if "not covered" not in str(exc):
+                    raise
+                self._lora_ok = False
+                return self._adapter_in_torch(x, residual, *selection)
+            # the base layer's measured exception holds here as well (the store loop is the same one)
+            in_kernel = residual is not None and self._residual_in_kernel(rows, K)
+            try:
+                y = getattr(ext, gemv if one else batched)(xa, *self._kernel_operands(x, residual if in_kernel else None), B, *selection, t)
+                return y if in_kernel or residual is None else y + residual
+            except RuntimeError as exc:  # a refusal clears the flag of the op that refused, whatever its wording
+                if "not available" not in str(exc) and "not covered" not in str(exc):
+                    raise
+                setattr(self, self._lora_route_flags[0 if one else 1], False)  # outside that op's coverage: the fallback from now on
+        return self._adapter_in_torch(x, residual, *selection)
 
 
 class LoRANF4Linear(LoRAAdapterMixin, FusedNF4Linear):
@@ -399,56 +489,20 @@ class LoRANF4Linear(LoRAAdapterMixin, FusedNF4Linear):
     def gate_up_from_packed(cls, *args, **kwargs):
         raise TypeError("LoRANF4Linear needs adapters: build a FusedNF4Linear.gate_up_from_packed(...) and pass it to gate_up_from_fused()")
 
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)  # device moves only
-        for name in ("lora_A", "lora_B", "lora_scale"):
-            self._buffers[name] = self._buffers[name].to(self.qweight.device)
-        self._cast = {}
-        return self
-
     # -- forward -----------------------------------------------------------------------------------------------------
-    def _adapter_in_torch(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
-        delta = self._adapter_delta(x)
-        if self.epilogue == EPILOGUE_SILU_MUL_PAIRS:
-            y = (self.quant_data.forward(x).float() + delta).to(x.dtype)
-            y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
-        else:
-            y = (FusedNF4Linear.forward(self, x).float() + delta).to(x.dtype)
-        return y if residual is None else y + residual
+    _lora_ops = ("lora_down", "gemv_nf4_lora", "gemm_nf4_lora")
+    _lora_route_flags = ("_fused_ok", "_small_ok")  # the parent's own fused ops are the same kernel families and are not tried again either
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         qd = self.quant_data
         K = x.shape[-1]
         self._fix_compute_dtype(x)
         rows = x.numel() // K if K else 0
+        one = many = False
         if self._lora_ok and rows >= 1 and K == self.in_features and x.dtype == qd.o_type and K % qd.blocksize == 0:
             one = rows == 1 and x.ndim in (2, 3) and self._fused_ok
-            many = (2 <= rows <= 64 and self._small_ok and x.dtype in (torch.float16, torch.bfloat16) and qd.blocksize == 64
-                    and K % 64 == 0)
-            if (one or many) and lora_fused_ahead(rows, int(qd.M), K, int(self.lora_A.shape[0])):
-                A, B = self._adapter(x.dtype)
-                x = aligned16(x)  # lora_down and both adapter ops read x in 16-byte pieces
-                try:
-                    t = ext.lora_down(x, A, self.lora_scale)
-                except RuntimeError as exc:
-                    if "not covered" not in str(exc):
-                        raise
-                    self._lora_ok = False
-                    return self._adapter_in_torch(x, residual)
-                # the parent's measured exception holds here as well (the store loop is the same one)
-                in_kernel = residual is not None and self._residual_in_kernel(rows, K)
-                try:
-                    op = ext.gemv_nf4_lora if one else ext.gemm_nf4_lora
-                    y = op(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual if in_kernel else None, self.epilogue, B, t)
-                    return y if in_kernel or residual is None else y + residual
-                except RuntimeError as exc:  # a refusal clears the flag of the op that refused, whatever its wording
-                    if "not available" not in str(exc) and "not covered" not in str(exc):
-                        raise
-                    if one:
-                        self._fused_ok = False  # outside the GEMV's fused coverage: the fallback from now on
-                    else:
-                        self._small_ok = False
-        return self._adapter_in_torch(x, residual)
+            many = self._small_ok and nf4_batched_covers(rows, K, qd.blocksize, x.dtype)
+        return self._adapter_forward(x, residual, rows, one, many)
 
     def extra_repr(self) -> str:
         return super().extra_repr() + f", lora_rank={self.rank}"
@@ -509,19 +563,7 @@ class AdapterSelection:
         return f"AdapterSelection(len={self._n}, capacity={self.capacity}, names={self.names})"
 
 
-def pad_adapter_to(lora_A: torch.Tensor, lora_B: torch.Tensor, scale: torch.Tensor, rank: int):
-    """:func:`pad_adapter` up to a given rank (zero rows of A, zero columns of B, zero factors): exact for the same reason."""
-    pad = rank - lora_A.shape[0]
-    if pad < 0:
-        raise ValueError(f"cannot pad an adapter of rank {lora_A.shape[0]} to {rank}")
-    if pad:
-        lora_A = torch.cat([lora_A, lora_A.new_zeros(pad, lora_A.shape[1])], 0)
-        lora_B = torch.cat([lora_B, lora_B.new_zeros(lora_B.shape[0], pad)], 1)
-        scale = torch.cat([scale, scale.new_zeros(pad)], 0)
-    return lora_A.contiguous(), lora_B.contiguous(), scale.contiguous()
-
-
-class MultiLoRANF4Linear(FusedNF4Linear):
+class MultiLoRANF4Linear(LoRAAdapterMixin, FusedNF4Linear):
     """A :class:`FusedNF4Linear` with a stack of LoRA adapters and one adapter id per activation row, read on the device from an
     :class:`AdapterSelection`: row ``b`` of ``forward(x, residual=None)`` is what a :class:`LoRANF4Linear` holding adapter
     ``selection.ids[b]`` gives for that row, and what the bare :class:`FusedNF4Linear` gives where the id names no adapter.
@@ -544,26 +586,13 @@ class MultiLoRANF4Linear(FusedNF4Linear):
         if not isinstance(selection, AdapterSelection):
             raise TypeError("selection must be an AdapterSelection")
         dev, M, K = self.qweight.device, int(quant_data.M), self.in_features
-        triples = []
-        for A, B, scale in adapters:
-            if A.ndim != 2 or B.ndim != 2 or A.shape[1] != K or B.shape != (M, A.shape[0]):
-                raise ValueError(f"adapter shapes {tuple(A.shape)} / {tuple(B.shape)} do not fit a [{M}, {K}] weight (need A [r, K] and B [M, r])")
-            r = int(A.shape[0])
-            if not torch.is_tensor(scale):
-                scale = torch.full((r,), float(scale))
-            if scale.numel() != r:
-                raise ValueError(f"scale must be one factor or one per adapter row ({r}), got {scale.numel()}")
-            triples.append((A.detach().to(dev), B.detach().to(dev), scale.detach().reshape(-1).to(device=dev, dtype=torch.float32)))
+        triples = [self._checked_adapter(A, B, scale, M, K, dev) for A, B, scale in adapters]
         self.ranks = [int(A.shape[0]) for A, _, _ in triples]
-        rank = max(self.ranks) + (-max(self.ranks) % LORA_RANK_MULTIPLE)
+        rank = padded_rank(max(self.ranks))
         dtype = triples[0][0].dtype
         padded = [pad_adapter_to(A.to(dtype), B.to(dtype), s, rank) for A, B, s in triples]
-        self.register_buffer("lora_A_stack", torch.stack([p[0] for p in padded]).contiguous(), persistent=True)
-        self.register_buffer("lora_B_stack", torch.stack([p[1] for p in padded]).contiguous(), persistent=True)
-        self.register_buffer("lora_scale_stack", torch.stack([p[2] for p in padded]).contiguous(), persistent=True)
+        self._hold(*(torch.stack(part).contiguous() for part in zip(*padded)), M, K)
         self.selection = selection
-        self._lora_ok = rank <= LORA_MAX_RANK  # cleared as well when lora_down_multi reports a shape as not covered
-        self._cast = {}  # activation dtype -> (A_stack, B_stack) in that dtype
 
     # -- constructors ------------------------------------------------------------------------------------------------
     @classmethod
@@ -600,37 +629,21 @@ class MultiLoRANF4Linear(FusedNF4Linear):
         """The common (padded) rank of the stack."""
         return int(self.lora_A_stack.shape[1])
 
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)  # device moves only; the selection is shared and stays where it was built
-        for name in ("lora_A_stack", "lora_B_stack", "lora_scale_stack"):
-            self._buffers[name] = self._buffers[name].to(self.qweight.device)
-        self._cast = {}
-        return self
-
     # -- forward -----------------------------------------------------------------------------------------------------
-    def _stacks(self, dtype: torch.dtype):
-        if self.lora_A_stack.dtype == dtype:
-            return self.lora_A_stack, self.lora_B_stack
-        cast = self._cast.get(dtype)
-        if cast is None or cast[0].device != self.lora_A_stack.device:
-            cast = self._cast[dtype] = (self.lora_A_stack.to(dtype), self.lora_B_stack.to(dtype))
-        return cast
+    _adapter_buffers = ("lora_A_stack", "lora_B_stack", "lora_scale_stack")  # moved with the weight; the selection is shared and stays
+    _lora_ops = ("lora_down_multi", "gemv_nf4_lora_multi", "gemm_nf4_lora_multi")
+    _lora_route_flags = ("_fused_ok", "_small_ok")
 
-    def _adapters_in_torch(self, x: torch.Tensor, residual: Optional[torch.Tensor], ids: torch.Tensor) -> torch.Tensor:
-        A, B = self._stacks(x.dtype)
+    def _adapter_delta(self, x: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+        """Each row's own adapter term in torch, in f32, as a loop over the stack with row masks."""
+        A, B = self._adapter(x.dtype)
         xf = x.float().reshape(-1, x.shape[-1])
         delta = None
         for a in range(self.n_adapters):  # row masks: nothing about ids is read on the host
             mask = (ids == a).to(torch.float32).unsqueeze(1)
             d = mask * ((xf @ A[a].float().t() * self.lora_scale_stack[a]) @ B[a].float().t())
             delta = d if delta is None else delta + d
-        delta = delta.reshape(*x.shape[:-1], delta.shape[-1])
-        if self.epilogue == EPILOGUE_SILU_MUL_PAIRS:
-            y = (self.quant_data.forward(x).float() + delta).to(x.dtype)
-            y = nn.functional.silu(y[..., 0::2]) * y[..., 1::2]
-        else:
-            y = (FusedNF4Linear.forward(self, x).float() + delta).to(x.dtype)
-        return y if residual is None else y + residual
+        return delta.reshape(*x.shape[:-1], delta.shape[-1])
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         qd = self.quant_data
@@ -640,33 +653,11 @@ class MultiLoRANF4Linear(FusedNF4Linear):
         ids = self.selection.ids
         if ids.numel() != rows:
             raise ValueError(f"the AdapterSelection holds {ids.numel()} ids, the batch has {rows} rows: call selection.set() with one id per row")
+        one = many = False
         if self._lora_ok and rows >= 1 and K == self.in_features and x.dtype == qd.o_type and K % qd.blocksize == 0:
             one = rows == 1 and x.ndim in (2, 3) and self._fused_ok
-            many = (2 <= rows <= 64 and self._small_ok and x.dtype in (torch.float16, torch.bfloat16) and qd.blocksize == 64
-                    and K % 64 == 0)
-            if (one or many) and lora_fused_ahead(rows, int(qd.M), K, self.rank):
-                A, B = self._stacks(x.dtype)
-                x = aligned16(x)  # lora_down_multi and both adapter ops read x in 16-byte pieces
-                try:
-                    t = ext.lora_down_multi(x, A, self.lora_scale_stack, ids)
-                except RuntimeError as exc:
-                    if "not covered" not in str(exc):
-                        raise
-                    self._lora_ok = False
-                    return self._adapters_in_torch(x, residual, ids)
-                in_kernel = residual is not None and self._residual_in_kernel(rows, K)  # the parent's measured exception
-                try:
-                    op = ext.gemv_nf4_lora_multi if one else ext.gemm_nf4_lora_multi
-                    y = op(x, qd._B_t, qd.absmax, qd.blocksize, qd._shape_list, qd.bias, residual if in_kernel else None, self.epilogue, B, ids, t)
-                    return y if in_kernel or residual is None else y + residual
-                except RuntimeError as exc:  # a refusal clears the flag of the op that refused, whatever its wording
-                    if "not available" not in str(exc) and "not covered" not in str(exc):
-                        raise
-                    if one:
-                        self._fused_ok = False
-                    else:
-                        self._small_ok = False
-        return self._adapters_in_torch(x, residual, ids)
+            many = self._small_ok and nf4_batched_covers(rows, K, qd.blocksize, x.dtype)
+        return self._adapter_forward(x, residual, rows, one, many, (ids,))
 
     def extra_repr(self) -> str:
         return super().extra_repr() + f", adapters={self.n_adapters}, lora_ranks={self.ranks}, common_rank={self.rank}"

@@ -12,7 +12,9 @@ one offset per weight::
   result equals ``gemv_nf4_fused`` on the expanded absmax bit for bit; more rows expand into a temporary (``ext.qlinear_nf4_nested``)
   unless ``set_small_batch_fused(model, True, nf4=True, nf4_wide=True)`` has routed 2..64 rows to ``ext.gemm_nf4_nested``, the fused
   matrix-core kernels reading the compressed statistics (the bits of ``gemm_nf4_fused`` on the expanded absmax).
-  :class:`LoRANestedNF4Linear` is such a layer with one LoRA adapter (``attach_lora`` / ``load_lora_adapter`` build it).
+  :class:`LoRANestedNF4Linear` is such a layer with one LoRA adapter (``attach_lora`` / ``load_lora_adapter`` build it): its holder
+  and forward ladder are :class:`~torch_bnb_fp4.fused.LoRAAdapterMixin`'s, its ops, route flags and operand list its own; which
+  cells the batched ops are routed for is written once, in ``quant_data.py``.
 
 :class:`NestedNF4Linear` is deliberately not a :class:`TorchFP4Linear`: ``fuse_gated_mlps``, ``attach_lora_adapters``
 (:class:`~torch_bnb_fp4.fused.MultiLoRANF4Linear`) and the tensor-parallel wrappers permute, concatenate or re-route rows, and a
@@ -29,7 +31,7 @@ from torch import nn
 from ._ext import ext
 from .dtypes import ScalarType
 from .fused import LoRAAdapterMixin
-from .quant_data import aligned16
+from .quant_data import aligned16, nf4_batched_covers, nf4_residual_in_kernel, nf4_small_cell
 
 NESTED_BLOCKSIZE = 256  # what every bitsandbytes file holds, and what the resident GEMV reads
 
@@ -162,46 +164,47 @@ class NestedNF4Linear(nn.Module):
             raise ValueError(f"NestedNF4Linear: the activation's last dim is {x.shape[-1]}, in_features is {K}")
         if x.numel() == 0:
             return torch.empty(x.shape[:-1] + (M,), dtype=x.dtype, device=x.device)
-        bias = self._bias_for(x)
         if x.numel() == K and x.dim() in (2, 3) and x.dtype in (torch.float16, torch.bfloat16, torch.float32):
             # the GEMV reads x in 16-byte pieces: an activation off that boundary is copied once (an address belongs to the call)
-            return ext.gemv_nf4_nested(aligned16(x), self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset,
-                                       self.nested_blocksize, self.blocksize, self._shape_list, bias,
-                                       None if residual is None else residual.contiguous(), 0)
+            return ext.gemv_nf4_nested(aligned16(x), *self._kernel_operands(x, residual))
         rows = x.numel() // K
         if self._batched_ok and self._batched_routed(rows, K, x.dtype):
             in_kernel = residual is not None and self._residual_in_kernel(rows, K)
             try:
                 # the call is made coverable, so that a refusal caught below is about the shape, which belongs to the layer
-                y = ext.gemm_nf4_nested(aligned16(x), self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset,
-                                        self.nested_blocksize, self.blocksize, self._shape_list, bias,
-                                        residual.contiguous() if in_kernel else None, 0)
+                y = ext.gemm_nf4_nested(aligned16(x), *self._kernel_operands(x, residual if in_kernel else None))
                 return y if in_kernel or residual is None else y + residual
             except RuntimeError as exc:
                 if "not covered" not in str(exc):
                     raise
                 self._batched_ok = False  # not tried again: the expand path from now on
-        return self._expand_path(x, bias, residual)
+        return self._expand_path(x, self._bias_for(x), residual)
 
     def _expand_path(self, x: torch.Tensor, bias: Optional[torch.Tensor], residual: Optional[torch.Tensor]) -> torch.Tensor:
         y = ext.qlinear_nf4_nested(x, self.qweight, self.absmax_u8, self.nested_absmax, self.nested_code, self.offset,
                                    self.nested_blocksize, self.out_features, self.in_features, self.blocksize, bias)
         return y if residual is None else y + residual
 
+    epilogue = 0  # the resident kernels are instantiated with the plain epilogue only
+
+    def _kernel_operands(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> tuple:
+        """The operands of a resident op between the activation and an adapter's own."""
+        return (self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset, self.nested_blocksize, self.blocksize,
+                self._shape_list, self._bias_for(x), None if residual is None else residual.contiguous(), self.epilogue)
+
+    def _before_epilogue(self, x: torch.Tensor) -> torch.Tensor:
+        """``W x + bias`` rounded to the activation dtype on this class's own routes: what a subclass adds a term of its own to."""
+        return NestedNF4Linear.forward(self, x)
+
     def _batched_covers(self, rows: int, K: int, dtype: torch.dtype) -> bool:
-        """FusedNF4Linear._batched_covers: what ``ext.gemm_nf4_nested`` is routed for."""
-        return 2 <= rows <= 64 and dtype in (torch.float16, torch.bfloat16) and self.blocksize == 64 and K % 64 == 0
+        return nf4_batched_covers(rows, K, self.blocksize, dtype)  # what ``ext.gemm_nf4_nested`` is routed for
 
     def _batched_routed(self, rows: int, K: int, dtype: torch.dtype) -> bool:
         """The cells the two switches open, the same ones as on an expanded :class:`TorchFP4Linear` (quant_data.py)."""
-        if not self._batched_covers(rows, K, dtype):
-            return False
-        small = rows <= 16 and K % 512 == 0
-        return self.small_batch_fused_nf4 if small else self.wide_batch_fused_nf4
+        return self._batched_covers(rows, K, dtype) and (self.small_batch_fused_nf4 if nf4_small_cell(rows, K) else self.wide_batch_fused_nf4)
 
     def _residual_in_kernel(self, rows: int, K: int) -> bool:
-        # FusedNF4Linear._residual_in_kernel for the plain epilogue: the one cell in which the fused add measured no gain
-        return not (rows > 32 and K >= 8192)
+        return nf4_residual_in_kernel(rows, K, self.epilogue)  # all but the one measured cell, where the add stays torch's
 
     def expand(self, use_codebook_dequant: bool = True):
         """The ordinary :class:`TorchFP4Linear` this layer decodes to (f32 absmax; same outputs, 4x the statistics)."""
@@ -239,52 +242,22 @@ class LoRANestedNF4Linear(LoRAAdapterMixin, NestedNF4Linear):
         """From a :class:`NestedNF4Linear` (shares its packed weight and statistics) and one adapter."""
         return cls(layer, lora_A, lora_B, scaling)
 
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)  # device moves only
-        self._cast = {}
-        return self
-
-    def _adapter_in_torch(self, x: torch.Tensor, residual: Optional[torch.Tensor]) -> torch.Tensor:
-        y = (NestedNF4Linear.forward(self, x).float() + self._adapter_delta(x)).to(x.dtype)
-        return y if residual is None else y + residual
+    _lora_ops = ("lora_down", "gemv_nf4_lora_nested", "gemm_nf4_lora_nested")
+    _lora_route_flags = ("_gemv_lora_ok", "_gemm_lora_ok")  # its own: _batched_ok belongs to the base path
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        from .fused import lora_fused_ahead
-
         K, M = self.in_features, self.out_features
         if x.shape[-1] != K:
             raise ValueError(f"LoRANestedNF4Linear: the activation's last dim is {x.shape[-1]}, in_features is {K}")
         if x.numel() == 0:
             return torch.empty(x.shape[:-1] + (M,), dtype=x.dtype, device=x.device)
         rows = x.numel() // K
+        one = many = False
         if self._lora_ok:
             one = (rows == 1 and x.dim() in (2, 3) and self._gemv_lora_ok
                    and x.dtype in (torch.float16, torch.bfloat16, torch.float32))
             many = self._gemm_lora_ok and self._batched_covers(rows, K, x.dtype)
-            if (one or many) and lora_fused_ahead(rows, M, K, int(self.lora_A.shape[0])):
-                A, B = self._adapter(x.dtype)
-                xc = aligned16(x)  # lora_down and both adapter ops read x in 16-byte pieces
-                try:
-                    t = ext.lora_down(xc, A, self.lora_scale)
-                except RuntimeError as exc:
-                    if "not covered" not in str(exc):
-                        raise
-                    self._lora_ok = False
-                    return self._adapter_in_torch(x, residual)
-                in_kernel = residual is not None and (one or self._residual_in_kernel(rows, K))
-                try:
-                    op = ext.gemv_nf4_lora_nested if one else ext.gemm_nf4_lora_nested
-                    y = op(xc, self.qweight.t(), self.absmax_u8, self.nested_absmax, self.nested_code, self.offset, self.nested_blocksize,
-                           self.blocksize, self._shape_list, self._bias_for(x), residual.contiguous() if in_kernel else None, 0, B, t)
-                    return y if in_kernel or residual is None else y + residual
-                except RuntimeError as exc:  # a refusal clears the flag of the op that refused, whatever its wording
-                    if "not available" not in str(exc) and "not covered" not in str(exc):
-                        raise
-                    if one:
-                        self._gemv_lora_ok = False
-                    else:
-                        self._gemm_lora_ok = False
-        return self._adapter_in_torch(x, residual)
+        return self._adapter_forward(x, residual, rows, one, many)
 
     def expand(self, use_codebook_dequant: bool = True):
         """The :class:`~torch_bnb_fp4.fused.LoRANF4Linear` over the expanded weight, with this layer's adapter."""

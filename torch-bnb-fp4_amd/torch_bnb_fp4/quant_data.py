@@ -59,6 +59,27 @@ def small_fp4_covers(rows: int, K: int, blocksize: int, dtype: torch.dtype) -> b
                  or (rows <= 8 and blocksize >= 32 and blocksize & (blocksize - 1) == 0 and K % blocksize == 0 and K % 32 == 0 and K <= 4096)))
 
 
+def nf4_batched_covers(rows: int, K: int, blocksize: int, dtype: torch.dtype) -> bool:
+    """The cells the one-pass NF4 matrix-core ops are routed for - plain, with an epilogue, with an adapter or over resident
+    statistics: 2..64 rows of fp16 / bf16 against a blocksize-64 weight with K % 64 == 0, the range in which they are ahead of
+    dequant + GEMM (profiles/nf4_wide_batch.json; the ops themselves take up to 128 rows, in two passes above 64)."""
+    return 2 <= rows <= 64 and dtype in (torch.float16, torch.bfloat16) and blocksize == 64 and K % 64 == 0
+
+
+def nf4_small_cell(rows: int, K: int) -> bool:
+    """Which of the two NF4 switches opens a covered cell: ``small_batch_fused_nf4`` (``gemm_small_nf4``) up to 16 rows with
+    K % 512 == 0, ``wide_batch_fused_nf4`` (``gemm_wide_nf4``) every other one."""
+    return rows <= 16 and K % 512 == 0
+
+
+def nf4_residual_in_kernel(rows: int, K: int, epilogue: int) -> bool:
+    """Whether an NF4 op adds the residual itself; where it does not, torch adds it to the op's output - T(t + r) either way.  The
+    one cell in which the fused add measured no gain is left out (profiles/nf4_fused_epilogues.json: 55.5 vs 56.5 us at 64 rows,
+    inside the replay-to-replay ranges): more than 32 rows against rows of 8192 and more weights with the plain epilogue (0; a
+    down projection).  The adapter ops share the store loop, so the exception holds for them as well; one row is never in it."""
+    return not (epilogue == 0 and rows > 32 and K >= 8192)
+
+
 class QuantData:
     def __init__(self, A: torch.Tensor, state, shape: Tuple[int, int], original_lin=None,
                  bias: Optional[torch.Tensor] = None, use_codebook_dequant: Optional[bool] = True,
@@ -208,10 +229,9 @@ class QuantData:
             # (the f32 GEMV takes any address itself; the 16-bit kernels take the aligned copy)
             return ext.gemm_small_fp4(A.contiguous() if A.dtype == torch.float32 else aligned16(A), self.A.t(), self.absmax, self.blocksize,
                                       self._shape_list, self.bias)
-        if self.small_batch_fused_nf4 and self.nf4 and 2 <= rows <= 16 and self.blocksize == 64 and K % 512 == 0 and (
-                A.dtype in (torch.float16, torch.bfloat16)):
-            return ext.gemm_small_nf4(aligned16(A), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
-        if self.wide_batch_fused_nf4 and self.nf4 and self.blocksize == 64 and K % 64 == 0 and (
-                17 <= rows <= 64 or (2 <= rows <= 16 and K % 512 != 0)) and A.dtype in (torch.float16, torch.bfloat16):
-            return ext.gemm_wide_nf4(aligned16(A), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias)
+        if self.nf4 and (self.small_batch_fused_nf4 or self.wide_batch_fused_nf4) and nf4_batched_covers(rows, K, self.blocksize, A.dtype):
+            small = nf4_small_cell(rows, K)
+            if self.small_batch_fused_nf4 if small else self.wide_batch_fused_nf4:
+                return (ext.gemm_small_nf4 if small else ext.gemm_wide_nf4)(aligned16(A), self.A.t(), self.absmax, self.blocksize,
+                                                                            self._shape_list, self.bias)
         return self.qlinear(A)
