@@ -325,6 +325,23 @@ FP4_HIP_API int fp4_hip_gemm_fused_nf4(const void *x, const uint8_t *packed, con
                                        void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
 
 /*
+ * fp4_hip_gemm_blocks_nf4: fp4_hip_gemm_fused_nf4 for the block sizes above 64 - the same operands, rounding and epilogues (none,
+ * residual add with `residual` allowed to alias `out`, silu(gate) * up over interleaved row pairs into T[B, M/2], M even), in a kernel
+ * of its own (csrc/gemm_blocks_nf4.hip) that chains the matrix-core steps of a quant block into one tile and applies absmax once per
+ * block:
+ *   out[b][r] = T( sum_k x[b][k] * code[nib(r,k)] * absmax[(r*K + k) / blocksize] + bias[r] ),  then the epilogue.
+ * Covered: 1..64 rows, blocksize a power of two in 128..4096 dividing K, fp16 / bf16, x and packed 16-byte aligned, M <= 2^30,
+ * K <= 2^24 (64-bit addressing: M * K may pass 2^32).  One pass over the packed weight, f32 accumulation in a fixed order:
+ * deterministic, no allocation, no synchronisation, capturable.  Everything else: FP4_ERR_UNSUPPORTED, nothing launched, out
+ * untouched - blocksize 64 among it, which is fp4_hip_gemm_fused_nf4's (each block size has one kernel).  Negative B or M, K <= 0,
+ * blocksize <= 0, an unknown epilogue, the gated one with an odd M ("even row count") or a null operand of a non-empty problem:
+ * FP4_ERR_INVALID_ARGUMENT.  FP4_OK without a launch for M == 0 or B == 0.  fp4_hip_set_variant("gemm_blocks_nf4", 1 | 2 | -1):
+ * 16 / 32 weight rows per workgroup / the heuristic.  An addition to ABI version 7.
+ */
+FP4_HIP_API int fp4_hip_gemm_blocks_nf4(const void *x, const uint8_t *packed, const float *absmax, const void *bias, const void *residual,
+                                        void *out, int64_t B, int64_t M, int64_t K, int blocksize, int dtype, int epilogue, void *stream);
+
+/*
  * LoRA adapters beside an NF4 weight (QLoRA serving; an adapter cannot be merged into 4-bit weights without re-quantising them):
  *   y = W_nf4 x + B (s * A x)        A : T[R, K],  B : T[M, R],  s = lora_alpha / r.        Not in the reference.
  * Two steps, both accumulated in f32 in a fixed order (deterministic, no atomics), neither allocating nor synchronising (capturable).

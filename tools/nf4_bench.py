@@ -19,6 +19,13 @@ one-pass kernel, under its own heuristic and with 16 / 32 weight rows per workgr
 bytes, for orientation.  (a), (b), (c) carry min / max over the replays; a cell is won where (a) beats (b) AND (c), each by more than
 the two full ranges together.  --revision names the tree the figures belong to.
 
+--blocks: the block sizes above 64 (profiles/nf4_blocks.json).  Per shape (the four decoder shapes and 4096 x 11008), block size (128 /
+256 / 1024, where it divides K: 11008 has no 1024; one dense weight quantised at each), dtype and row count (2 / 8 / 16 / 32 / 64), in one run on the same operands, through
+the torch ops: (a) gemm_nf4_blocks under its own heuristic and with 16 / 32 weight rows per workgroup forced
+(fp4_hip_set_variant("gemm_blocks_nf4", 1 / 2)); (b) qlinear_nf4, NF4 dequant + hipBLASLt - what these layers run without the switch,
+the baseline; (c) gemm_nf4_fused on a blocksize-64 quantisation of the same dense weight, for orientation only.  (a) and (b) carry
+min / max over the replays; a cell is ahead where (a) beats (b) by more than the two full ranges together.
+
 --fused: the decode epilogues (profiles/nf4_fused_epilogues.json), bf16, one run on the same operands.  (1) The plain calls the
 epilogue work touched - gemv_nf4, gemm_small_nf4 at 2 / 16 rows, gemm_wide_nf4 at 32 / 64 rows, 4096 x 4096 and 14336 x 4096 - through
 this tree's library and, with --baseline-lib, through another build of it (the parent commit's) loaded side by side; a cell is
@@ -206,6 +213,62 @@ def wide_batch(args):
     print(json.dumps({"device": torch.cuda.get_device_name(0), "revision": args.revision, "blocksize": BS, "launches_per_graph": args.launches,
                       "reps": args.reps, "cells_won": sum(c["beats_every_baseline_beyond_spread"] for c in cells), "cells_total": len(cells),
                       "cells": cells}))
+
+
+def blocks(args):
+    """--blocks: see the module docstring."""
+    L = lib()
+    dev = torch.device("cuda", 0)
+    s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    p_ = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def timed(fn):
+        replay = capture(lambda: [fn() for _ in range(args.launches)])
+        med, samples = time_replays(replay, args.reps, args.launches)
+        q = sorted(samples)
+        return {"us": round(med, 2), "min_us": round(q[0], 2), "max_us": round(q[-1], 2)}
+
+    def quantised(w16, bs):
+        packed = torch.empty(w16.numel() // 2, dtype=torch.uint8, device=dev)
+        absmax = torch.empty(w16.numel() // bs, dtype=torch.float32, device=dev)
+        if L.fp4_hip_quantize_blockwise_nf4(p_(w16), DT[torch.float16], p_(packed), p_(absmax), w16.numel(), bs, s()):
+            raise RuntimeError(L.fp4_hip_last_error().decode())
+        return packed, absmax
+
+    cells = []
+    for M, K in WIDE_SHAPES:
+        torch.manual_seed(0)
+        w16 = (torch.randn(M * K, device=dev) * 0.02).to(torch.float16)
+        packed64, absmax64 = quantised(w16, BS)
+        for bs in (128, 256, 1024):
+            if K % bs:  # 11008 = 1024 * 10.75: a block would straddle two rows, which no NF4 kernel here takes
+                continue
+            packed, absmax = quantised(w16, bs)
+            B_t = packed.view(-1, 1).t()
+            print(f"{M} x {K}, blocksize {bs}", file=sys.stderr, flush=True)
+            for dtype in (torch.bfloat16, torch.float16):
+                for rows in (2, 8, 16, 32, 64):
+                    x = torch.randn(rows, K, device=dev).to(dtype)
+                    new = lambda: pkg.ext.gemm_nf4_blocks(x, B_t, absmax, bs, [M, K], None, None, 0)  # noqa: E731
+                    a = timed(new)
+                    forced = {}
+                    for v in (1, 2):
+                        L.fp4_hip_set_variant(b"gemm_blocks_nf4", v)
+                        forced[v] = timed(new)["us"]
+                    L.fp4_hip_set_variant(b"gemm_blocks_nf4", -1)
+                    b = timed(lambda: pkg.ext.qlinear_nf4(x, packed, absmax, M, K, bs))
+                    c = timed(lambda: pkg.ext.gemm_nf4_fused(x, packed64.view(-1, 1).t(), absmax64, BS, [M, K], None, None, 0))
+                    spread = (a["max_us"] - a["min_us"]) + (b["max_us"] - b["min_us"])
+                    diff = (new().float() - pkg.ext.qlinear_nf4(x, packed, absmax, M, K, bs).float()).abs().max().item()
+                    cells.append({"M": M, "K": K, "blocksize": bs, "dtype": NAME[dtype], "rows": rows, "gemm_nf4_blocks": a,
+                                  "rows16_per_workgroup_us": forced[1], "rows32_per_workgroup_us": forced[2], "qlinear_nf4": b,
+                                  "blocksize64_gemm_nf4_fused_us": c["us"], "speedup_vs_qlinear_nf4": round(b["us"] / a["us"], 2),
+                                  "spread_us": round(spread, 2), "ahead_beyond_spread": bool(b["us"] - a["us"] > spread),
+                                  "max_abs_diff_vs_qlinear_nf4": diff})
+            del packed, absmax
+        del w16, packed64, absmax64
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "revision": args.revision, "launches_per_graph": args.launches, "reps": args.reps,
+                      "cells_ahead": sum(c["ahead_beyond_spread"] for c in cells), "cells_total": len(cells), "cells": cells}))
 
 
 def fused_epilogues(args):
@@ -638,7 +701,8 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--small-batch", action="store_true", help="the 2..16-row NF4 regime (profiles/nf4_small_batch.json)")
     ap.add_argument("--wide-batch", action="store_true", help="the 17..128-row NF4 regime (profiles/nf4_wide_batch.json)")
-    ap.add_argument("--revision", default="unknown", help="--wide-batch: the git revision the figures belong to, recorded as given")
+    ap.add_argument("--blocks", action="store_true", help="2..64 rows at block sizes 128 / 256 / 1024 (profiles/nf4_blocks.json)")
+    ap.add_argument("--revision", default="unknown", help="--wide-batch / --blocks: the git revision the figures belong to, recorded as given")
     ap.add_argument("--fused", action="store_true", help="the fused NF4 decode epilogues (profiles/nf4_fused_epilogues.json)")
     ap.add_argument("--baseline-lib", default=None, help="--fused / --nested: another build of libtorch_bnb_fp4_hip.so to time the plain calls of, side by side")
     ap.add_argument("--lora", action="store_true", help="LoRA adapters beside NF4 weights, fused against torch ops (profiles/nf4_lora.json)")
@@ -665,6 +729,8 @@ def main():
         return small_batch(args)
     if args.wide_batch:
         return wide_batch(args)
+    if args.blocks:
+        return blocks(args)
     L = lib()
     dev = torch.device("cuda", 0)
     s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731

@@ -75,6 +75,10 @@ extern "C" int fp4_hip_set_variant(const char *kernel, int variant) {
         fp4::set_wide_nf4_variant(variant);
         return FP4_OK;
     }
+    if (kernel && !std::strcmp(kernel, "gemm_blocks_nf4")) {
+        fp4::set_blocks_nf4_variant(variant);
+        return FP4_OK;
+    }
     if (kernel && !std::strcmp(kernel, "quantize")) {
         fp4::set_quantize_variant(variant);
         return FP4_OK;

@@ -29,5 +29,6 @@ void set_wide_variant(int v);          // gemm_wide_fp4.hip
 void set_quantize_variant(int v);      // quantize_fp4.hip
 void set_gemv_nf4_variant(int v);      // gemv_nf4.hip
 void set_wide_nf4_variant(int v);      // gemm_wide_nf4.hip
+void set_blocks_nf4_variant(int v);    // gemm_blocks_nf4.hip
 
 }  // namespace fp4

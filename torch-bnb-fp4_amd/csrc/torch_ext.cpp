@@ -16,7 +16,7 @@
 // Extra exports (not in the reference):
 //   * FP4:    gemv_fp4_bias, gemv_fp4_fused, gemm_small_fp4, gemm_small_fp4_fused, gemv_fp4_partial, quantize_fp4;
 //   * NF4 (bitsandbytes' second 4-bit code, same shapes and dispatch): dequantize_nf4, gemv_nf4, gemv_nf4_bias, qlinear_nf4,
-//     qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4, gemv_nf4_fused, gemm_nf4_fused, quantize_nf4;
+//     qlinear_nf4_bias, gemm_small_nf4, gemm_wide_nf4, gemv_nf4_fused, gemm_nf4_fused, gemm_nf4_blocks, quantize_nf4;
 //   * LoRA adapters beside an NF4 weight: lora_down, gemv_nf4_lora, gemm_nf4_lora; several adapters per batch, chosen per row on
 //     the device: lora_down_multi, gemv_nf4_lora_multi, gemm_nf4_lora_multi;
 //   * double-quantised absmax: absmax_unnest, absmax_nest, gemv_nf4_nested, gemm_nf4_nested, gemv_nf4_lora_nested,
@@ -759,6 +759,15 @@ torch::Tensor gemm_nf4_fused(torch::Tensor A, torch::Tensor B, torch::Tensor abs
                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
     return nf4_decode_op("gemm_nf4_fused", false, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue, nullptr, nullptr, nullptr);
 }
+// gemm_nf4_fused for the block sizes above 64 (fp4_hip_gemm_blocks_nf4: 1..64 rows, a power-of-two blocksize in 128..4096 dividing K)
+torch::Tensor gemm_nf4_blocks(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
+                              c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue) {
+    WeightCall w = weight_op({"gemm_nf4_blocks", 64}, A, B, &absmax, blocksize, Bshape, bias, residual, epilogue);
+    c10::DeviceGuard guard(A.device());
+    check_status(fp4_hip_gemm_blocks_nf4(A.data_ptr(), B.data_ptr<uint8_t>(), absmax.data_ptr<float>(), w.bias_ptr, w.res_ptr, w.out.data_ptr(),
+                                         w.rows, w.m, w.k, blocksize, w.dt, epilogue, current_stream(A)));
+    return std::move(w.out);
+}
 torch::Tensor gemv_nf4_lora(torch::Tensor A, torch::Tensor B, torch::Tensor absmax, int blocksize, std::vector<uint32_t> Bshape,
                             c10::optional<torch::Tensor> bias, c10::optional<torch::Tensor> residual, int epilogue, torch::Tensor lora_B,
                             torch::Tensor t) {
@@ -954,6 +963,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "1 = silu(gate) * up over interleaved rows");
     m.def("gemm_nf4_fused", &gemm_nf4_fused,
           "fused NF4 product for 1..128 rows with an epilogue: (A, B, absmax, blocksize, Bshape, bias|None, residual|None, epilogue)");
+    m.def("gemm_nf4_blocks", &gemm_nf4_blocks,
+          "gemm_nf4_fused for 1..64 rows against a blocksize of 128..4096: (A, B, absmax, blocksize, [m, k] of the weight, bias|None, "
+          "residual|None, epilogue)");
     m.def("lora_down", &lora_down, "LoRA down projection: (x, A [R, K], scale float32 [R]) -> t = scale * (x @ A^T), float32 [rows, R]");
     m.def("gemv_nf4_lora", &gemv_nf4_lora,
           "gemv_nf4_fused plus the adapter term lora_B @ t in f32 before the rounding: (A, B, absmax, blocksize, Bshape, bias|None, "

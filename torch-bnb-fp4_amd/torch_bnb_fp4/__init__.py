@@ -12,7 +12,9 @@ Both bitsandbytes 4-bit codes are decoded: ``quant_type="fp4"`` (the reference's
 NF4 runs a fused GEMV for one token and, behind ``set_small_batch_fused(model, True, nf4=True)`` (``QuantData.small_batch_fused_nf4``,
 off by default), a fused matrix-core kernel for 2..16 rows (``ext.gemm_small_nf4``; blocksize 64, in_features % 512 == 0, fp16 / bf16);
 behind ``nf4_wide=True`` (``QuantData.wide_batch_fused_nf4``, off by default) a one-pass kernel for 17..64 rows, and for 2..16 rows where
-in_features % 512 != 0 (``ext.gemm_wide_nf4``; blocksize 64, in_features % 64 == 0, fp16 / bf16); everything else is NF4 dequant + GEMM.
+in_features % 512 != 0 (``ext.gemm_wide_nf4``; blocksize 64, in_features % 64 == 0, fp16 / bf16); behind ``nf4_blocks=True``
+(``QuantData.blocks_batch_fused_nf4``, off by default) a kernel for 2..64 rows against the larger block sizes (``ext.gemm_nf4_blocks``; a
+power-of-two blocksize in 128..4096 dividing in_features, fp16 / bf16); everything else is NF4 dequant + GEMM.
 Double-quantised (nested) absmax - ``bnb_4bit_use_double_quant=True`` - loads either expanded to f32 once (the default: every kernel
 above applies) or, with ``load_fp4_layers(..., nested="resident")``, stays compressed on the device in :class:`NestedNF4Linear`, whose
 one-token path is a GEMV that reads the compressed statistics directly (:mod:`torch_bnb_fp4.nested`); the two NF4 switches above route

@@ -40,7 +40,7 @@ from torch import nn
 
 from ._ext import ext
 from .nn import QuantState, fp4_code, nf4_code
-from .quant_data import QuantData, aligned16, nf4_batched_covers, nf4_residual_in_kernel, small_fp4_covers
+from .quant_data import QuantData, aligned16, nf4_batched_covers, nf4_blocks_covers, nf4_residual_in_kernel, small_fp4_covers
 
 EPILOGUE_NONE = 0
 EPILOGUE_SILU_MUL_PAIRS = 1
@@ -254,7 +254,9 @@ class FusedNF4Linear(FusedFP4Linear):
     and torch's silu / mul / add.  An op that reports a shape as not covered is not tried again.  One measured cell is left out
     of the fused residual add: more than 32 rows against rows of 8192 and more weights with the plain epilogue (a down
     projection; profiles/nf4_fused_epilogues.json: 55.5 vs 56.5 us at 64 rows, inside the replay-to-replay ranges) - there the
-    op runs without the residual and torch adds it, the same bits."""
+    op runs without the residual and torch adds it, the same bits.  A weight of blocksize 128..4096 (a power of two dividing K) whose
+    ``quant_data.blocks_batch_fused_nf4`` is set (``set_small_batch_fused(model, True, nf4_blocks=True)``) runs 2..64 rows on
+    ``fp4_hip_gemm_blocks_nf4`` with the same epilogues in the kernel; without the switch it stays on the unfused sequence."""
 
     quant_type = "nf4"
 
@@ -263,16 +265,39 @@ class FusedNF4Linear(FusedFP4Linear):
         return nf4_code()
 
     _gemv_op = "gemv_nf4_fused"
-    _batched_op = "gemm_nf4_fused"
+
+    @classmethod
+    def from_linear(cls, layer) -> "FusedNF4Linear":
+        fused = super().from_linear(layer)
+        fused.quant_data.blocks_batch_fused_nf4 = layer.quant_data.blocks_batch_fused_nf4
+        return fused
+
+    @classmethod
+    def gate_up(cls, gate_layer, up_layer) -> "FusedNF4Linear":
+        fused = super().gate_up(gate_layer, up_layer)
+        fused.quant_data.blocks_batch_fused_nf4 = gate_layer.quant_data.blocks_batch_fused_nf4 and up_layer.quant_data.blocks_batch_fused_nf4
+        return fused
+
+    def _blocks(self) -> bool:
+        """A weight of a larger block size: its batched op is ``gemm_nf4_blocks``, behind ``quant_data.blocks_batch_fused_nf4``."""
+        return self.quant_data.blocksize != 64
+
+    @property
+    def _batched_op(self) -> str:  # each block size has one kernel
+        return "gemm_nf4_blocks" if self._blocks() else "gemm_nf4_fused"
 
     def _batched_covers(self, rows: int, K: int, dtype: torch.dtype) -> bool:
-        return nf4_batched_covers(rows, K, self.quant_data.blocksize, dtype)
+        qd = self.quant_data
+        if self._blocks():
+            return qd.blocks_batch_fused_nf4 and nf4_blocks_covers(rows, K, qd.blocksize, dtype)
+        return nf4_batched_covers(rows, K, qd.blocksize, dtype)
 
     def _gemv_wants_alignment(self) -> bool:
         return True  # fp4_hip_gemv_fused_nf4 has no generic kernel behind it: either epilogue refuses an address off 16 bytes
 
     def _residual_in_kernel(self, rows: int, K: int) -> bool:
-        return nf4_residual_in_kernel(rows, K, self.epilogue)  # all but the one measured cell, where the add stays torch's
+        # all but the one measured cell, where the add stays torch's (the larger block sizes keep the rule: the same store loop, the same bits)
+        return nf4_residual_in_kernel(rows, K, self.epilogue)
 
 
 LORA_RANK_MULTIPLE = 8  # the kernels read B and t in 16-byte units

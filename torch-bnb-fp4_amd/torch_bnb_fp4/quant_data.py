@@ -21,7 +21,9 @@ csrc/gemm_small_nf4.hip) instead of dequant + GEMM; every other input goes where
 ignores it.  ``wide_batch_fused_nf4`` (OFF by default) does the same for 17..64 rows, and for 2..16 rows where K % 512 != 0,
 with K % 64 == 0: they go to ``gemm_wide_nf4`` (csrc/gemm_wide_nf4.hip, one pass over the packed weight).  The op itself takes up
 to 128 rows (two passes above 64); those lose to dequant + GEMM on an MI355X and are not routed (profiles/nf4_wide_batch.json).
-Any other ``quant_type`` is refused.
+``blocks_batch_fused_nf4`` (OFF by default) is the switch of the larger block sizes: 2..64 rows against a weight whose blocksize is
+a power of two in 128..4096 go to ``gemm_nf4_blocks`` (csrc/gemm_blocks_nf4.hip); the other two switches leave such a weight on
+dequant + GEMM.  Any other ``quant_type`` is refused.
 
 Two extensions.  ``fuse_bias`` (ON by default) folds the post-GEMV ``out += bias`` into the kernel epilogue: the table above
 still holds and the result is bit-identical (``T(T(sum) + bias)``), there is just one launch fewer; ``fuse_bias=False`` runs the
@@ -66,6 +68,20 @@ def nf4_batched_covers(rows: int, K: int, blocksize: int, dtype: torch.dtype) ->
     return 2 <= rows <= 64 and dtype in (torch.float16, torch.bfloat16) and blocksize == 64 and K % 64 == 0
 
 
+def nf4_blocks_covers(rows: int, K: int, blocksize: int, dtype: torch.dtype) -> bool:
+    """The cells ``ext.gemm_nf4_blocks`` (csrc/gemm_blocks_nf4.hip: one scale application per quant block) is routed for: 2..64 rows
+    of fp16 / bf16 against a weight whose blocksize is a power of two in 128..4096 and divides K.  Blocksize 64 is
+    ``nf4_batched_covers``'s; one row is the GEMV's.  Measured against dequant + GEMM in profiles/nf4_blocks.json (five shapes, block
+    sizes 128 / 256 / 1024, 2 / 8 / 16 / 32 / 64 rows, both dtypes): ahead by more than both replay-to-replay ranges in 138 of 140 cells,
+    2.2x..5.0x up to 16 rows, 1.5x..2.4x at 32, 1.04x..1.5x at 64.  The two that are not - 64 bf16 rows against 4096 x 14336 at blocksize 128 (55.3 vs 57.6 us, ranges 2.9) and against
+    4096 x 11008 at blocksize 256 (43.4 vs 45.5 us, ranges 2.5) - stay on dequant + GEMM from 33 rows on; their fp16 twins and the
+    neighbouring block sizes are ahead by 2..4 us as well, just past their ranges.  The C entry point covers those cells all the same."""
+    if rows > 32 and dtype == torch.bfloat16 and (K, blocksize) in ((14336, 128), (11008, 256)):
+        return False
+    return (2 <= rows <= 64 and dtype in (torch.float16, torch.bfloat16) and 128 <= blocksize <= 4096
+            and blocksize & (blocksize - 1) == 0 and K % blocksize == 0)
+
+
 def nf4_small_cell(rows: int, K: int) -> bool:
     """Which of the two NF4 switches opens a covered cell: ``small_batch_fused_nf4`` (``gemm_small_nf4``) up to 16 rows with
     K % 512 == 0, ``wide_batch_fused_nf4`` (``gemm_wide_nf4``) every other one."""
@@ -85,7 +101,7 @@ class QuantData:
                  bias: Optional[torch.Tensor] = None, use_codebook_dequant: Optional[bool] = True,
                  allow_reduced_precision_linear: Optional[bool] = False, fuse_bias: bool = True,
                  small_batch_fused: bool = False, small_batch_fused_nf4: bool = False,
-                 wide_batch_fused_nf4: bool = False):
+                 wide_batch_fused_nf4: bool = False, blocks_batch_fused_nf4: bool = False):
         self.use_codebook_dequant = use_codebook_dequant
         state = expand_quant_state(state)  # a nested (double-quantised) state is expanded once: the kernels below take f32 absmax
         self.quant_type = check_quant_type(getattr(state, "quant_type", "fp4"))
@@ -113,6 +129,8 @@ class QuantData:
         # opt-in, NF4 weights only: 17..64 rows (and 2..16 where K % 512 != 0) go to the one-pass NF4 kernel; 65..128 rows, which the
         # kernel serves in two passes, measured slower than dequant + GEMM and stay there (profiles/nf4_wide_batch.json)
         self.wide_batch_fused_nf4 = wide_batch_fused_nf4
+        # opt-in, NF4 weights of blocksize 128..4096 only: 2..64 rows go to the block-chained NF4 kernel (``nf4_blocks_covers``)
+        self.blocks_batch_fused_nf4 = blocks_batch_fused_nf4
         # per-call constants of the decode path, built once (224 calls per token in a 7B model)
         self._B_t = A.t()
         self._shape_list = [int(shape[0]), int(shape[1])]
@@ -234,4 +252,6 @@ class QuantData:
             if self.small_batch_fused_nf4 if small else self.wide_batch_fused_nf4:
                 return (ext.gemm_small_nf4 if small else ext.gemm_wide_nf4)(aligned16(A), self.A.t(), self.absmax, self.blocksize,
                                                                             self._shape_list, self.bias)
+        if self.nf4 and self.blocks_batch_fused_nf4 and nf4_blocks_covers(rows, K, self.blocksize, A.dtype):
+            return ext.gemm_nf4_blocks(aligned16(A), self.A.t(), self.absmax, self.blocksize, self._shape_list, self.bias, None, 0)
         return self.qlinear(A)

@@ -136,7 +136,8 @@ def recursively_replace_with_fp4_linear(
         return module
 
 
-def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = False, nf4_wide: bool = False) -> int:
+def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = False, nf4_wide: bool = False,
+                          nf4_blocks: bool = False) -> int:
     """Route 2..128 activation rows of every :class:`TorchFP4Linear` below ``module`` to the fused small-batch kernels
     (``enabled=True``) or back to the reference's dispatch, dequant + GEMM for every batch > 1
     (torch_bnb_fp4/__init__.py:592,616-617; the default, so that a converted model behaves like the reference's).
@@ -148,7 +149,12 @@ def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = F
     sets every NF4 layer's ``wide_batch_fused_nf4``: 17..64 rows, and 2..16 rows where K % 512 != 0, go to the one-pass NF4
     kernel (``ext.gemm_wide_nf4``; blocksize 64, K % 64 == 0); an NF4 layer is counted once whichever of the two is set.
     A resident :class:`~torch_bnb_fp4.nested.NestedNF4Linear` (NF4, statistics compressed on the device) takes the two NF4 switches
-    the same way and is counted like an NF4 layer: the same cells then run ``ext.gemm_nf4_nested`` instead of its expand path."""
+    the same way and is counted like an NF4 layer: the same cells then run ``ext.gemm_nf4_nested`` instead of its expand path.
+    ``nf4_blocks=True`` sets every NF4 layer's ``blocks_batch_fused_nf4`` - the switch of the block sizes the other two leave on
+    dequant + GEMM: 2..64 rows against a blocksize of 128..4096 go to ``ext.gemm_nf4_blocks`` - on each :class:`TorchFP4Linear` and on
+    each :class:`~torch_bnb_fp4.fused.FusedNF4Linear` (the gate|up layers of :func:`fuse_gated_mlps` among them), whose batched
+    epilogues then run in that kernel; those fused layers are counted as well.  FP4 layers and resident nested layers ignore it."""
+    from .fused import FusedNF4Linear
     from .nested import NestedNF4Linear
 
     n = 0
@@ -161,16 +167,23 @@ def set_small_batch_fused(module: nn.Module, enabled: bool = True, nf4: bool = F
                     m.wide_batch_fused_nf4 = bool(enabled)
                 n += 1
             continue
+        if isinstance(m, FusedNF4Linear):
+            if nf4_blocks:
+                m.quant_data.blocks_batch_fused_nf4 = bool(enabled)
+                n += 1
+            continue
         if not isinstance(m, TorchFP4Linear):
             continue
         if not m.quant_data.nf4:
             m.quant_data.small_batch_fused = bool(enabled)
             n += 1
-        elif nf4 or nf4_wide:
+        elif nf4 or nf4_wide or nf4_blocks:
             if nf4:
                 m.quant_data.small_batch_fused_nf4 = bool(enabled)
             if nf4_wide:
                 m.quant_data.wide_batch_fused_nf4 = bool(enabled)
+            if nf4_blocks:
+                m.quant_data.blocks_batch_fused_nf4 = bool(enabled)
             n += 1
     return n
 
